@@ -30,6 +30,19 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X FP64 matrix spec; measured ceilings: DESIGN.md
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files of one run together
+
+
+def dump_outputs(path, arrays, suffix="", limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the timed path handed its caller in its last step, one <path>/<name><suffix>.npy per array in
+    float64, so that two builds can be compared output for output on the same seeded inputs."""
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the limit of {limit}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
 
 
 def live_traffic(config, kernel="k_front_dataflow"):
@@ -111,7 +124,13 @@ def main():
                     help="skip config.sharded_model: the measured multi-GPU prediction for BASELINE config 5 (per-part phases timed on this one GPU)")
     ap.add_argument("--strict-sharded", action="store_true",
                     help="exit with code 3 (after printing the metric line) when the sharded leg fails or times out; without it the failure only shows as config.sharded.error")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): the solution x, D of the "
+                         "factor in pivot order, the inertia counts and the factorisation's flag; rank r > 0 adds the suffix _rank<r>; "
+                         "--mode sharded: rank 0's x, inertia and flag of the sharded system")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under torchrun: start the N ranks as a CHILD (this process has not touched the GPU and never will) and pass
@@ -199,6 +218,9 @@ def main():
     resid = float(np.max(np.abs(M @ x - rhs)) / np.max(np.abs(rhs)))
     st = hip.stats()
     ok = (rc == 1) and hip.inertia == (n, m, 0, 0) and resid < 2e-6      # the run reaches 4.6e-7 (oracle: 1.8e-7): a regression of 5 x fails the line
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": x, "d": hip.diag(), "inertia": hip.inertia, "flag": [rc]},
+                     suffix=f"_rank{rank}" if rank else "", limit=DUMP_LIMIT_BYTES // world)
 
     if rank == 0:
         value = world * args.steps / elapsed
@@ -363,7 +385,9 @@ def bench_sharded(args, rank, world, local_rank, config):
     K = synth.augmented_matrix(prob, delta=1e-8)
     dev = torch.device("cuda", local_rank)
     rhs = np.random.default_rng(1234).normal(size=n + m)
-    steps, warm = max(args.steps, 5), max(args.warmup, 2)
+    # --mode sharded: this is the timed path of the line and takes --steps / --warmup as given; behind the replica line (--mode both)
+    # the sharded leg runs at least 5 + 2
+    steps, warm = (args.steps, args.warmup) if args.mode == "sharded" else (max(args.steps, 5), max(args.warmup, 2))
     # transport: the collectives inside the library on RCCL (okkt_dist_factor / okkt_dist_solve, what a Julia host would
     # call; default) or the phase-by-phase C ABI with torch.distributed collectives (OKKT_DIST_TRANSPORT=torch)
     transport = os.environ.get("OKKT_DIST_TRANSPORT", "abi")
@@ -399,6 +423,8 @@ def bench_sharded(args, rank, world, local_rank, config):
     torch.cuda.synchronize(); dist.barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, True)
     x = fetch()
+    if args.mode == "sharded" and args.dump_outputs and rank == 0:      # this is the timed path (with --mode both the replicas are)
+        dump_outputs(args.dump_outputs, {"x": x, "inertia": sh.inertia, "flag": [flag]})
     st_last = s0.stats()
     # the same system on ONE GPU (rank 0, an ordinary handle, behind the sharded run): what the strong-scaling number is a speed-up of
     single = None

@@ -1,5 +1,6 @@
 """CPU checks of the benchmark contract: `python bench.py --gpus N` starts its N ranks itself (one child, torch.distributed.run on
-127.0.0.1, nothing touches the GPU in the parent), and the committed JSON line of the round carries every field the driver reads."""
+127.0.0.1, nothing touches the GPU in the parent), and the committed JSON line of the round carries every field the driver reads.
+On the GPU: what `--dump-outputs DIR` writes is the last timed step's result on the seeded inputs."""
 import json
 import os
 import sys
@@ -56,3 +57,54 @@ def test_committed_bench_line_has_the_contract_fields():
     assert c["kind"] in ("port", "reference") and c["unit"] == d["unit"]
     assert d["parity"]["inertia_equal"] and d["parity"]["sign_D_equal"] and d["parity"]["rel_err_x"] <= d["parity"]["tolerance_x"]
     assert abs(d["value"] - d["n_gpus"] * d["steps"] / (d["ms_per_step"] * d["steps"] / 1e3)) < 1e-6 * d["value"]
+
+
+def test_steps_below_one_are_refused_before_any_work(monkeypatch):
+    import bench
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as exc:
+        bench.main()
+    assert exc.value.code == 2                                    # argparse's usage error: ms_per_step needs a timed step
+
+
+def test_dump_outputs_writes_float64_npy_files_within_the_limit(tmp_path):
+    import numpy as np
+
+    import bench
+    bench.dump_outputs(str(tmp_path / "out"), {"x": np.arange(4, dtype=np.float32), "flag": [1]}, suffix="_rank2")
+    assert sorted(os.listdir(tmp_path / "out")) == ["flag_rank2.npy", "x_rank2.npy"]
+    x = np.load(tmp_path / "out" / "x_rank2.npy")
+    assert x.dtype == np.float64 and x.tolist() == [0.0, 1.0, 2.0, 3.0]
+    assert np.load(tmp_path / "out" / "flag_rank2.npy").tolist() == [1.0]
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(9)}, limit=64)
+    assert not (tmp_path / "big").exists()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_the_last_timed_step(tmp_path):
+    import subprocess
+
+    import numpy as np
+
+    from onephase_jl_amd import synth
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "S-small", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+           "--no-kkt-level", "--no-live-pmc", "--no-sharded-model", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["d.npy", "flag.npy", "inertia.npy", "x.npy"]
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert all(a.dtype == np.float64 for a in got.values())
+    # rank 0's seeded inputs, rebuilt here: the dumped x solves that system
+    prob = synth.make_config("S-small", seed=0)
+    n, m = prob["n"], prob["m"]
+    M = synth.symmetrize_lower(synth.augmented_matrix(prob, delta=1e-8))
+    rhs = np.random.default_rng(1234).normal(size=n + m)
+    assert got["x"].shape == got["d"].shape == (n + m,)
+    assert np.max(np.abs(M @ got["x"] - rhs)) <= 1e-8 * np.max(np.abs(rhs))
+    assert got["inertia"].tolist() == [n, m, 0, 0] and got["flag"].tolist() == [1]
+    assert np.sum(got["d"] > 0) == n and np.sum(got["d"] < 0) == m
