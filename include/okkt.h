@@ -192,7 +192,9 @@ int64_t okkt_debug_dataflow_queue(int32_t nfronts, const int32_t* f, const int32
  *   solve : okkt_dist_solve_begin(rhs) -> okkt_dist_cv(buf, 0) [reduce(sum) to part 0] okkt_dist_cv(buf, 1) ->
  *           okkt_dist_solve_top (part 0) -> okkt_dist_x(buf, 0) on part 0 [broadcast] okkt_dist_x(buf, 1) ->
  *           okkt_dist_solve_end -> okkt_dist_x(sol, 2) [reduce(sum)]: the solution in original order.
- * Buffers must be zero before the pack calls (every slot has exactly one writer, the sum is exact). */
+ * Buffers must be zero before the pack calls (every slot has exactly one writer, the sum is exact).
+ * A partitioned plan takes fronts of at most 46 000 rows (its f x f buffers keep 32-bit local offsets): with nparts > 1 and a
+ * larger front okkt_dist_set_partition returns OKKT_ERR_INVALID (okkt_last_error says why); the single-GPU plan has no such limit. */
 int okkt_dist_set_partition(okkt_handle h, int nparts, int part_id);
 int okkt_dist_info(okkt_handle h, int64_t* cb_doubles, int64_t* cv_doubles, int64_t* n_boundary,
                    double* part_flops_out /* [nparts] or NULL */, double* top_flops_out);

@@ -46,6 +46,7 @@ int okkt_dist_set_partition(okkt_handle h, int nparts, int part_id) {
     numeric_release(h->N);
     h->numeric_ready = false;
   }
+  if (nparts > 1 && h->S.max_front > kPartedMaxFront) return solver_set_error(h, OKKT_ERR_INVALID, parted_front_error(h->S.max_front));
   h->factored = false;
   partition_tree(h->S, nparts);
   h->part_id = part_id;

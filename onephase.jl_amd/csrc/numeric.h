@@ -36,7 +36,7 @@ struct DevPlan {
   int64_t* cv_pos = nullptr;
   int64_t* aent_ptr = nullptr;
   int64_t* aent_src = nullptr;
-  int* aent_dst = nullptr;
+  int64_t* aent_dst = nullptr;   // lrow + lcol * f (symbolic.h): 64-bit, a front may pass 2^31 entries
   int* perm = nullptr;
   int* sched = nullptr;  // supernode ids grouped by (level, class); for the small classes: the ROOT of a task
   int* task_lo = nullptr;  // [supernode] first supernode of the task rooted there (small fronts): the workgroup runs task_lo[s] .. s in order
@@ -110,6 +110,14 @@ struct DfFront { int s, f, k; };
 // update task where the tile allows it; model_us = the simulated makespan
 void df_build_queue(const std::vector<DfFront>& fronts, int workers, int group, int rows_per_task, bool fuse_d, bool split_tu, std::vector<DfTask>& out, double* model_us,
                     bool fuse_tl = false, bool lockstep = false, bool multi_rows = true);
+
+// largest front order a partitioned plan (okkt_dist_*, dist.cpp) accepts: its f x f buffers keep 32-bit local offsets (f * f < 2^31);
+// single-GPU plans have no such limit
+constexpr int kPartedMaxFront = 46000;
+inline std::string parted_front_error(int64_t max_front) {
+  return "partitioned plans take fronts of at most " + std::to_string(kPartedMaxFront) + " rows (32-bit local offsets); the largest front has " +
+         std::to_string(max_front) + " rows: factor this system on one GPU";
+}
 
 constexpr int kDfHeadStride = 16;   // queue counter of a level (word 0; one cache line per level)
 constexpr int kCountSlots = 64, kCountStride = 16;

@@ -125,13 +125,13 @@ __global__ __launch_bounds__(TPB) void k_front_small(DevPlan P, const int* __res
     const int64_t e0 = P.aent_ptr[s], e1 = P.aent_ptr[s + 1];
     if (!P.has_dup) {
       for (int64_t e = e0 + tid; e < e1; e += TPB) {
-        const int dst = P.aent_dst[e];
+        const int dst = (int)P.aent_dst[e];      // f <= 136 here: the offset fits in 32 bits
         const int lc = dst / f, lr = dst - lc * f;
         F[lr + lc * ldf] = P.vals[P.aent_src[e]];
       }
     } else if (tid == 0) {
       for (int64_t e = e0; e < e1; ++e) {
-        const int dst = P.aent_dst[e];
+        const int dst = (int)P.aent_dst[e];
         const int lc = dst / f, lr = dst - lc * f;
         F[lr + lc * ldf] += P.vals[P.aent_src[e]];
       }
@@ -215,16 +215,16 @@ __device__ __forceinline__ void assemble_column(const DevPlan& P, int s, int pc,
   if (pc < k) {
     const int64_t e0 = P.aent_ptr[s];
     const int ne = (int)(P.aent_ptr[s + 1] - e0);
-    const int* dstv = P.aent_dst + e0;
+    const int64_t* dstv = P.aent_dst + e0;
     // range of this column's entries: precomputed on the host (two binary searches = ~25 dependent loads otherwise)
     const int64_t gcol = P.bigcol_base[s] + pc;
     const int lo = (int)(P.acol_lo[gcol] - e0);
     const int hi = pc + 1 < f ? (int)(P.acol_lo[gcol + 1] - e0) : ne;
-    const int base = pc * f + pc;     // dstv holds offsets in the front; entry (row, pc) sits at pc * f + row
+    const int64_t base = (int64_t)pc * f + pc;     // dstv holds offsets in the front; entry (row, pc) sits at pc * f + row (past 2^31 above 46 340 rows)
     if (!P.has_dup) {
-      for (int e = lo + lane; e < hi; e += 64) buf[dstv[e] - base] = P.vals[P.aent_src[e0 + e]];
+      for (int e = lo + lane; e < hi; e += 64) buf[(int)(dstv[e] - base)] = P.vals[P.aent_src[e0 + e]];
     } else if (lane == 0) {
-      for (int e = lo; e < hi; ++e) buf[dstv[e] - base] += P.vals[P.aent_src[e0 + e]];
+      for (int e = lo; e < hi; ++e) buf[(int)(dstv[e] - base)] += P.vals[P.aent_src[e0 + e]];
     }
     __threadfence_block();
     if (lane == 0) buf[0] += P.diagadd[col0 + pc];
@@ -361,15 +361,15 @@ __global__ __launch_bounds__(256) void k_big_assemble_chunked(DevPlan P, const i
   const int64_t gc = P.bigcol_base[s] + pc;
   if (pc < k) {
     const int64_t lo = P.acol_lo[gc], hi = pc + 1 < f ? P.acol_lo[gc + 1] : P.aent_ptr[s + 1];
-    const int cbase = pc * f;
+    const int64_t cbase = (int64_t)pc * f;
     if (!P.has_dup) {
       for (int64_t e = lo + lane; e < hi; e += 64) {
-        const int row = P.aent_dst[e] - cbase;
+        const int row = (int)(P.aent_dst[e] - cbase);
         if (row >= r0 && row < r1) base[row - r0] = P.vals[P.aent_src[e]];
       }
     } else if (lane == 0) {
       for (int64_t e = lo; e < hi; ++e) {
-        const int row = P.aent_dst[e] - cbase;
+        const int row = (int)(P.aent_dst[e] - cbase);
         if (row >= r0 && row < r1) base[row - r0] += P.vals[P.aent_src[e]];
       }
     }
@@ -1041,7 +1041,9 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
   if (getenv("OKKT_SB_TAIL_ROWS")) N.sb_tail_rows = atoi(getenv("OKKT_SB_TAIL_ROWS"));   // -1: at the end of the factorisation only
   N.group_one_rows = getenv("OKKT_GROUP_ONE_ROWS") ? atoi(getenv("OKKT_GROUP_ONE_ROWS")) : 4000;
   N.nnz_in = S.nnz_in;
-  if (S.max_front > 46000) return "front order exceeds the 32-bit local offset range";
+  // the single-GPU plan addresses every front with 64-bit offsets: no limit on the front order but the memory.  The partitioned plans
+  // keep f x f buffers (boundary exchange, dist.cpp) that have not been audited for offsets past 2^31: they refuse larger fronts
+  if (S.nparts > 1 && S.max_front > kPartedMaxFront) return parted_front_error(S.max_front);
   const int ns = S.nsuper;
   DevPlan& d = N.d;
   d.n = (int)S.n;
@@ -1432,7 +1434,7 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
         const int64_t e0 = S.aent_ptr[s], e1 = S.aent_ptr[s + 1];
         int64_t e = e0;
         for (int64_t pc = 0; pc < f; ++pc) {
-          while (e < e1 && (int64_t)S.aent_dst[e] < pc * f) ++e;
+          while (e < e1 && S.aent_dst[e] < pc * f) ++e;
           acol_lo[bigcol_base[s] + pc] = e;
         }
       }

@@ -584,7 +584,7 @@ static std::string analyze_one(int64_t n64, const int64_t* colptr, const int64_t
             if (s < 0) continue;
             const int64_t q = S.aent_ptr[s] + off[s]++;
             S.aent_src[q] = p;
-            S.aent_dst[q] = (int)(S.amap[p] - S.front_pos[s]);
+            S.aent_dst[q] = S.amap[p] - S.front_pos[s];
           }
         }
       });
@@ -594,7 +594,7 @@ static std::string analyze_one(int64_t n64, const int64_t* colptr, const int64_t
     // locates the entries of a column block by binary search
     {
       const std::string perr = parallel_pieces(ns, map_threads, [&](int64_t slo, int64_t shi, int) {
-        std::vector<std::pair<int, int64_t>> tmp;
+        std::vector<std::pair<int64_t, int64_t>> tmp;
         for (int64_t s = slo; s < shi; ++s) {
           const int64_t e0 = S.aent_ptr[s], e1 = S.aent_ptr[s + 1];
           bool sorted = true;

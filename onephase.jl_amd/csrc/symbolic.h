@@ -89,7 +89,7 @@ struct Symbolic {
   // the same, grouped by destination supernode (for the fused assemble-in-LDS kernel)
   std::vector<int64_t> aent_ptr; // [nsuper+1]
   std::vector<int64_t> aent_src; // source index into nzval
-  std::vector<int> aent_dst;     // local offset lrow + lcol * f inside the front
+  std::vector<int64_t> aent_dst; // local offset lrow + lcol * f inside the front (64-bit: f * f passes 2^31 above 46 340 rows)
 
   // level schedule: supernodes ordered by level
   int nlevels = 0;
