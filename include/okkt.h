@@ -86,7 +86,11 @@ typedef struct {
   int32_t small_front_max;    /* fronts of order <= this use the LDS-resident kernel; <=0 default */
   int32_t panel_nb;           /* block-column width in the big-front kernels; <=0 default */
   int32_t early_exit;         /* 1: a factorisation may stop once its inertia is decided wrong (see okkt_set_early_exit); default 0 */
-  int32_t reserved;
+  int32_t schur_dense_rows;   /* Schur KKT kinds only (OKKT_KKT_SCHUR, OKKT_KKT_SCHUR_DIRECT): rows of J kept out of J' Sigma J.
+                                 0 (default) off; > 0: a row with more than this many entries is dense; -1 automatic: dense when
+                                 nnz(row) > max(64, 10 sqrt(n)); other negative values are refused by okkt_kkt_create.  The k dense rows
+                                 J_d become the border of A = [[H + J_s' Sigma_s J_s + delta I, J_d'], [J_d, -diag(s_d / y_d)]] (order
+                                 n + k), whose Schur complement of the (2,2) block is Q.  Ignored by the other kinds and by level 1. */
 } okkt_opts;
 
 typedef struct {
@@ -317,6 +321,11 @@ int okkt_kkt_get_direction(okkt_kkt_handle k, double* dx, double* dy, double* ds
 int okkt_kkt_get_matrix(okkt_kkt_handle k, int64_t* dim_out, int64_t* nnz_out,
                         int64_t* colptr_out, int64_t* rowval_out, double* nzval_out);
 int okkt_kkt_get_schur_diag(okkt_kkt_handle k, double* out /* [n] */);
+/* the rows of J that opts.schur_dense_rows took out of the Schur complement (valid after okkt_kkt_set_structure): their count and,
+ * unless rows_out is NULL, the rows themselves (0-based, ascending).  The factorised matrix (okkt_kkt_get_matrix) then has order n + count,
+ * the inertia okkt_kkt_factor reports is its inertia and the flag is 1 exactly for (n, count, 0, 0), every pivot counted with tolerance 0;
+ * okkt_kkt_get_schur_diag and okkt_kkt_diag_min keep describing diag(Q) of the whole Q. */
+int okkt_kkt_get_dense_rows(okkt_kkt_handle k, int64_t* count_out, int64_t* rows_out /* [count] or NULL */);
 
 /* ---- Clever_Symmetric only -------------------------------------------------------
  * initialize!(::Clever_Symmetric_KKT_solver, it) = compute_indicies(get_jac(it)) (clever_symmetric.jl:53-61,

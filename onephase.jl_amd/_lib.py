@@ -44,7 +44,7 @@ class OkktOpts(C.Structure):
         ("small_front_max", C.c_int32),
         ("panel_nb", C.c_int32),
         ("early_exit", C.c_int32),
-        ("reserved", C.c_int32),
+        ("schur_dense_rows", C.c_int32),
     ]
 
 
@@ -199,6 +199,7 @@ SIGNATURES = {
     "okkt_kkt_compute_direction": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int32, _f64p, _f64p, _f64p, C.POINTER(OkktKktError)]),
     "okkt_kkt_get_matrix": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p, _f64p]),
     "okkt_kkt_get_schur_diag": (C.c_int, [_vp, _f64p]),
+    "okkt_kkt_get_dense_rows": (C.c_int, [_vp, _i64p, _i64p]),
     "okkt_kkt_compute_indicies": (C.c_int, [_vp, _f64p, C.POINTER(C.c_int64)]),
     "okkt_kkt_get_indicies": (C.c_int, [_vp, _i64p, _i64p, _i64p, _f64p, _f64p, _f64p, _f64p]),
     "okkt_kkt_set_rescale": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),

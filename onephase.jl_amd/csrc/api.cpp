@@ -53,13 +53,13 @@ int solver_ensure_numeric(okkt_solver_s* h) {
 }
 
 int solver_factor_device(okkt_solver_s* h, const double* d_vals, int64_t n, int64_t m, int sym_kind,
-                         okkt_inertia* out) {
+                         okkt_inertia* out, bool zero_tol) {
   int rc = solver_ensure_numeric(h);
   if (rc != OKKT_OK) return rc;
   if (n < 0 || m < 0 || n + m != h->S.n) return solver_set_error(h, OKKT_ERR_INVALID, "n + m does not match the analysed dimension");
   if (sym_kind != OKKT_SYM_DEFINITE && sym_kind != OKKT_SYM_SYMMETRIC) return solver_set_error(h, OKKT_ERR_INVALID, "unknown sym_kind");
   if (sym_kind == OKKT_SYM_DEFINITE && m != 0) return solver_set_error(h, OKKT_ERR_INVALID, ":definite requires m == 0 (julia.jl:30)");
-  const double tol = sym_kind == OKKT_SYM_DEFINITE ? 0.0 : h->opts.inertia_tol;
+  const double tol = (sym_kind == OKKT_SYM_DEFINITE || zero_tol) ? 0.0 : h->opts.inertia_tol;
   h->factored = false;
   h->N.early_check = h->early_exit;
   h->N.early_device = h->early_exit && h->last_failed;   // the previous factorisation failed the inertia: this one is a retry
@@ -148,6 +148,7 @@ int okkt_default_opts(okkt_opts* o) {
   o->small_front_max = 128;
   o->panel_nb = 128;
   o->early_exit = 0;
+  o->schur_dense_rows = 0;
   return OKKT_OK;
 }
 

@@ -113,6 +113,16 @@ __global__ __launch_bounds__(256) void k_assemble_schur_lds(int64_t n, int G, in
   }
 }
 
+// The border of the Schur system with dense rows, A = [[Q_s, J_d'], [J_d, -diag(s_d / y_d)]]: the CSC entries of J_d and the
+// diagonal of the (2,2) block through precomputed slots.  Runs after the Q_s assembly, which leaves zeros in these slots.
+__global__ void k_assemble_border(int64_t nnzJd, int64_t kd, const int64_t* __restrict__ bsrc, const int64_t* __restrict__ bslot,
+                                  const int64_t* __restrict__ drows, const int64_t* __restrict__ bdiag, const double* __restrict__ Jx,
+                                  const double* __restrict__ s, const double* __restrict__ y, double* __restrict__ A) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < nnzJd) A[bslot[t]] = Jx[bsrc[t]];
+  else if (t < nnzJd + kd) { const int64_t r = t - nnzJd, i = drows[r]; A[bdiag[r]] = -s[i] / y[i]; }
+}
+
 // schur_diag = diag(H) + sum_i J_ij^2 sig_i (kkt_system_solver.jl:296-300, eval.jl:89-100)
 __global__ void k_schur_diag(int64_t n, const int64_t* __restrict__ Jp, const int* __restrict__ Ji,
                              const double* __restrict__ Jx, const double* __restrict__ sig,
@@ -297,15 +307,30 @@ __global__ void k_clever_y(int64_t m, const int* __restrict__ row_grp, const dou
 // so a wave reads one contiguous run of values and indices; the partial sums meet by xor-shuffles inside the group.
 // The summation order is fixed by LPR alone (bitwise reproducible run to run).  No early return before the shuffles:
 // rows past the end are clamped and simply not stored.
+// skip: the group runs the shuffles of an empty row (a dense row whose dot k_dense_dot has computed)
 template <int LPR>
 __device__ __forceinline__ double seg_dot(const int64_t* __restrict__ ptr, const int* __restrict__ idx, const double* __restrict__ vals,
-                                          const double* __restrict__ x, int64_t row, int sub) {
+                                          const double* __restrict__ x, int64_t row, int sub, bool skip = false) {
   double a = 0.0;
   const int64_t p1 = ptr[row + 1];
-  for (int64_t p = ptr[row] + sub; p < p1; p += LPR) a += vals[p] * x[idx[p]];
+  for (int64_t p = skip ? p1 : ptr[row] + sub; p < p1; p += LPR) a += vals[p] * x[idx[p]];
 #pragma unroll
   for (int o = LPR / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
   return a;
+}
+// the dot of row `row` of J: from the segment, or with DR for a row flagged dense (dflag[row] = its index among the dense rows)
+// the value k_dense_dot left in dd.  Without DR this is seg_dot itself.
+template <int LPR, bool DR>
+__device__ __forceinline__ double seg_dot_dr(const int64_t* __restrict__ ptr, const int* __restrict__ idx, const double* __restrict__ vals,
+                                             const double* __restrict__ x, int64_t row, int sub, const int* __restrict__ dflag,
+                                             const double* __restrict__ dd) {
+  if constexpr (!DR) {
+    return seg_dot<LPR>(ptr, idx, vals, x, row, sub);
+  } else {
+    const int t = dflag[row];
+    const double a = seg_dot<LPR>(ptr, idx, vals, x, row, sub, t >= 0);
+    return t >= 0 ? dd[t] : a;
+  }
 }
 // hess_product (eval.jl:221-234) of row i: (L x)_i + (L' x)_i - diag(L)_i x_i with the lower-stored H in CSR and CSC order
 template <int LPR>
@@ -349,15 +374,17 @@ __global__ void k_diag_dom_margin(int64_t n, const double* __restrict__ hcol, co
   out[i] = (v != v) ? 1.0e308 : v;
 }
 
-template <int LPR>
+// DR: rows of J flagged dense take their dot from dd (k_dense_dot) instead of their own segment
+template <int LPR, bool DR = false>
 __global__ __launch_bounds__(256) void k_seg_spmv(int64_t nrows, const int64_t* __restrict__ ptr, const int* __restrict__ idx,
                                                   const double* __restrict__ vals, const double* __restrict__ x, const double* __restrict__ scale,
-                                                  const double* __restrict__ addv, double beta, double* __restrict__ y) {
+                                                  const double* __restrict__ addv, double beta, double* __restrict__ y,
+                                                  const int* __restrict__ dflag, const double* __restrict__ dd) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t row = t / LPR;
   const int sub = (int)(t % LPR);
   const int64_t rc = row < nrows ? row : nrows - 1;
-  double r = seg_dot<LPR>(ptr, idx, vals, x, rc, sub);
+  double r = seg_dot_dr<LPR, DR>(ptr, idx, vals, x, rc, sub, dflag, dd);
   if (sub == 0 && row < nrows) {
     if (scale) r *= scale[row];
     if (addv) r = r + beta * addv[row];
@@ -392,16 +419,17 @@ __global__ __launch_bounds__(256) void k_schur_resid(int64_t n, const int64_t* _
   if (sub == 0 && row < n) res[i] = rhs[i] - (jac + (hx + delta * dx[i]));
 }
 // dy, ds from J dx (schur.jl:113-116); direct = 1: ds = (comp_r - dy .* s) ./ y (schur_direct.jl:54-56), y, s, sig of the CURRENT iterate
-template <int LPR>
+template <int LPR, bool DR = false>
 __global__ __launch_bounds__(256) void k_schur_dyds(int64_t m, const int64_t* __restrict__ Jrp, const int* __restrict__ Jrj, const double* __restrict__ Jcsr,
                                                     const double* __restrict__ dx, const double* __restrict__ rP, const double* __restrict__ rC,
                                                     const double* __restrict__ y, const double* __restrict__ s, const double* __restrict__ sig, int direct,
-                                                    double* __restrict__ dy, double* __restrict__ ds) {
+                                                    double* __restrict__ dy, double* __restrict__ ds, const int* __restrict__ dflag,
+                                                    const double* __restrict__ dd) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t row = t / LPR;
   const int sub = (int)(t % LPR);
   const int64_t i = row < m ? row : m - 1;
-  const double Jdx = seg_dot<LPR>(Jrp, Jrj, Jcsr, dx, i, sub);
+  const double Jdx = seg_dot_dr<LPR, DR>(Jrp, Jrj, Jcsr, dx, i, sub, dflag, dd);
   if (sub == 0 && row < m) {
     const double dyi = -(Jdx - (rP[i] + rC[i] / y[i])) * sig[i];
     dy[i] = dyi;
@@ -429,16 +457,17 @@ __global__ __launch_bounds__(256) void k_err_dual(int64_t n, const int64_t* __re
   block_max_store<2>(v, part);
 }
 // primal and complementarity blocks: |J dx - ds - primal_r|, |s dy + y ds - comp_r|, |primal_r|, |comp_r|
-template <int LPR>
+template <int LPR, bool DR = false>
 __global__ __launch_bounds__(256) void k_err_pc(int64_t m, const int64_t* __restrict__ Jrp, const int* __restrict__ Jrj, const double* __restrict__ Jcsr,
                                                 const double* __restrict__ dx, const double* __restrict__ ds, const double* __restrict__ dy,
                                                 const double* __restrict__ s, const double* __restrict__ y, const double* __restrict__ rP,
-                                                const double* __restrict__ rC, double* __restrict__ part) {
+                                                const double* __restrict__ rC, double* __restrict__ part, const int* __restrict__ dflag,
+                                                const double* __restrict__ dd) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t row = t / LPR;
   const int sub = (int)(t % LPR);
   const int64_t i = row < m ? row : m - 1;
-  const double Jdx = seg_dot<LPR>(Jrp, Jrj, Jcsr, dx, i, sub);
+  const double Jdx = seg_dot_dr<LPR, DR>(Jrp, Jrj, Jcsr, dx, i, sub, dflag, dd);
   double v[4] = {0.0, 0.0, 0.0, 0.0};
   if (sub == 0 && row < m) {
     v[0] = fabs(Jdx - ds[i] - rP[i]);
@@ -511,11 +540,45 @@ __global__ void k_form_prep(int64_t nnzJ, int64_t nnzH, int64_t n, int64_t m, co
   }
 }
 
+// Dots of the kd dense rows of J with nx vectors, for one or two value arrays (va1 = NULL: one).  A row of 10^4 - 10^5 entries in
+// one lane group of the row kernels is a chain of thousands of dependent gathers; here workgroup (c, r, pair) owns chunk c of
+// kDenseChunk entries of dense row r: pair = a * nx + v takes the values va_a and the vector x + v * xstride.  The partial of a
+// workgroup has a fixed order (strided lanes, xor tree, four waves), k_dense_dot_sum adds the chunks in order: no atomics,
+// bitwise reproducible.  dd[pair * kd + r].
+constexpr int kDenseChunk = 4096;
+__global__ __launch_bounds__(256) void k_dense_dot(int64_t kd, int64_t nchunk, int nx, const int64_t* __restrict__ drows, const int64_t* __restrict__ Jrp,
+                                                   const int* __restrict__ Jrj, const double* __restrict__ va0, const double* __restrict__ va1,
+                                                   const double* __restrict__ x, int64_t xstride, double* __restrict__ part) {
+  __shared__ double sh[4];
+  const int64_t r = (int64_t)blockIdx.x / nchunk, c = (int64_t)blockIdx.x % nchunk;
+  const int pr = (int)blockIdx.y;
+  const double* __restrict__ vals = pr < nx ? va0 : va1;
+  const double* __restrict__ xv = x + (int64_t)(pr % nx) * xstride;
+  const int64_t i = drows[r];
+  const int64_t p0 = Jrp[i] + c * kDenseChunk, p1 = min(Jrp[i + 1], p0 + (int64_t)kDenseChunk);
+  double a = 0.0;
+  for (int64_t p = p0 + threadIdx.x; p < p1; p += 256) a += vals[p] * xv[Jrj[p]];
+  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) part[((int64_t)pr * kd + r) * nchunk + c] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+__global__ void k_dense_dot_sum(int64_t total, int64_t nchunk, const double* __restrict__ part, double* __restrict__ dd) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  double v = 0.0;
+  for (int64_t c = 0; c < nchunk; ++c) v += part[t * nchunk + c];
+  dd[t] = v;
+}
+// the most vector / value pairs one call of dense_dots takes: okkt_kkt_compute_directions' 16 right-hand sides times two value arrays
+constexpr int kDenseMaxPairs = 32;
+
 inline int pick_lpr(int64_t nnz, int64_t rows) {
   const double avg = rows > 0 ? (double)nnz / (double)rows : 1.0;
   return avg <= 5.0 ? 4 : (avg <= 10.0 ? 8 : (avg <= 24.0 ? 16 : (avg <= 56.0 ? 32 : 64)));
 }
 inline dim3 seg_grid(int64_t rows, int lpr) { return dim3((unsigned)std::max<int64_t>(1, (rows * lpr + 255) / 256)); }
+#define NO_DR (const int*)nullptr, (const double*)nullptr
 #define SEG_LAUNCH(KERN, lpr, rows, st, ...)                                                                   \
   do {                                                                                                         \
     const int64_t rows__ = (rows);                                                                             \
@@ -526,6 +589,18 @@ inline dim3 seg_grid(int64_t rows, int lpr) { return dim3((unsigned)std::max<int
         case 32: hipLaunchKernelGGL((KERN<32>), seg_grid(rows__, 32), dim3(256), 0, st, __VA_ARGS__); break;   \
         default: hipLaunchKernelGGL((KERN<64>), seg_grid(rows__, 64), dim3(256), 0, st, __VA_ARGS__); break;   \
       }                                                                                                        \
+  } while (0)
+// the same with the dense-row variant of a row kernel (the last two arguments: k->dflag and the dots of k_dense_dot)
+#define SEG_LAUNCH_DR(KERN, lpr, rows, st, ...)                                                                      \
+  do {                                                                                                               \
+    const int64_t rows__ = (rows);                                                                                   \
+    if (rows__ > 0) switch (lpr) {                                                                                   \
+        case 4: hipLaunchKernelGGL((KERN<4, true>), seg_grid(rows__, 4), dim3(256), 0, st, __VA_ARGS__); break;      \
+        case 8: hipLaunchKernelGGL((KERN<8, true>), seg_grid(rows__, 8), dim3(256), 0, st, __VA_ARGS__); break;      \
+        case 16: hipLaunchKernelGGL((KERN<16, true>), seg_grid(rows__, 16), dim3(256), 0, st, __VA_ARGS__); break;   \
+        case 32: hipLaunchKernelGGL((KERN<32, true>), seg_grid(rows__, 32), dim3(256), 0, st, __VA_ARGS__); break;   \
+        default: hipLaunchKernelGGL((KERN<64, true>), seg_grid(rows__, 64), dim3(256), 0, st, __VA_ARGS__); break;   \
+      }                                                                                                              \
   } while (0)
 
 int kk_fail(okkt_kkt_s* k, int code, const std::string& msg) { k->err = msg; return code; }
@@ -545,13 +620,25 @@ int kk_reduce(okkt_kkt_s* k, int64_t n, const double* v, int mode, double* host_
 
 // J x, J' v, H x on the handle's stream (segmented products; J x and H x read the CSR-ordered copies of form_system)
 void spmv_J(okkt_kkt_s* k, const double* x, double* y) {
-  SEG_LAUNCH(k_seg_spmv, k->lprJr, k->m, kk_stream(k), k->m, k->Jrp, k->Jrj, k->Jcsr, x, (const double*)nullptr, (const double*)nullptr, 0.0, y);
+  SEG_LAUNCH(k_seg_spmv, k->lprJr, k->m, kk_stream(k), k->m, k->Jrp, k->Jrj, k->Jcsr, x, (const double*)nullptr, (const double*)nullptr, 0.0, y, NO_DR);
 }
 void spmv_JT(okkt_kkt_s* k, const double* Jx, const double* v, double* y) {
-  SEG_LAUNCH(k_seg_spmv, k->lprJc, k->n, kk_stream(k), k->n, k->Jp, k->Ji, Jx, v, (const double*)nullptr, (const double*)nullptr, 0.0, y);
+  SEG_LAUNCH(k_seg_spmv, k->lprJc, k->n, kk_stream(k), k->n, k->Jp, k->Ji, Jx, v, (const double*)nullptr, (const double*)nullptr, 0.0, y, NO_DR);
 }
 void spmv_H(okkt_kkt_s* k, const double* x, double* y) {
   SEG_LAUNCH(k_seg_hess, k->lprH, k->n, kk_stream(k), k->n, k->Hrp, k->Hrj, k->Hcsr, k->Hp, k->Hi, k->Hx, k->Hdiag, x, y);
+}
+// OKKT_DENSE_DOT=0 in the environment: the row kernels go through the dense rows themselves (the A/B switch of k_dense_dot)
+bool dense_dot_on(const okkt_kkt_s* k) {
+  static const bool on = !(getenv("OKKT_DENSE_DOT") && atoi(getenv("OKKT_DENSE_DOT")) == 0);
+  return k->kd > 0 && on;
+}
+// the dots of the dense rows of J with the nx vectors x + v * xstride, for the values va0 and (unless NULL) va1: k->ddot[(a * nx + v) * kd + r]
+void dense_dots(okkt_kkt_s* k, hipStream_t st, const double* va0, const double* va1, const double* x, int64_t xstride, int nx) {
+  const int npair = va1 ? 2 * nx : nx;
+  hipLaunchKernelGGL(k_dense_dot, dim3((unsigned)(k->kd * k->dchunks), (unsigned)npair), dim3(256), 0, st, k->kd, k->dchunks, nx, k->drows, k->Jrp,
+                     k->Jrj, va0, va1, x, xstride, k->dpart);
+  hipLaunchKernelGGL(k_dense_dot_sum, grid1(npair * k->kd), dim3(256), 0, st, npair * k->kd, k->dchunks, k->dpart, k->ddot);
 }
 
 }  // namespace
@@ -581,6 +668,7 @@ int okkt_kkt_create(okkt_kkt_handle* out, const okkt_opts* opts, int kkt_kind) {
   if (!out) return OKKT_ERR_INVALID;
   *out = nullptr;
   if (kkt_kind != OKKT_KKT_SCHUR && kkt_kind != OKKT_KKT_SYMMETRIC && kkt_kind != OKKT_KKT_CLEVER_SYMMETRIC && kkt_kind != OKKT_KKT_SCHUR_DIRECT) return OKKT_ERR_INVALID;
+  if ((kkt_kind == OKKT_KKT_SCHUR || kkt_kind == OKKT_KKT_SCHUR_DIRECT) && opts && opts->schur_dense_rows < -1) return OKKT_ERR_INVALID;
   okkt_kkt_s* k = new (std::nothrow) okkt_kkt_s();
   if (!k) return OKKT_ERR_ALLOC;
   k->kind = kkt_kind;
@@ -684,10 +772,20 @@ int okkt_kkt_set_structure(okkt_kkt_handle k, int64_t n, int64_t m, const int64_
       UPL(mapH, mapH); UPL(mapJ, mapJ); UPL(diagA, diagA);
       k->Ap = Ap; k->Ai = Ai;
     } else {
-      // lower triangle of J' S J + H: pairs (a >= b) of the columns present in each row of J
-      k->dimA = n;
+      // dense rows of J (okkt_opts.schur_dense_rows) stay out of J' S J: they border it, A = [[Q_s, J_d'], [J_d, -diag(s_d / y_d)]]
+      std::vector<int> dflag(m, -1);
+      k->h_drows.clear();
+      if (const int32_t dro = k->ls->opts.schur_dense_rows) {
+        const double thr = dro > 0 ? (double)dro : std::max(64.0, 10.0 * std::sqrt((double)n));
+        for (int64_t i = 0; i < m; ++i)
+          if ((double)(Jrp[i + 1] - Jrp[i]) > thr) { dflag[i] = (int)k->h_drows.size(); k->h_drows.push_back(i); }
+      }
+      const int64_t kd = k->kd = (int64_t)k->h_drows.size();
+      // lower triangle of J_s' S J_s + H: pairs (a >= b) of the columns present in each sparse row of J
+      k->dimA = n + kd;
       std::vector<std::vector<int>> cols(n);   // per column b: rows a >= b
       for (int64_t i = 0; i < m; ++i)
+        if (dflag[i] < 0)
         for (int64_t p = Jrp[i]; p < Jrp[i + 1]; ++p)
           for (int64_t q = Jrp[i]; q < Jrp[i + 1]; ++q)
             if (Jrj[p] >= Jrj[q]) cols[Jrj[q]].push_back(Jrj[p]);
@@ -697,11 +795,27 @@ int okkt_kkt_set_structure(okkt_kkt_handle k, int64_t n, int64_t m, const int64_
         std::sort(cols[j].begin(), cols[j].end());
         cols[j].erase(std::unique(cols[j].begin(), cols[j].end()), cols[j].end());
       }
-      std::vector<int64_t> Ap(n + 1, 0), Ai, diagA(n);
-      for (int64_t j = 0; j < n; ++j) { Ap[j + 1] = Ap[j] + (int64_t)cols[j].size(); }
-      Ai.resize(Ap[n]);
-      for (int64_t j = 0; j < n; ++j) { std::copy(cols[j].begin(), cols[j].end(), Ai.begin() + Ap[j]); diagA[j] = Ap[j]; }
-      k->nnzA = Ap[n];
+      // column j < n: the pattern of Q_s, then the border rows n + r of the dense rows r holding column j; column n + r: its diagonal
+      std::vector<int64_t> Ap(n + kd + 1, 0), Ai, diagA(n), bsrc, bslot, bdiag(kd);
+      for (int64_t j = 0; j < n; ++j) {
+        int64_t nb = 0;
+        if (kd) for (int64_t p = Jp[j]; p < Jp[j + 1]; ++p) nb += dflag[Ji[p]] >= 0;
+        Ap[j + 1] = Ap[j] + (int64_t)cols[j].size() + nb;
+      }
+      for (int64_t r = 0; r < kd; ++r) Ap[n + r + 1] = Ap[n + r] + 1;
+      Ai.resize(Ap[n + kd]);
+      for (int64_t j = 0; j < n; ++j) {
+        std::copy(cols[j].begin(), cols[j].end(), Ai.begin() + Ap[j]);
+        diagA[j] = Ap[j];
+        if (kd) {
+          int64_t e = Ap[j] + (int64_t)cols[j].size();
+          for (int64_t p = Jp[j]; p < Jp[j + 1]; ++p)   // rows ascending within the column: border rows ascending
+            if (dflag[Ji[p]] >= 0) { bsrc.push_back(p); bslot.push_back(e); Ai[e++] = n + dflag[Ji[p]]; }
+        }
+      }
+      for (int64_t r = 0; r < kd; ++r) { Ai[Ap[n + r]] = n + r; bdiag[r] = Ap[n + r]; }
+      k->nnzA = Ap[n + kd];
+      k->nnzJd = (int64_t)bsrc.size();
       std::vector<int64_t> qh(k->nnzA, -1);
       auto slot = [&](int a, int bcol) -> int64_t {
         auto it = std::lower_bound(Ai.begin() + Ap[bcol], Ai.begin() + Ap[bcol + 1], (int64_t)a);
@@ -722,13 +836,14 @@ int okkt_kkt_set_structure(okkt_kkt_handle k, int64_t n, int64_t m, const int64_
         for (int64_t bcol = 0; bcol < n; ++bcol)
           for (int64_t p = Jp[bcol]; p < Jp[bcol + 1]; ++p) {
             const int i = Ji[p];
+            if (dflag[i] >= 0) { seg_q[p] = Jrp[i + 1]; seg_t[p] = nterms; continue; }   // a dense row: an empty segment
             seg_q[p] = cur[i]++;
             seg_t[p] = nterms;
             nterms += Jrp[i + 1] - seg_q[p];
           }
         seg_t[nnzJ] = nterms;
         std::vector<uint16_t> tslot((size_t)nterms);
-        std::vector<int> pos(n, -1);
+        std::vector<int> pos(n + kd, -1);
         for (int64_t bcol = 0; bcol < n; ++bcol) {
           for (int64_t e = Ap[bcol]; e < Ap[bcol + 1]; ++e) pos[Ai[e]] = (int)(e - Ap[bcol]);
           for (int64_t p = Jp[bcol]; p < Jp[bcol + 1]; ++p) {
@@ -741,6 +856,7 @@ int okkt_kkt_set_structure(okkt_kkt_handle k, int64_t n, int64_t m, const int64_
         // contribution lists per Q entry (columns of Q too long for LDS: one thread per entry, k_assemble_schur)
         std::vector<int64_t> qptr(k->nnzA + 1, 0);
         for (int64_t i = 0; i < m; ++i)
+          if (dflag[i] < 0)
           for (int64_t p = Jrp[i]; p < Jrp[i + 1]; ++p)
             for (int64_t q = Jrp[i]; q < Jrp[i + 1]; ++q)
               if (Jrj[p] >= Jrj[q]) ++qptr[slot(Jrj[p], Jrj[q]) + 1];
@@ -748,6 +864,7 @@ int okkt_kkt_set_structure(okkt_kkt_handle k, int64_t n, int64_t m, const int64_
         std::vector<int> qa(qptr[k->nnzA]), qb(qptr[k->nnzA]), qi(qptr[k->nnzA]);
         std::vector<int64_t> fill(qptr.begin(), qptr.end() - 1);
         for (int64_t i = 0; i < m; ++i)   // rows ascending: fixed summation order
+          if (dflag[i] < 0)
           for (int64_t p = Jrp[i]; p < Jrp[i + 1]; ++p)
             for (int64_t q = Jrp[i]; q < Jrp[i + 1]; ++q)
               if (Jrj[p] >= Jrj[q]) {
@@ -758,14 +875,24 @@ int okkt_kkt_set_structure(okkt_kkt_handle k, int64_t n, int64_t m, const int64_
         UPL(qptr, qptr); UPL(qa, qa); UPL(qb, qb); UPL(qi, qi);
       }
       UPL(qh, qh); UPL(diagA, diagA);
+      if (kd) {
+        std::vector<int64_t> drows(k->h_drows);
+        UPL(dflag, dflag); UPL(drows, drows); UPL(bsrc, bsrc); UPL(bslot, bslot); UPL(bdiag, bdiag);
+        int64_t maxlen = 1;
+        for (int64_t i : k->h_drows) maxlen = std::max(maxlen, Jrp[i + 1] - Jrp[i]);
+        k->dchunks = (maxlen + kDenseChunk - 1) / kDenseChunk;
+        if ((rc = kk_alloc(k, (size_t)(kDenseMaxPairs * kd), &k->ddot)) || (rc = kk_alloc(k, (size_t)(kDenseMaxPairs * kd * k->dchunks), &k->dpart)) ||
+            (rc = kk_alloc(k, (size_t)(n + kd), &k->pad_res)))
+          return rc;
+      }
       k->Ap = Ap; k->Ai = Ai;
     }
 #undef UPL
     if ((rc = kk_alloc(k, (size_t)nnzH, &k->Hx)) || (rc = kk_alloc(k, (size_t)nnzJ, &k->Jx)) || (rc = kk_alloc(k, (size_t)m, &k->s)) ||
         (rc = kk_alloc(k, (size_t)m, &k->y)) || (rc = kk_alloc(k, (size_t)m, &k->sig)) || (rc = kk_alloc(k, (size_t)k->nnzA, &k->Avals)) ||
         (rc = kk_alloc(k, (size_t)n, &k->schur_diag)) || (rc = kk_alloc(k, (size_t)n, &k->rD)) || (rc = kk_alloc(k, (size_t)m, &k->rP)) ||
-        (rc = kk_alloc(k, (size_t)m, &k->rC)) || (rc = kk_alloc(k, (size_t)n, &k->dx)) || (rc = kk_alloc(k, (size_t)m, &k->dy)) ||
-        (rc = kk_alloc(k, (size_t)m, &k->ds)) || (rc = kk_alloc(k, (size_t)n, &k->vn1)) || (rc = kk_alloc(k, (size_t)n, &k->vn2)) ||
+        (rc = kk_alloc(k, (size_t)m, &k->rC)) || (rc = kk_alloc(k, (size_t)(n + k->kd), &k->dx)) || (rc = kk_alloc(k, (size_t)m, &k->dy)) ||
+        (rc = kk_alloc(k, (size_t)m, &k->ds)) || (rc = kk_alloc(k, (size_t)n, &k->vn1)) || (rc = kk_alloc(k, (size_t)(n + k->kd), &k->vn2)) ||
         (rc = kk_alloc(k, (size_t)n, &k->vn3)) || (rc = kk_alloc(k, (size_t)m, &k->vm1)) || (rc = kk_alloc(k, (size_t)m, &k->vm2)) ||
         (rc = kk_alloc(k, (size_t)(n + m), &k->big1)) || (rc = kk_alloc(k, (size_t)(n + m), &k->big2)) || (rc = kk_alloc(k, (size_t)8, &k->red)) ||
         (rc = kk_alloc(k, (size_t)nnzJ, &k->Jcsr)) || (rc = kk_alloc(k, (size_t)nnzH, &k->Hcsr)) || (rc = kk_alloc(k, (size_t)n, &k->Hdiag)) ||
@@ -847,7 +974,14 @@ int okkt_kkt_form_system(okkt_kkt_handle k, const double* H_nzval, const double*
     } else if (k->nnzA) {
       hipLaunchKernelGGL(k_assemble_schur, grid1(k->nnzA), dim3(256), 0, st, k->nnzA, k->qptr, k->qa, k->qb, k->qi, k->qh, k->Jx, k->sig, k->Hx, k->Avals);
     }
-    if (k->n) hipLaunchKernelGGL(k_gather, grid1(k->n), dim3(256), 0, st, k->n, k->diagA, k->Avals, k->schur_diag);   // schur_diag = diag(Q), schur.jl:56
+    if (k->kd) {
+      // the border, then schur_diag = diag(Q) of the whole Q (dense rows included) from the columns of J, as the symmetric kind does
+      hipLaunchKernelGGL(k_assemble_border, grid1(k->nnzJd + k->kd), dim3(256), 0, st, k->nnzJd, k->kd, k->bsrc, k->bslot, k->drows, k->bdiag, k->Jx,
+                         k->s, k->y, k->Avals);
+      SEG_LAUNCH(k_schur_diag_seg, k->lprJc, k->n, st, k->n, k->Jp, k->Ji, k->Jx, k->sig, k->Hdiag, k->schur_diag);
+    } else if (k->n) {
+      hipLaunchKernelGGL(k_gather, grid1(k->n), dim3(256), 0, st, k->n, k->diagA, k->Avals, k->schur_diag);   // schur_diag = diag(Q), schur.jl:56
+    }
   }
   const size_t e2 = k->tm_form.mark(st);
   k->tm_form.seg(0, e0, e1);
@@ -886,11 +1020,11 @@ int okkt_kkt_is_diag_dom(okkt_kkt_handle k, int32_t* out) {
   }
   const bool schur = k->kind == OKKT_KKT_SCHUR || k->kind == OKKT_KKT_SCHUR_DIRECT;
   // column sums of the stored H (CSC columns as rows of the segmented product), row sums (CSR copy)
-  SEG_LAUNCH(k_seg_spmv, k->lprH, n, st, n, k->Hp, k->Hi, k->Hx, k->ones, (const double*)nullptr, (const double*)nullptr, 0.0, k->vn1);
-  SEG_LAUNCH(k_seg_spmv, k->lprH, n, st, n, k->Hrp, k->Hrj, k->Hcsr, k->ones, (const double*)nullptr, (const double*)nullptr, 0.0, k->vn2);
+  SEG_LAUNCH(k_seg_spmv, k->lprH, n, st, n, k->Hp, k->Hi, k->Hx, k->ones, (const double*)nullptr, (const double*)nullptr, 0.0, k->vn1, NO_DR);
+  SEG_LAUNCH(k_seg_spmv, k->lprH, n, st, n, k->Hrp, k->Hrj, k->Hcsr, k->ones, (const double*)nullptr, (const double*)nullptr, 0.0, k->vn2, NO_DR);
   if (schur && m) {   // (J' Sigma J) 1 = J' (Sigma .* (J 1)): row sums = column sums (symmetric block, stored in full)
-    SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->ones, k->sig, (const double*)nullptr, 0.0, k->vm2);
-    SEG_LAUNCH(k_seg_spmv, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, k->vm2, (const double*)nullptr, (const double*)nullptr, 0.0, k->vn3);
+    SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->ones, k->sig, (const double*)nullptr, 0.0, k->vm2, NO_DR);
+    SEG_LAUNCH(k_seg_spmv, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, k->vm2, (const double*)nullptr, (const double*)nullptr, 0.0, k->vn3, NO_DR);
   }
   hipLaunchKernelGGL(k_diag_dom_margin, grid1(n), dim3(256), 0, st, n, k->vn1, k->vn2, (schur && m) ? k->vn3 : (const double*)nullptr,
                      schur ? k->schur_diag : k->Hdiag, k->delta, k->big1);
@@ -921,7 +1055,7 @@ int okkt_kkt_estimate_y_tilde(okkt_kkt_handle k, const double* g, double* y_out)
     if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
   }
   if (m) {
-    SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, (const double*)nullptr, (const double*)nullptr, 0.0, k->vm1);
+    SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, (const double*)nullptr, (const double*)nullptr, 0.0, k->vm1, NO_DR);
     hipLaunchKernelGGL(k_scale, grid1(m), dim3(256), 0, st, m, -1.0, k->vm1, k->vm2);
     KK_TRY(k, hipMemcpyAsync(y_out, k->vm2, (size_t)m * 8, hipMemcpyDeviceToHost, st));
   }
@@ -955,6 +1089,9 @@ static int kkt_factor_impl(okkt_kkt_s* k, double delta, okkt_inertia* inertia_ou
   k->tm_factor.seg(0, e0, e1);
   if (k->kind == OKKT_KKT_CLEVER_SYMMETRIC) rc = solver_factor_device(k->ls, k->Avals, k->n, k->m_new, OKKT_SYM_SYMMETRIC, inertia_out);   // clever_symmetric.jl:395-400
   else if (k->kind == OKKT_KKT_SYMMETRIC) rc = solver_factor_device(k->ls, k->Avals, k->n, k->m, OKKT_SYM_SYMMETRIC, inertia_out);
+  // the bordered Schur system: In(A) = In(Q) + (0, kd, 0) (Haynsworth; s, y > 0), so Q positive definite <=> In(A) = (n, kd, 0), every
+  // pivot counted with tolerance 0 as the Cholesky rule of the plain Schur system does
+  else if (k->kd) rc = solver_factor_device(k->ls, k->Avals, k->n, k->kd, OKKT_SYM_SYMMETRIC, inertia_out, true);
   else rc = solver_factor_device(k->ls, k->Avals, k->n, 0, OKKT_SYM_DEFINITE, inertia_out);
   k->ls->early_exit = saved_early;
   k->t_factor_ms = k->ls->last_factor_ms;
@@ -1153,19 +1290,35 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
     const double* Jr = direct ? k->cur_Jcsr : k->Jcsr;
     if (m) hipLaunchKernelGGL(k_schur_t1, grid1(m), dim3(256), 0, st, m, k->rP, k->rC, sg, ss, k->vm1);
     // vn2 = schur_rhs = dual_r + J' y_
-    SEG_LAUNCH(k_seg_spmv, k->lprJc, n, st, n, k->Jp, k->Ji, Jc, k->vm1, (const double*)nullptr, k->rD, 1.0, k->vn2);
-    if (n) KK_TRY(k, hipMemsetAsync(k->dx, 0, (size_t)n * 8, st));
+    SEG_LAUNCH(k_seg_spmv, k->lprJc, n, st, n, k->Jp, k->Ji, Jc, k->vm1, (const double*)nullptr, k->rD, 1.0, k->vn2, NO_DR);
+    // with dense rows the system is bordered: rhs [r; 0] (vn2 and pad_res have a zero tail of kd), the solves accumulate into dx of
+    // n + kd entries, of which the first n are dir_x
+    const int64_t kd = k->kd;
+    const bool dr = dense_dot_on(k);
+    double* res = kd ? k->pad_res : k->big1;
+    if (n) KK_TRY(k, hipMemsetAsync(k->dx, 0, (size_t)(n + kd) * 8, st));
     for (int it = 0; it < ItRefine_Num; ++it) {
-      rc = solve(it == 0 ? k->vn2 : k->big1, k->dx, true);          // dir_x .+= ls_solve(res_old)
+      rc = solve(it == 0 ? k->vn2 : res, k->dx, true);          // dir_x .+= ls_solve(res_old)
       if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
       // the residual behind the last solve is only printed by the reference (output_level >= 4): not evaluated
       if (it + 1 < ItRefine_Num && n) {
-        SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, k->sig, (const double*)nullptr, 0.0, k->vm2);   // Sigma .* (J dx)
+        if (dr) {
+          dense_dots(k, st, k->Jcsr, nullptr, k->dx, 0, 1);
+          SEG_LAUNCH_DR(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, k->sig, (const double*)nullptr, 0.0, k->vm2, k->dflag, k->ddot);
+        } else {
+          SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, k->sig, (const double*)nullptr, 0.0, k->vm2, NO_DR);   // Sigma .* (J dx)
+        }
         SEG_LAUNCH(k_schur_resid, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, k->vm2, k->Hrp, k->Hrj, k->Hcsr, k->Hp, k->Hi, k->Hx, k->Hdiag, k->dx, k->vn2,
-                   k->delta, k->big1);
+                   k->delta, res);
       }
     }
-    SEG_LAUNCH(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, k->dx, k->rP, k->rC, ys, ss, sg, direct ? 1 : 0, k->dy, k->ds);
+    if (dr) {
+      // J dx with the rows dy / ds take (Jr) and with those of the N err (Jcsr): pairs 0 and, when they differ, 1
+      dense_dots(k, st, Jr, Jr == k->Jcsr ? nullptr : k->Jcsr, k->dx, 0, 1);
+      SEG_LAUNCH_DR(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, k->dx, k->rP, k->rC, ys, ss, sg, direct ? 1 : 0, k->dy, k->ds, k->dflag, k->ddot);
+    } else {
+      SEG_LAUNCH(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, k->dx, k->rP, k->rC, ys, ss, sg, direct ? 1 : 0, k->dy, k->ds, NO_DR);
+    }
   } else if (k->kind == OKKT_KKT_CLEVER_SYMMETRIC) {
     // compute_direction_implementation!(::Clever_Symmetric_KKT_solver), clever_symmetric.jl:417-492
     const int64_t mn = k->m_new, dim = n + mn;
@@ -1186,7 +1339,7 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
     if (dim) hipLaunchKernelGGL(k_clever_unscale, grid1(dim), dim3(256), 0, st, n, mn, k->big2, k->Dres, k->dx, k->big4);   // big4 = v
     if (m) {
       hipLaunchKernelGGL(k_clever_y, grid1(m), dim3(256), 0, st, m, k->row_grp, k->row_ratio, k->s, k->y, k->vm1, k->crhs, k->gU, k->big4, k->dy);
-      SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, (const double*)nullptr, k->rP, -1.0, k->ds);   // J dx - primal_r
+      SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, (const double*)nullptr, k->rP, -1.0, k->ds, NO_DR);   // J dx - primal_r
     }
   } else {
     // symmetric.jl:59-83
@@ -1194,7 +1347,7 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
     rc = solve(k->big1, k->big2, false);
     if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
     if (n + m) hipLaunchKernelGGL(k_sym_split, grid1(n + m), dim3(256), 0, st, n, m, k->big2, k->dx, k->dy);
-    SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, (const double*)nullptr, k->rP, -1.0, k->ds);       // J dx - primal_r
+    SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, (const double*)nullptr, k->rP, -1.0, k->ds, NO_DR);       // J dx - primal_r
   }
   lap(1);
   // update_kkt_error! (p = Inf), kkt_system_solver.jl:67-96: always with the matrices of factor_it
@@ -1202,7 +1355,12 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
   std::memset(&E, 0, sizeof(E));
   const int64_t nbD = n ? (int64_t)seg_grid(n, k->lprJc).x : 0, nbM = m ? (int64_t)seg_grid(m, k->lprJr).x : 0;
   SEG_LAUNCH(k_err_dual, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, k->dy, k->Hrp, k->Hrj, k->Hcsr, k->Hp, k->Hi, k->Hx, k->Hdiag, k->dx, k->rD, k->delta, k->part);
-  SEG_LAUNCH(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, k->ds, k->dy, k->s, k->y, k->rP, k->rC, k->part + nbD * 8);
+  if (dense_dot_on(k)) {
+    const double* dd = k->ddot + (direct && k->cur_Jcsr != k->Jcsr ? k->kd : 0);   // the Jcsr pair of the dense_dots above
+    SEG_LAUNCH_DR(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, k->ds, k->dy, k->s, k->y, k->rP, k->rC, k->part + nbD * 8, k->dflag, dd);
+  } else {
+    SEG_LAUNCH(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, k->ds, k->dy, k->s, k->y, k->rP, k->rC, k->part + nbD * 8, NO_DR);
+  }
   hipLaunchKernelGGL(k_err_final, dim3(1), dim3(256), 0, st, nbD, nbM, k->part, k->red);
   lap(2);
   T.seg(3, t_begin, t_last);
@@ -1245,12 +1403,16 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
   const bool schur = k->kind != OKKT_KKT_SYMMETRIC, direct = k->kind == OKKT_KKT_SCHUR_DIRECT;
   hipStream_t st = kk_stream(k);
   const int64_t n = k->n, m = k->m, dim = schur ? n : n + m;
+  // the bordered Schur system (dense rows): the linear system has order n + kd; per rhs its rhs [r; 0], solution and residual have
+  // that stride (b_rhs, b_sol, b_res), dir_x is compacted to stride n (b_dx) after the refinement
+  const int64_t kd = k->kd, dS = n + kd;
+  const bool dr = dense_dot_on(k);
   if (k->batch_cap < nrhs) {
     const size_t c = (size_t)nrhs;
     int rc2;
     if ((rc2 = kk_alloc(k, c * std::max<int64_t>(n, 1), &k->b_rD)) || (rc2 = kk_alloc(k, c * std::max<int64_t>(m, 1), &k->b_rP)) ||
         (rc2 = kk_alloc(k, c * std::max<int64_t>(m, 1), &k->b_rC)) || (rc2 = kk_alloc(k, c * (size_t)(n + m + 1), &k->b_rhs)) ||
-        (rc2 = kk_alloc(k, c * (size_t)(n + m + 1), &k->b_sol)) || (rc2 = kk_alloc(k, c * std::max<int64_t>(n, 1), &k->b_res)) ||
+        (rc2 = kk_alloc(k, c * (size_t)(n + m + 1), &k->b_sol)) || (rc2 = kk_alloc(k, c * std::max<int64_t>(n + kd, 1), &k->b_res)) ||
         (rc2 = kk_alloc(k, c * std::max<int64_t>(n, 1), &k->b_dx)) || (rc2 = kk_alloc(k, c * std::max<int64_t>(m, 1), &k->b_dy)) ||
         (rc2 = kk_alloc(k, c * std::max<int64_t>(m, 1), &k->b_ds)) || (rc2 = kk_alloc(k, c * 8, &k->b_red)))
       return rc2;
@@ -1269,6 +1431,10 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
   const double* Jc = direct ? k->cur_Jx : k->Jx;
   const double* Jr = direct ? k->cur_Jcsr : k->Jcsr;
   // System_rhs for every triple, then the rhs of the linear system
+  if (kd) {
+    KK_TRY(k, hipMemsetAsync(k->b_rhs, 0, (size_t)nrhs * dS * 8, st));
+    KK_TRY(k, hipMemsetAsync(k->b_res, 0, (size_t)nrhs * dS * 8, st));
+  }
   for (int q = 0; q < nrhs; ++q) {
     const double eP = etas[3 * q], eD = etas[3 * q + 1], eM = etas[3 * q + 2];
     double* rD = k->b_rD + (size_t)q * n; double* rP = k->b_rP + (size_t)q * m; double* rC = k->b_rC + (size_t)q * m;
@@ -1276,7 +1442,7 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
     if (m) hipLaunchKernelGGL(k_rhs_pc, grid1(m), dim3(256), 0, st, m, k->cur_cons, k->cur_s, k->cur_y, 1.0 - eP, k->cur_mu * eM, rP, rC);
     if (schur) {
       if (m) hipLaunchKernelGGL(k_schur_t1, grid1(m), dim3(256), 0, st, m, rP, rC, sg, ss, k->vm1);
-      SEG_LAUNCH(k_seg_spmv, k->lprJc, n, st, n, k->Jp, k->Ji, Jc, k->vm1, (const double*)nullptr, rD, 1.0, k->b_rhs + (size_t)q * n);
+      SEG_LAUNCH(k_seg_spmv, k->lprJc, n, st, n, k->Jp, k->Ji, Jc, k->vm1, (const double*)nullptr, rD, 1.0, k->b_rhs + (size_t)q * dS, NO_DR);
     } else if (dim) {
       hipLaunchKernelGGL(k_sym_rhs, grid1(dim), dim3(256), 0, st, n, m, rD, rP, rC, k->y, k->b_rhs + (size_t)q * dim);
     }
@@ -1284,24 +1450,39 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
   lap(1);
   int rc;
   if (schur) {
-    if (n) KK_TRY(k, hipMemsetAsync(k->b_dx, 0, (size_t)nrhs * n * 8, st));
+    double* xs = kd ? k->b_sol : k->b_dx;       // the solves' target, stride dS
+    if (n) KK_TRY(k, hipMemsetAsync(xs, 0, (size_t)nrhs * dS * 8, st));
     for (int it = 0; it < ItRefine_Num; ++it) {
-      rc = solver_solve_enqueue(k->ls, it == 0 ? k->b_rhs : k->b_res, k->b_dx, nrhs, true);     // dir_x .+= ls_solve(res_old), all right-hand sides per sweep
+      rc = solver_solve_enqueue(k->ls, it == 0 ? k->b_rhs : k->b_res, xs, nrhs, true);     // dir_x .+= ls_solve(res_old), all right-hand sides per sweep
       if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
       k->n_solves += nrhs;
       lap(0);
-      if (it + 1 < ItRefine_Num && n)
+      if (it + 1 < ItRefine_Num && n) {
+        if (dr) dense_dots(k, st, k->Jcsr, nullptr, xs, dS, nrhs);
         for (int q = 0; q < nrhs; ++q) {
-          double* dxq = k->b_dx + (size_t)q * n;
-          SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, k->sig, (const double*)nullptr, 0.0, k->vm2);
+          double* dxq = xs + (size_t)q * dS;
+          if (dr)
+            SEG_LAUNCH_DR(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, k->sig, (const double*)nullptr, 0.0, k->vm2, k->dflag, k->ddot + q * kd);
+          else
+            SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, k->sig, (const double*)nullptr, 0.0, k->vm2, NO_DR);
           SEG_LAUNCH(k_schur_resid, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, k->vm2, k->Hrp, k->Hrj, k->Hcsr, k->Hp, k->Hi, k->Hx, k->Hdiag, dxq,
-                     k->b_rhs + (size_t)q * n, k->delta, k->b_res + (size_t)q * n);
+                     k->b_rhs + (size_t)q * dS, k->delta, k->b_res + (size_t)q * dS);
         }
+      }
       lap(1);
     }
-    for (int q = 0; q < nrhs; ++q)
-      SEG_LAUNCH(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, k->b_dx + (size_t)q * n, k->b_rP + (size_t)q * m, k->b_rC + (size_t)q * m, ys, ss, sg,
-                 direct ? 1 : 0, k->b_dy + (size_t)q * m, k->b_ds + (size_t)q * m);
+    if (kd) {
+      KK_TRY(k, hipMemcpy2DAsync(k->b_dx, (size_t)n * 8, xs, (size_t)dS * 8, (size_t)n * 8, (size_t)nrhs, hipMemcpyDeviceToDevice, st));
+      if (dr) dense_dots(k, st, Jr, Jr == k->Jcsr ? nullptr : k->Jcsr, k->b_dx, n, nrhs);   // pairs q (Jr) and nrhs + q (Jcsr, when it differs)
+    }
+    for (int q = 0; q < nrhs; ++q) {
+      if (dr)
+        SEG_LAUNCH_DR(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, k->b_dx + (size_t)q * n, k->b_rP + (size_t)q * m, k->b_rC + (size_t)q * m, ys, ss, sg,
+                      direct ? 1 : 0, k->b_dy + (size_t)q * m, k->b_ds + (size_t)q * m, k->dflag, k->ddot + q * kd);
+      else
+        SEG_LAUNCH(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, k->b_dx + (size_t)q * n, k->b_rP + (size_t)q * m, k->b_rC + (size_t)q * m, ys, ss, sg,
+                   direct ? 1 : 0, k->b_dy + (size_t)q * m, k->b_ds + (size_t)q * m, NO_DR);
+    }
   } else {
     rc = solver_solve_enqueue(k->ls, k->b_rhs, k->b_sol, nrhs, false);
     if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
@@ -1310,7 +1491,7 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
     for (int q = 0; q < nrhs; ++q) {
       if (dim) hipLaunchKernelGGL(k_sym_split, grid1(dim), dim3(256), 0, st, n, m, k->b_sol + (size_t)q * dim, k->b_dx + (size_t)q * n, k->b_dy + (size_t)q * m);
       SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->b_dx + (size_t)q * n, (const double*)nullptr, k->b_rP + (size_t)q * m, -1.0,
-                 k->b_ds + (size_t)q * m);
+                 k->b_ds + (size_t)q * m, NO_DR);
     }
   }
   lap(1);
@@ -1318,7 +1499,11 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
   for (int q = 0; q < nrhs; ++q) {
     const double* dxq = k->b_dx + (size_t)q * n; const double* dyq = k->b_dy + (size_t)q * m; const double* dsq = k->b_ds + (size_t)q * m;
     SEG_LAUNCH(k_err_dual, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, dyq, k->Hrp, k->Hrj, k->Hcsr, k->Hp, k->Hi, k->Hx, k->Hdiag, dxq, k->b_rD + (size_t)q * n, k->delta, k->part);
-    SEG_LAUNCH(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, dsq, dyq, k->s, k->y, k->b_rP + (size_t)q * m, k->b_rC + (size_t)q * m, k->part + nbD * 8);
+    if (dr)
+      SEG_LAUNCH_DR(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, dsq, dyq, k->s, k->y, k->b_rP + (size_t)q * m, k->b_rC + (size_t)q * m,
+                    k->part + nbD * 8, k->dflag, k->ddot + (Jr == k->Jcsr ? q : nrhs + q) * kd);
+    else
+      SEG_LAUNCH(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, dsq, dyq, k->s, k->y, k->b_rP + (size_t)q * m, k->b_rC + (size_t)q * m, k->part + nbD * 8, NO_DR);
     hipLaunchKernelGGL(k_err_final, dim3(1), dim3(256), 0, st, nbD, nbM, k->part, k->b_red + (size_t)q * 8);
   }
   lap(2);
@@ -1526,6 +1711,14 @@ int okkt_kkt_get_matrix(okkt_kkt_handle k, int64_t* dim_out, int64_t* nnz_out, i
     KK_TRY(k, hipStreamSynchronize(kk_stream(k)));
     if (k->nnzA) KK_TRY(k, hipMemcpy(nzval_out, k->Avals, (size_t)k->nnzA * 8, hipMemcpyDeviceToHost));
   }
+  return OKKT_OK;
+}
+
+int okkt_kkt_get_dense_rows(okkt_kkt_handle k, int64_t* count_out, int64_t* rows_out) {
+  if (!k || !count_out) return OKKT_ERR_INVALID;
+  if (!k->structured) return kk_fail(k, OKKT_ERR_INVALID, "structure not set");
+  *count_out = k->kd;
+  if (rows_out) std::copy(k->h_drows.begin(), k->h_drows.end(), rows_out);
   return OKKT_OK;
 }
 

@@ -36,6 +36,16 @@ struct okkt_kkt_s {
   uint16_t* tslot = nullptr;
   int schur_groups = 0, schur_maxcol = 0;
   double* schur_diag = nullptr;
+  // schur, dense rows of J (okkt_opts.schur_dense_rows): the kd rows left out of J' Sigma J border the factorised matrix,
+  // A = [[Q_s + delta I, J_d'], [J_d, -diag(s_d / y_d)]] of order n + kd.  Host: the rows (ascending); device: per row of J its index
+  // among the dense rows or -1, the rows, and the slots of the border (the CSC entries of J_d and the k diagonal entries)
+  int64_t kd = 0;
+  std::vector<int64_t> h_drows;
+  int *dflag = nullptr;
+  int64_t *drows = nullptr, *bsrc = nullptr, *bslot = nullptr, *bdiag = nullptr;
+  int64_t nnzJd = 0, dchunks = 0;   // entries of J_d, workgroups per dense row of k_dense_dot
+  double *ddot = nullptr, *dpart = nullptr;   // dense-row dots (k_dense_dot): results [pair][kd], per-workgroup partials
+  double *pad_res = nullptr;                  // residual of the refinement, n + kd (tail stays 0)
   // work vectors
   double *rD = nullptr, *rP = nullptr, *rC = nullptr, *dx = nullptr, *dy = nullptr, *ds = nullptr;
   double *vn1 = nullptr, *vn2 = nullptr, *vn3 = nullptr, *vm1 = nullptr, *vm2 = nullptr, *big1 = nullptr, *big2 = nullptr;

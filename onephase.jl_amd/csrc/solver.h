@@ -50,8 +50,10 @@ struct okkt_solver_s {
 
 namespace okkt {
 // shared by the linear-solver level and the KKT level
+// zero_tol: count a pivot as zero only when it is exactly 0 (|d| <= 0), the rule of OKKT_SYM_DEFINITE, also for OKKT_SYM_SYMMETRIC
+// (the bordered Schur system decides its flag the way the Cholesky rule of the plain one does)
 int solver_factor_device(okkt_solver_s* h, const double* d_vals, int64_t n, int64_t m, int sym_kind,
-                         okkt_inertia* out);
+                         okkt_inertia* out, bool zero_tol = false);
 int solver_solve_device(okkt_solver_s* h, const double* d_rhs, double* d_sol, int64_t nrhs);
 // the same without synchronisation or timing (the KKT level strings solves and vector kernels together on the stream);
 // accumulate: d_sol += F \ d_rhs

@@ -56,6 +56,18 @@ function kkt_hip_check(k::HIP_KKT_solver, what::String, rc)
     return rc
 end
 
+# the rows of J (1-based, ascending) that okkt_opts.schur_dense_rows ("kkt!hip_schur_dense_rows", carried by okkt_opts_from_pars) moved out
+# of Q into the border of the factorised Schur system; empty with the option off and for the other kinds
+function dense_rows(k::HIP_KKT_solver)
+    cnt = Ref{Int64}(0)
+    kkt_hip_check(k, "okkt_kkt_get_dense_rows", ccall((:okkt_kkt_get_dense_rows, OKKT_LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}),
+                                                      k.handle, cnt, C_NULL))
+    rows = zeros(Int64, cnt[])
+    kkt_hip_check(k, "okkt_kkt_get_dense_rows", ccall((:okkt_kkt_get_dense_rows, OKKT_LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}),
+                                                      k.handle, cnt, rows))
+    return rows .+ 1
+end
+
 # initialize!(::Clever_Symmetric_KKT_solver, it) (clever_symmetric.jl:53-61): the parallel-row grouping is computed
 # once, from the Jacobian of the initial iterate
 function initialize!(k::HIP_KKT_solver, intial_it::Class_iterate)

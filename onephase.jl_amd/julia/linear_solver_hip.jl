@@ -33,7 +33,7 @@ struct OkktOpts
     small_front_max::Int32
     panel_nb::Int32
     early_exit::Int32
-    reserved::Int32
+    schur_dense_rows::Int32    # Schur kinds: 0 off, > 0 rows longer than this border the system, -1 automatic
 end
 
 function okkt_default_opts()
@@ -44,7 +44,7 @@ end
 
 # The back-end's own knobs ride in pars.kkt like the reference's `ma97_u` (parameters.jl:13,25 -> linear_solver_HSL(..., pars.kkt.ma97_u),
 # kkt_system_solver.jl:247): the fields hip_device, hip_ordering, hip_relax_always / _small / _mid, hip_relax_small_frac / _mid_frac /
-# _any_frac, hip_inertia_tol of Class_kkt_solver_options (INTEGRATION.md, edit 4), set through the existing plumbing, e.g.
+# _any_frac, hip_inertia_tol, hip_schur_dense_rows of Class_kkt_solver_options (INTEGRATION.md, edit 4), set through the existing plumbing, e.g.
 # "kkt!hip_ordering" => 3 (create_pars_JuMP, JuMPinterface.jl:570-586).  -1 / 0.0 keep the library's default.
 function okkt_opts_from_pars(kkt)
     d = okkt_default_opts()
@@ -54,7 +54,8 @@ function okkt_opts_from_pars(kkt)
                     Int32(pick(kkt.hip_relax_always, d.relax_always)), Int32(pick(kkt.hip_relax_small, d.relax_small)), Int32(pick(kkt.hip_relax_mid, d.relax_mid)),
                     pick(kkt.hip_relax_small_frac, d.relax_small_frac), pick(kkt.hip_relax_mid_frac, d.relax_mid_frac), pick(kkt.hip_relax_any_frac, d.relax_any_frac),
                     kkt.hip_inertia_tol > 0 ? kkt.hip_inertia_tol : d.inertia_tol,
-                    d.small_front_max, d.panel_nb, d.early_exit, d.reserved)
+                    d.small_front_max, d.panel_nb, d.early_exit,
+                    kkt.hip_schur_dense_rows != 0 ? Int32(kkt.hip_schur_dense_rows) : d.schur_dense_rows)
 end
 
 mutable struct linear_solver_HIP <: abstract_linear_system_solver

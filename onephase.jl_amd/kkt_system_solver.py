@@ -105,6 +105,9 @@ class Class_kkt_solver_options:   # parameters.jl:4-46 (the entries the path rea
     hip_relax_mid_frac: float = 0.0
     hip_relax_any_frac: float = 0.0
     hip_inertia_tol: float = 1e-20      # okkt_opts.inertia_tol (julia.jl:73)
+    # okkt_opts.schur_dense_rows, Schur kinds only: 0 off, > 0 rows of J with more entries are dense, -1 automatic (max(64, 10 sqrt(n))).
+    # Dense rows border the factorised matrix instead of filling Q = H + J' Sigma J ("kkt!hip_schur_dense_rows")
+    hip_schur_dense_rows: int = 0
 
 
 def okkt_opts_from_pars(kkt):
@@ -125,6 +128,8 @@ def okkt_opts_from_pars(kkt):
             o[name] = float(v)
     if kkt.hip_inertia_tol != 1e-20:
         o["inertia_tol"] = float(kkt.hip_inertia_tol)
+    if kkt.hip_schur_dense_rows != 0:
+        o["schur_dense_rows"] = int(kkt.hip_schur_dense_rows)
     return o
 
 
@@ -477,6 +482,15 @@ class HIP_KKT_solver:
                     "okkt_kkt_get_matrix")
         return sp.csc_matrix((val[: nnz.value], rowval[: nnz.value], colptr), shape=(dim.value, dim.value))
 
+    def dense_rows(self):
+        """The rows of J (0-based, ascending) that border the Schur system instead of entering Q (okkt_opts.schur_dense_rows);
+        empty for the other kinds and with the option off."""
+        cnt = C.c_int64()
+        self._check(self._lib.okkt_kkt_get_dense_rows(self._k, C.byref(cnt), None), "okkt_kkt_get_dense_rows")
+        rows = np.zeros(max(cnt.value, 1), dtype=np.int64)
+        self._check(self._lib.okkt_kkt_get_dense_rows(self._k, C.byref(cnt), L.p_i64(rows)), "okkt_kkt_get_dense_rows")
+        return rows[: cnt.value]
+
     def linear_solver_stats(self):
         st = L.OkktStats()
         h = self._lib.okkt_kkt_linear_solver(self._k)
@@ -500,11 +514,15 @@ class HIP_KKT_solver:
             raise OkktError("kkt solver not ready: factor! first")
         h = C.c_void_p(self._lib.okkt_kkt_linear_solver(self._k))
         b = L.f64(np.asarray(rhs, dtype=float))
+        # a Schur system with dense rows factors the bordered matrix: Q x = r <=> A [x; z] = [r; 0]
+        kd = len(self.dense_rows()) if self.kind in ("schur", "schur_direct") else 0
+        if kd:
+            b = L.f64(np.concatenate([b, np.zeros(kd)]))
         x = np.zeros_like(b)
         rc = self._lib.okkt_solve(h, L.p_f64(b), L.p_f64(x), 1)
         if rc != 0:
             raise OkktError(f"okkt_solve failed ({rc})")
-        return x
+        return x[: len(x) - kd] if kd else x
 
 
 def estimate_y_tilde(J, g, pars=None, **opts):
