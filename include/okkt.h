@@ -149,6 +149,35 @@ int okkt_factor_dev(okkt_handle h, const double* d_nzval, int64_t n, int64_t m, 
 /* sol = F \ rhs for nrhs right-hand sides stored one after another (julia.jl:101,110).  rhs may alias sol. */
 int okkt_solve(okkt_handle h, const double* rhs, double* sol, int64_t nrhs);
 int okkt_solve_dev(okkt_handle h, const double* d_rhs, double* d_sol, int64_t nrhs);
+/* Iterative refinement with extra-precise residuals.  A is the symmetric matrix whose lower triangle the
+ * analysed CSC holds with the values nzval (same order as rowval; upper-triangle entries ignored, duplicates summed, as the
+ * factorisation reads them); nzval need not be the factored values (refining A with the factor of A + delta I is legitimate).
+ * The residual r = b - A x is accumulated in double-double and rounded once; omega = max_i |r_i| / (|A||x| + |b|)_i is the
+ * componentwise backward error (0 / 0 = 0; NaN when r or x holds a non-finite value).  The first call after an analysis builds a row-wise map of the pattern on the host
+ * (O(nnz)) and keeps it, with a workspace of 8 B per entry, on the device until the next analysis.  Partitioned handles
+ * (okkt_dist_set_partition with nparts > 1) are refused with OKKT_ERR_INVALID.
+ * okkt_solve_refine: x = F \ b, then for each right-hand side on its own (Arioli-Demmel-Duff): compute r and omega, stop when
+ * omega <= tol (<= 0: 2^-52), when omega > omega_prev / 2 (stagnation), when a value is non-finite or after max_steps corrections,
+ * else x += F \ r.  Each right-hand side returns the iterate with the smallest finite omega it reached; max_steps = 0 returns the
+ * x of okkt_solve and omega0.  One small device-to-host read per step decides.  Returns OKKT_OK whenever it ran: the outcome is in
+ * info.status.  rhs may alias sol. */
+typedef struct {
+  int32_t steps;      /* corrections applied, max over the right-hand sides */
+  int32_t status;     /* worst over the right-hand sides: 0 omega <= tol, 1 step limit, 2 stagnated, 3 non-finite */
+  double omega0;      /* max over rhs: componentwise backward error of the plain solve */
+  double omega;       /* max over rhs: ... of the returned solutions */
+  double resid_inf;   /* max over rhs: ||b - A x||_inf of the returned solutions */
+} okkt_refine_info;
+
+int okkt_residual(okkt_handle h, const double* nzval, const double* rhs, const double* x, double* r, int64_t nrhs,
+                  double* omega_out /* [nrhs] or NULL */);
+/* the same with device pointers for nzval, rhs, x and r; omega_out is host memory */
+int okkt_residual_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, const double* d_x, double* d_r, int64_t nrhs,
+                      double* omega_out);
+int okkt_solve_refine(okkt_handle h, const double* nzval, const double* rhs, double* sol, int64_t nrhs, int32_t max_steps,
+                      double tol, okkt_refine_info* info /* or NULL */, double* omega_out /* [nrhs] or NULL */);
+int okkt_solve_refine_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
+                          double tol, okkt_refine_info* info, double* omega_out);
 /* diag(F): the D of LDL^T in pivot (permuted) order, as `diag(solver._factor)` (julia.jl:72) */
 int okkt_get_diag(okkt_handle h, double* d_out /* [dim] */);
 /* L as CSC in permuted numbering (unit diagonal not stored), for parity tests; pass NULLs to size */
@@ -325,6 +354,10 @@ int okkt_kkt_get_schur_diag(okkt_kkt_handle k, double* out /* [n] */);
  * unless rows_out is NULL, the rows themselves (0-based, ascending).  The factorised matrix (okkt_kkt_get_matrix) then has order n + count,
  * the inertia okkt_kkt_factor reports is its inertia and the flag is 1 exactly for (n, count, 0, 0), every pivot counted with tolerance 0;
  * okkt_kkt_get_schur_diag and okkt_kkt_diag_min keep describing diag(Q) of the whole Q. */
+/* OKKT_KKT_SYMMETRIC only: the triangular solve of okkt_kkt_compute_direction(s) becomes okkt_solve_refine against the assembled,
+ * shifted K that was factored (max_steps corrections at most, stop at omega <= tol, tol <= 0: 2^-52).  max_steps = 0 (the default)
+ * leaves the plain solve.  The other kinds refine through ItRefine_Num and refuse it with OKKT_ERR_INVALID. */
+int okkt_kkt_set_ls_refine(okkt_kkt_handle k, int32_t max_steps, double tol);
 int okkt_kkt_get_dense_rows(okkt_kkt_handle k, int64_t* count_out, int64_t* rows_out /* [count] or NULL */);
 
 /* ---- Clever_Symmetric only -------------------------------------------------------

@@ -130,6 +130,20 @@ class OkktKktTimers(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class OkktRefineInfo(C.Structure):
+    """okkt_refine_info: outcome of okkt_solve_refine (status 0 omega <= tol, 1 step limit, 2 stagnated, 3 non-finite)."""
+    _fields_ = [
+        ("steps", C.c_int32),
+        ("status", C.c_int32),
+        ("omega0", C.c_double),
+        ("omega", C.c_double),
+        ("resid_inf", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/okkt.h declares, with its signature
 _i64p = C.POINTER(C.c_int64)
 _f64p = C.POINTER(C.c_double)
@@ -150,6 +164,10 @@ SIGNATURES = {
     "okkt_factor_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, C.POINTER(OkktInertia)]),
     "okkt_solve": (C.c_int, [_vp, _f64p, _f64p, C.c_int64]),
     "okkt_solve_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64]),
+    "okkt_residual": (C.c_int, [_vp, _f64p, _f64p, _f64p, _f64p, C.c_int64, _f64p]),
+    "okkt_residual_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _f64p]),
+    "okkt_solve_refine": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
+    "okkt_solve_refine_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
     "okkt_get_diag": (C.c_int, [_vp, _f64p]),
     "okkt_get_factor_csc": (C.c_int, [_vp, _i64p, _i64p, _f64p, _i64p]),
     "okkt_dev_alloc": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp)]),
@@ -200,6 +218,7 @@ SIGNATURES = {
     "okkt_kkt_get_matrix": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p, _f64p]),
     "okkt_kkt_get_schur_diag": (C.c_int, [_vp, _f64p]),
     "okkt_kkt_get_dense_rows": (C.c_int, [_vp, _i64p, _i64p]),
+    "okkt_kkt_set_ls_refine": (C.c_int, [_vp, C.c_int32, C.c_double]),
     "okkt_kkt_compute_indicies": (C.c_int, [_vp, _f64p, C.POINTER(C.c_int64)]),
     "okkt_kkt_get_indicies": (C.c_int, [_vp, _i64p, _i64p, _i64p, _f64p, _f64p, _f64p, _f64p]),
     "okkt_kkt_set_rescale": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),

@@ -3,6 +3,7 @@
 // (/root/reference/src/linear_system_solvers/julia.jl).  No exception leaves this file.
 #include <mutex>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -118,6 +119,199 @@ int solver_solve_device(okkt_solver_s* h, const double* d_rhs, double* d_sol, in
   if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("solve failed: ") + hipGetErrorString(he));
   float ms = 0;
   if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->last_solve_ms = ms;
+  return OKKT_OK;
+}
+
+// ---- refinement with extra-precise residuals (refine.hip) ------------------------------------
+
+void solver_refine_release(okkt_solver_s* h) {
+  refine_map_release(h->rf);
+  if (h->rf_work) (void)hipFree(h->rf_work);
+  if (h->rf_om) (void)hipFree(h->rf_om);
+  h->rf_work = nullptr; h->rf_work_len = 0;
+  h->rf_om = nullptr; h->rf_om_len = 0;
+}
+
+// device, analysis, no partition; the row map of the pattern on the first call after an analysis
+static int refine_ready(okkt_solver_s* h, bool need_factor) {
+  int rc = ensure_device(h);
+  if (rc != OKKT_OK) return rc;
+  if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_analyze has not been called");
+  if (h->S.nparts > 1)
+    return solver_set_error(h, OKKT_ERR_INVALID, "residuals and refinement are not available on a partitioned handle (okkt_dist_set_partition with nparts > 1)");
+  if (need_factor) {
+    if ((rc = solver_ensure_numeric(h)) != OKKT_OK) return rc;
+    if (!h->factored) return solver_set_error(h, OKKT_ERR_INVALID, "refinement called before a factorisation");
+  }
+  if (!h->rf.ready) {
+    std::string e = refine_map_build(h->S.n, h->pat_colptr.data(), h->pat_rowval.data(), h->pat_colptr[0], h->rf);
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, "refinement map: " + e);
+  }
+  return OKKT_OK;
+}
+
+// work vectors of the handle: len doubles and nom (omega, |r|) pairs' doubles (grown, never shrunk until the next analysis)
+static int refine_work(okkt_solver_s* h, int64_t len, int64_t nom) {
+  auto grow = [&](double** p, int64_t* have, int64_t want) -> bool {
+    if (*have >= want) return true;
+    (void)hipStreamSynchronize(h->stream);
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    if (hipMalloc((void**)p, (size_t)std::max<int64_t>(want, 2) * sizeof(double)) != hipSuccess) { *p = nullptr; return false; }
+    *have = want;
+    return true;
+  };
+  if (!grow(&h->rf_work, &h->rf_work_len, len) || !grow(&h->rf_om, &h->rf_om_len, nom))
+    return solver_set_error(h, OKKT_ERR_ALLOC, "refinement work vectors: hipMalloc failed");
+  return OKKT_OK;
+}
+
+static double nan_max(double a, double b) { return (a != a || b != b) ? NAN : std::max(a, b); }
+
+// r = b - A x and omega for nrhs right-hand sides (device pointers, checked handle); omega_out host [nrhs] or NULL
+static int residual_device(okkt_solver_s* h, const double* d_nzval, const double* d_b, const double* d_x, double* d_r, int64_t nrhs,
+                           double* omega_out) {
+  const int64_t n = h->S.n;
+  int rc = refine_work(h, 0, 2 * nrhs);
+  if (rc != OKKT_OK) return rc;
+  hipStream_t st = h->stream;
+  refine_gather_enqueue(h->rf, d_nzval, st);
+  for (int64_t q0 = 0; q0 < nrhs; q0 += 4) {
+    const int nr = (int)std::min<int64_t>(4, nrhs - q0);
+    ResidSet S;
+    for (int s = 0; s < 4; ++s) {
+      const int64_t q = q0 + std::min(s, nr - 1);
+      S.b[s] = d_b + q * n; S.x[s] = d_x + q * n; S.r[s] = d_r + q * n; S.om[s] = h->rf_om + 2 * q;
+    }
+    refine_residual_enqueue(h->rf, S, nr, st);
+  }
+  std::vector<double> om((size_t)(2 * nrhs));
+  hipError_t he = hipMemcpyAsync(om.data(), h->rf_om, (size_t)(2 * nrhs) * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("residual: ") + hipGetErrorString(he));
+  if (omega_out) for (int64_t q = 0; q < nrhs; ++q) omega_out[q] = om[(size_t)(2 * q)];
+  return OKKT_OK;
+}
+
+int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
+                         double tol, okkt_refine_info* info, double* omega_out, void (*lap)(void*, int), void* lap_ctx, int* n_solves_out) {
+  if (n_solves_out) *n_solves_out = 0;
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  if (max_steps < 0) return solver_set_error(h, OKKT_ERR_INVALID, "max_steps < 0");
+  int rc = refine_ready(h, true);
+  if (rc != OKKT_OK) return rc;
+  if (!(tol > 0.0)) tol = std::ldexp(1.0, -52);
+  const int64_t n = h->S.n;
+  okkt_refine_info I;
+  std::memset(&I, 0, sizeof(I));
+  if (nrhs == 0 || n == 0) {
+    if (info) *info = I;
+    if (omega_out) for (int64_t q = 0; q < nrhs; ++q) omega_out[q] = 0.0;
+    return OKKT_OK;
+  }
+  if ((rc = refine_work(h, 4 * nrhs * n, 2 * nrhs)) != OKKT_OK) return rc;
+  double* B = h->rf_work;            // the right-hand sides (rhs may alias sol)
+  double* R = B + nrhs * n;          // residuals of the active right-hand sides, packed
+  double* D = R + nrhs * n;          // their corrections, packed
+  double* XP = D + nrhs * n;         // the iterate before the last correction, per right-hand side
+  hipStream_t st = h->stream;
+  auto mark = [&](int tag) { if (lap) lap(lap_ctx, tag); };
+  int nsolves = 0;
+  hipError_t he = hipMemcpyAsync(B, d_rhs, (size_t)(nrhs * n) * sizeof(double), hipMemcpyDeviceToDevice, st);
+  if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("refinement rhs copy: ") + hipGetErrorString(he));
+  refine_gather_enqueue(h->rf, d_nzval, st);
+  mark(1);
+  if ((rc = solver_solve_enqueue(h, B, d_sol, nrhs, false)) != OKKT_OK) return rc;   // x = F \ b: the batches of okkt_solve
+  nsolves += (int)nrhs;
+  mark(0);
+  const size_t Q = (size_t)nrhs;
+  std::vector<double> w0(Q, 0.0), wprev(Q, 0.0), rprev(Q, 0.0), wbest(Q, 0.0), rbest(Q, 0.0), om(2 * Q);
+  std::vector<int> steps(Q, 0), status(Q, 0);
+  std::vector<int64_t> act(Q);
+  for (size_t q = 0; q < Q; ++q) act[q] = (int64_t)q;
+  for (int it = 0; !act.empty(); ++it) {
+    // omega of every active right-hand side; slot k of R belongs to act[k]
+    for (size_t k0 = 0; k0 < act.size(); k0 += 4) {
+      const int nr = (int)std::min<size_t>(4, act.size() - k0);
+      ResidSet S;
+      for (int s = 0; s < 4; ++s) {
+        const size_t k = k0 + (size_t)std::min(s, nr - 1);
+        const int64_t q = act[k];
+        S.b[s] = B + q * n; S.x[s] = d_sol + q * n; S.r[s] = R + (int64_t)k * n; S.om[s] = h->rf_om + 2 * q;
+      }
+      refine_residual_enqueue(h->rf, S, nr, st);
+    }
+    he = hipMemcpyAsync(om.data(), h->rf_om, 2 * Q * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);    // the one device-to-host read of a step
+    if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("refinement residual: ") + hipGetErrorString(he));
+    mark(1);
+    std::vector<int64_t> next, next_slot;
+    for (size_t k = 0; k < act.size(); ++k) {
+      const size_t q = (size_t)act[k];
+      const double w = om[2 * q], ri = om[2 * q + 1];
+      if (it == 0) w0[q] = w;
+      // the previous iterate is the better one: back to it (the last correction is undone)
+      auto restore = [&]() -> int {
+        hipError_t e2 = hipMemcpyAsync(d_sol + (int64_t)q * n, XP + (int64_t)q * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st);
+        if (e2 != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("refinement restore: ") + hipGetErrorString(e2));
+        wbest[q] = wprev[q]; rbest[q] = rprev[q]; --steps[q];
+        return OKKT_OK;
+      };
+      if (!std::isfinite(w) || !std::isfinite(ri)) {
+        status[q] = 3;
+        if (it > 0) { if ((rc = restore()) != OKKT_OK) return rc; }
+        else { wbest[q] = w; rbest[q] = ri; }
+      } else if (w <= tol) {
+        status[q] = 0; wbest[q] = w; rbest[q] = ri;
+      } else if (it > 0 && w > 0.5 * wprev[q]) {
+        status[q] = 2;
+        if (w > wprev[q]) { if ((rc = restore()) != OKKT_OK) return rc; }
+        else { wbest[q] = w; rbest[q] = ri; }
+      } else if (it >= max_steps) {
+        status[q] = 1; wbest[q] = w; rbest[q] = ri;
+      } else {
+        wprev[q] = w; rprev[q] = ri;
+        next.push_back((int64_t)q);
+        next_slot.push_back((int64_t)k);
+      }
+    }
+    if (next.empty()) break;
+    // the residuals of the right-hand sides that go on, to the front of R (slot k' <= k: nothing unread is overwritten)
+    for (size_t k = 0; k < next.size(); ++k)
+      if (next_slot[k] != (int64_t)k) {
+        he = hipMemcpyAsync(R + (int64_t)k * n, R + next_slot[k] * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st);
+        if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("refinement compaction: ") + hipGetErrorString(he));
+      }
+    mark(1);
+    if ((rc = solver_solve_enqueue(h, R, D, (int64_t)next.size(), false)) != OKKT_OK) return rc;   // d = F \ r
+    nsolves += (int)next.size();
+    mark(0);
+    // masked correction: only the right-hand sides that go on are touched (no solve of a zero rhs: 0 * NaN is not 0)
+    for (size_t k0 = 0; k0 < next.size(); k0 += 4) {
+      const int nr = (int)std::min<size_t>(4, next.size() - k0);
+      UpdateSet U;
+      for (int s = 0; s < 4; ++s) {
+        const size_t k = k0 + (size_t)std::min(s, nr - 1);
+        const int64_t q = next[k];
+        U.x[s] = d_sol + q * n; U.xp[s] = XP + q * n; U.d[s] = D + (int64_t)k * n;
+      }
+      refine_update_enqueue(n, U, nr, st);
+    }
+    for (int64_t q : next) ++steps[(size_t)q];
+    act.swap(next);
+  }
+  for (size_t q = 0; q < Q; ++q) {
+    if (q == 0) { I.omega0 = w0[q]; I.omega = wbest[q]; I.resid_inf = rbest[q]; }
+    else { I.omega0 = nan_max(I.omega0, w0[q]); I.omega = nan_max(I.omega, wbest[q]); I.resid_inf = nan_max(I.resid_inf, rbest[q]); }
+    I.steps = std::max(I.steps, steps[q]);
+    I.status = std::max(I.status, status[q]);
+    if (omega_out) omega_out[q] = wbest[q];
+  }
+  if (info) *info = I;
+  if (n_solves_out) *n_solves_out = nsolves;
+  he = hipStreamSynchronize(st);
+  if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("refinement: ") + hipGetErrorString(he));
   return OKKT_OK;
 }
 
@@ -314,6 +508,7 @@ int okkt_destroy(okkt_handle h) {
     // a finalizer that runs after the process-exit handler: every pooled stream has been synchronised and destroyed
     // there, so nothing is in flight; only memory and events are released, no stream is touched
     numeric_release(h->N);
+    solver_refine_release(h);
     if (h->d_rhs_stage) (void)hipFree(h->d_rhs_stage);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -321,6 +516,7 @@ int okkt_destroy(okkt_handle h) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     numeric_release(h->N);
+    solver_refine_release(h);
     if (h->d_rhs_stage) (void)hipFree(h->d_rhs_stage);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -372,6 +568,11 @@ int okkt_analyze(okkt_handle h, int64_t dim, const int64_t* colptr, const int64_
     if (h->opts.ordering == 2 && (int64_t)h->user_perm.size() != dim)
       return solver_set_error(h, OKKT_ERR_INVALID, "ordering=user: okkt_set_perm must supply dim entries first");
     auto t0 = std::chrono::steady_clock::now();
+    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om)) {   // the refinement map belongs to the old pattern
+      (void)hipSetDevice(h->device);
+      (void)hipStreamSynchronize(h->stream);
+      solver_refine_release(h);
+    }
     if (h->numeric_ready) {
       (void)hipSetDevice(h->device);
       (void)hipStreamSynchronize(h->stream);
@@ -627,6 +828,99 @@ int okkt_get_profile(okkt_handle h, int64_t* n_launches, double* total_ms, doubl
   *total_ms = ms;
   *total_flops = fl;
   return OKKT_OK;
+}
+
+int okkt_residual_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, const double* d_x, double* d_r, int64_t nrhs,
+                      double* omega_out) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  try {
+    int rc = refine_ready(h, false);
+    if (rc != OKKT_OK) return rc;
+    if (nrhs == 0) return OKKT_OK;
+    if ((!d_nzval && h->S.nnz_in > 0) || !d_rhs || !d_x || !d_r) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+    return residual_device(h, d_nzval, d_rhs, d_x, d_r, nrhs, omega_out);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_residual_dev");
+  }
+}
+
+int okkt_residual(okkt_handle h, const double* nzval, const double* rhs, const double* x, double* r, int64_t nrhs, double* omega_out) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  try {
+    int rc = refine_ready(h, false);
+    if (rc != OKKT_OK) return rc;
+    if (nrhs == 0) return OKKT_OK;
+    if ((!nzval && h->S.nnz_in > 0) || !rhs || !x || !r) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+    const int64_t len = nrhs * h->S.n;
+    std::string e = refine_stage_alloc(h->rf);
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_ALLOC, "nzval staging: " + e);
+    if ((rc = refine_work(h, 3 * len, 2 * nrhs)) != OKKT_OK) return rc;
+    double* db = h->rf_work;
+    double* dxv = db + len;
+    double* dr = dxv + len;
+    hipStream_t st = h->stream;
+    hipError_t he = hipSuccess;
+    if (h->S.nnz_in > 0) he = hipMemcpyAsync(h->rf.nz_stage, nzval, (size_t)h->S.nnz_in * sizeof(double), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && len > 0) he = hipMemcpyAsync(db, rhs, (size_t)len * sizeof(double), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && len > 0) he = hipMemcpyAsync(dxv, x, (size_t)len * sizeof(double), hipMemcpyHostToDevice, st);
+    if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("residual upload: ") + hipGetErrorString(he));
+    if ((rc = residual_device(h, h->rf.nz_stage, db, dxv, dr, nrhs, omega_out)) != OKKT_OK) return rc;
+    if (len > 0 && hipMemcpy(r, dr, (size_t)len * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "residual download failed");
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_residual");
+  }
+}
+
+int okkt_solve_refine_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
+                          double tol, okkt_refine_info* info, double* omega_out) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs > 0 && (!d_rhs || !d_sol || (!d_nzval && h->S.nnz_in > 0))) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+  try {
+    return solver_refine_device(h, d_nzval, d_rhs, d_sol, nrhs, max_steps, tol, info, omega_out);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_solve_refine_dev");
+  }
+}
+
+int okkt_solve_refine(okkt_handle h, const double* nzval, const double* rhs, double* sol, int64_t nrhs, int32_t max_steps, double tol,
+                      okkt_refine_info* info, double* omega_out) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  if (max_steps < 0) return solver_set_error(h, OKKT_ERR_INVALID, "max_steps < 0");
+  if (nrhs > 0 && (!rhs || !sol || (!nzval && h->S.nnz_in > 0))) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+  try {
+    int rc = refine_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    const int64_t len = h->S.n * nrhs;
+    if (len == 0) return solver_refine_device(h, nullptr, nullptr, nullptr, nrhs, max_steps, tol, info, omega_out);
+    std::string e = refine_stage_alloc(h->rf);
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_ALLOC, "nzval staging: " + e);
+    if (h->rhs_stage_len < len) {
+      (void)hipStreamSynchronize(h->stream);
+      if (h->d_rhs_stage) (void)hipFree(h->d_rhs_stage);
+      h->d_rhs_stage = nullptr;
+      h->rhs_stage_len = 0;
+      if (hipMalloc((void**)&h->d_rhs_stage, (size_t)len * sizeof(double)) != hipSuccess)
+        return solver_set_error(h, OKKT_ERR_ALLOC, "rhs staging allocation failed");
+      h->rhs_stage_len = len;
+    }
+    hipStream_t st = h->stream;
+    hipError_t he = hipSuccess;
+    if (h->S.nnz_in > 0) he = hipMemcpyAsync(h->rf.nz_stage, nzval, (size_t)h->S.nnz_in * sizeof(double), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(h->d_rhs_stage, rhs, (size_t)len * sizeof(double), hipMemcpyHostToDevice, st);
+    if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("refinement upload: ") + hipGetErrorString(he));
+    rc = solver_refine_device(h, h->rf.nz_stage, h->d_rhs_stage, h->d_rhs_stage, nrhs, max_steps, tol, info, omega_out);
+    if (rc != OKKT_OK) return rc;
+    if (hipMemcpy(sol, h->d_rhs_stage, (size_t)len * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "sol download failed");
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_solve_refine");
+  }
 }
 
 int64_t okkt_debug_dataflow_queue(int32_t nfronts, const int32_t* f, const int32_t* k, int32_t workers, int32_t group,

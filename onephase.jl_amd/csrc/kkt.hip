@@ -176,6 +176,12 @@ __global__ void k_sym_rhs(int64_t n, int64_t m, const double* rD, const double* 
   if (i < n) o[i] = rD[i];
   else if (i < n + m) o[i] = rP[i - n] + rC[i - n] / y[i - n];       // symmetric.jl:65
 }
+// the values the refined solve of the symmetric kind works against: K with delta on the first n diagonal entries, added as the
+// factorisation adds it (k_set_shift: one rounding of a + delta)
+__global__ void k_shift_diag(int64_t n, const int64_t* __restrict__ diagA, double delta, double* __restrict__ A) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) A[diagA[j]] = A[diagA[j]] + delta;
+}
 __global__ void k_sym_split(int64_t n, int64_t m, const double* sol, double* dx, double* dy) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dx[i] = sol[i];
@@ -1242,6 +1248,30 @@ int okkt_kkt_system_rhs(okkt_kkt_handle k, const double* J_nzval_cur, const doub
   return OKKT_OK;
 }
 
+// the solve of the symmetric kind refined against the shifted K (okkt_kkt_set_ls_refine): nr right-hand sides, lap(tag) marks the
+// phases (0 solve, 1 residuals and vector work) as the plain solve does
+static int kk_refined_solve(okkt_kkt_s* k, const double* rhs, double* sol, int64_t nr, void (*lap)(void*, int), void* lap_ctx) {
+  hipStream_t st = kk_stream(k);
+  if (!k->rf_vals) { int rc = kk_alloc(k, (size_t)std::max<int64_t>(k->nnzA, 1), &k->rf_vals); if (rc) return rc; }
+  if (k->nnzA) KK_TRY(k, hipMemcpyAsync(k->rf_vals, k->Avals, (size_t)k->nnzA * 8, hipMemcpyDeviceToDevice, st));
+  if (k->n) hipLaunchKernelGGL(k_shift_diag, grid1(k->n), dim3(256), 0, st, k->n, k->diagA, k->delta, k->rf_vals);
+  int ns = 0;
+  const int rc = solver_refine_device(k->ls, k->rf_vals, rhs, sol, nr, k->ls_refine_steps, k->ls_refine_tol, &k->last_refine, nullptr,
+                                      lap, lap_ctx, &ns);
+  k->n_solves += ns;
+  return rc;
+}
+
+int okkt_kkt_set_ls_refine(okkt_kkt_handle k, int32_t max_steps, double tol) {
+  if (!k) return OKKT_ERR_INVALID;
+  if (k->kind != OKKT_KKT_SYMMETRIC)
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_set_ls_refine: symmetric kind only (the Schur and clever-symmetric kinds refine through ItRefine_Num)");
+  if (max_steps < 0) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_set_ls_refine: max_steps < 0");
+  k->ls_refine_steps = max_steps;
+  k->ls_refine_tol = tol;
+  return OKKT_OK;
+}
+
 int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const double* primal_r, const double* comp_r,
                                int32_t ItRefine_Num, double* dx, double* dy, double* ds, okkt_kkt_error* err_out) {
   if (!k) return OKKT_ERR_INVALID;
@@ -1344,7 +1374,8 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
   } else {
     // symmetric.jl:59-83
     if (n + m) hipLaunchKernelGGL(k_sym_rhs, grid1(n + m), dim3(256), 0, st, n, m, k->rD, k->rP, k->rC, k->y, k->big1);
-    rc = solve(k->big1, k->big2, false);
+    if (k->ls_refine_steps > 0) rc = kk_refined_solve(k, k->big1, k->big2, 1, [](void* c, int tag) { (*(decltype(lap)*)c)(tag); }, &lap);   // okkt_kkt_set_ls_refine
+    else rc = solve(k->big1, k->big2, false);
     if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
     if (n + m) hipLaunchKernelGGL(k_sym_split, grid1(n + m), dim3(256), 0, st, n, m, k->big2, k->dx, k->dy);
     SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, (const double*)nullptr, k->rP, -1.0, k->ds, NO_DR);       // J dx - primal_r
@@ -1482,6 +1513,14 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
       else
         SEG_LAUNCH(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, k->b_dx + (size_t)q * n, k->b_rP + (size_t)q * m, k->b_rC + (size_t)q * m, ys, ss, sg,
                    direct ? 1 : 0, k->b_dy + (size_t)q * m, k->b_ds + (size_t)q * m, NO_DR);
+    }
+  } else if (k->ls_refine_steps > 0) {
+    rc = kk_refined_solve(k, k->b_rhs, k->b_sol, nrhs, [](void* c, int tag) { (*(decltype(lap)*)c)(tag); }, &lap);   // okkt_kkt_set_ls_refine
+    if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
+    for (int q = 0; q < nrhs; ++q) {
+      if (dim) hipLaunchKernelGGL(k_sym_split, grid1(dim), dim3(256), 0, st, n, m, k->b_sol + (size_t)q * dim, k->b_dx + (size_t)q * n, k->b_dy + (size_t)q * m);
+      SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->b_dx + (size_t)q * n, (const double*)nullptr, k->b_rP + (size_t)q * m, -1.0,
+                 k->b_ds + (size_t)q * m, NO_DR);
     }
   } else {
     rc = solver_solve_enqueue(k->ls, k->b_rhs, k->b_sol, nrhs, false);

@@ -71,6 +71,12 @@ struct okkt_kkt_s {
   const double* cur_Jcsr = nullptr;          // the same in CSR order
   bool have_cur = false, have_rhs = false;
   double* part = nullptr;                    // per-workgroup partial maxima of the N-err kernels
+  // symmetric kind, okkt_kkt_set_ls_refine: refinement steps of the direction's solve (0 = the plain solve), its tolerance, the
+  // values it refines against (K with delta on the first n diagonal entries: the matrix the factor sees) and the last outcome
+  int32_t ls_refine_steps = 0;
+  double ls_refine_tol = 0.0;
+  double* rf_vals = nullptr;
+  okkt_refine_info last_refine = {0, 0, 0.0, 0.0, 0.0};
   int64_t part_blocks = 0;
   // device timers: (tag, start, stop) event segments of the last call of each kind, summed per tag on request
   struct Timer {

@@ -7,6 +7,7 @@
 
 #include "../../include/okkt.h"
 #include "numeric.h"
+#include "refine.h"
 #include "symbolic.h"
 
 struct okkt_solver_s {
@@ -46,6 +47,13 @@ struct okkt_solver_s {
   long long* dist_counts = nullptr;  // 4 summed pivot counts on the device
   double* d_rhs_stage = nullptr;  // staging for host-side rhs/sol
   int64_t rhs_stage_len = 0;
+  // refinement (refine.hip): the row-wise map of the analysed input pattern, built on the first residual / refine call after an
+  // analysis and released with it; per-call work vectors of nrhs x n (b, r, d, the previous iterate, host-side x) and (omega, |r|) pairs
+  okkt::RefineMap rf;
+  double* rf_work = nullptr;
+  int64_t rf_work_len = 0;
+  double* rf_om = nullptr;
+  int64_t rf_om_len = 0;
 };
 
 namespace okkt {
@@ -60,4 +68,11 @@ int solver_solve_device(okkt_solver_s* h, const double* d_rhs, double* d_sol, in
 int solver_solve_enqueue(okkt_solver_s* h, const double* d_rhs, double* d_sol, int64_t nrhs, bool accumulate);
 int solver_set_error(okkt_solver_s* h, int code, const std::string& msg);
 int solver_ensure_numeric(okkt_solver_s* h);
+// refinement driver (api.cpp): x = F \ b, then corrections from the double-double residual against d_nzval until omega <= tol,
+// stagnation, a non-finite value or max_steps.  d_rhs, d_sol: nrhs x n on the device (they may alias).  lap(tag), if given, is called at
+// the phase boundaries (tag 0: a solve ended, 1: residual / vector work ended); n_solves_out: right-hand sides solved
+int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
+                         double tol, okkt_refine_info* info, double* omega_out, void (*lap)(void*, int) = nullptr, void* lap_ctx = nullptr,
+                         int* n_solves_out = nullptr);
+void solver_refine_release(okkt_solver_s* h);
 }  // namespace okkt

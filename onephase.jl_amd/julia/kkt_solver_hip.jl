@@ -56,6 +56,18 @@ function kkt_hip_check(k::HIP_KKT_solver, what::String, rc)
     return rc
 end
 
+# okkt_kkt_set_ls_refine (symmetric kind only): pars.kkt.hip_ls_refine_steps / hip_ls_refine_tol ("kkt!hip_ls_refine_steps",
+# "kkt!hip_ls_refine_tol"; not okkt_opts fields).  Call once after construction; 0 steps (the default) leaves the plain solve.
+function set_ls_refine!(k::HIP_KKT_solver, max_steps::Integer, tol::Float64=0.0)
+    kkt_hip_check(k, "okkt_kkt_set_ls_refine", ccall((:okkt_kkt_set_ls_refine, OKKT_LIB), Cint, (Ptr{Cvoid}, Int32, Float64),
+                                                     k.handle, Int32(max_steps), tol))
+end
+function set_ls_refine!(k::HIP_KKT_solver, pars::Class_parameters)
+    steps = hasproperty(pars.kkt, :hip_ls_refine_steps) ? pars.kkt.hip_ls_refine_steps : 0
+    tol = hasproperty(pars.kkt, :hip_ls_refine_tol) ? pars.kkt.hip_ls_refine_tol : 0.0
+    (steps != 0 || tol != 0.0) && set_ls_refine!(k, steps, tol)
+end
+
 # the rows of J (1-based, ascending) that okkt_opts.schur_dense_rows ("kkt!hip_schur_dense_rows", carried by okkt_opts_from_pars) moved out
 # of Q into the border of the factorised Schur system; empty with the option off and for the other kinds
 function dense_rows(k::HIP_KKT_solver)

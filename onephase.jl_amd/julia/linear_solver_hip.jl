@@ -137,6 +137,27 @@ function ls_solve!(solver::linear_solver_HIP, my_rhs::Array{Float64,1}, my_sol::
     pause_advanced_timer(timer, "HIP/ls_solve")
 end
 
+struct OkktRefineInfo     # okkt_refine_info of include/okkt.h
+    steps::Int32
+    status::Int32        # 0 omega <= tol, 1 step limit, 2 stagnated, 3 non-finite
+    omega0::Float64
+    omega::Float64
+    resid_inf::Float64
+end
+
+# sol = F \ rhs refined against A (its nzval in the analysed order; the factor may be of a nearby matrix): at most max_steps
+# corrections from double-double residuals, stopping at a componentwise backward error <= tol (<= 0: 2^-52).  Not part of the
+# reference interface (DESIGN.md section 8.2).
+function ls_solve_refine!(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}, my_rhs::Array{Float64,1}, my_sol::Array{Float64,1};
+                          max_steps::Integer=3, tol::Float64=0.0)
+    info = Ref(OkktRefineInfo(0, 0, 0.0, 0.0, 0.0))
+    rc = ccall((:okkt_solve_refine, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Float64,
+                                                     Ref{OkktRefineInfo}, Ptr{Float64}),
+               solver.handle, A.nzval, my_rhs, my_sol, 1, Int32(max_steps), tol, info, C_NULL)
+    rc < 0 && okkt_error(solver, "okkt_solve_refine", rc)
+    return info[]
+end
+
 function ls_solve(solver::linear_solver_HIP, my_rhs::AbstractArray, timer::class_advanced_timer)
     rhs = Vector{Float64}(my_rhs)      # SparseVector rhs is densified, as in julia.jl:105-113
     sol = zeros(length(rhs))

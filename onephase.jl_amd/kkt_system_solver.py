@@ -108,6 +108,11 @@ class Class_kkt_solver_options:   # parameters.jl:4-46 (the entries the path rea
     # okkt_opts.schur_dense_rows, Schur kinds only: 0 off, > 0 rows of J with more entries are dense, -1 automatic (max(64, 10 sqrt(n))).
     # Dense rows border the factorised matrix instead of filling Q = H + J' Sigma J ("kkt!hip_schur_dense_rows")
     hip_schur_dense_rows: int = 0
+    # Symmetric kind only, not okkt_opts fields (okkt_kkt_set_ls_refine): the direction's solve refined with double-double residuals
+    # against the factored K, at most hip_ls_refine_steps corrections (0 = the plain solve), stopping at a componentwise backward error
+    # <= hip_ls_refine_tol (0.0 = 2^-52) ("kkt!hip_ls_refine_steps", "kkt!hip_ls_refine_tol")
+    hip_ls_refine_steps: int = 0
+    hip_ls_refine_tol: float = 0.0
 
 
 def okkt_opts_from_pars(kkt):
@@ -184,6 +189,9 @@ class HIP_KKT_solver:
             raise OkktError("pick a solver!")          # kkt_system_solver.jl:280
         self.kind = kind
         self.pars = pars or Class_parameters()
+        # the refinement of the symmetric kind is a setter of the handle, not an okkt_opts field: keywords override pars.kkt
+        self.ls_refine_steps = int(opts.pop("hip_ls_refine_steps", self.pars.kkt.hip_ls_refine_steps))
+        self.ls_refine_tol = float(opts.pop("hip_ls_refine_tol", self.pars.kkt.hip_ls_refine_tol))
         self._opts = opts
         self._lib = None
         self._k = None
@@ -213,6 +221,8 @@ class HIP_KKT_solver:
                 raise OkktError(f"okkt_kkt_create failed with code {rc}"
                                 + (" (no HIP device: the KKT path has no CPU fallback)" if rc == L.OKKT_ERR_NO_DEVICE else ""))
             self._k = k
+            if self.ls_refine_steps != 0 or self.ls_refine_tol != 0.0:
+                self._check(self._lib.okkt_kkt_set_ls_refine(self._k, self.ls_refine_steps, self.ls_refine_tol), "okkt_kkt_set_ls_refine")
         self.dir = Class_point(np.zeros(intial_it.dim()), np.zeros(intial_it.ncon()), np.zeros(intial_it.ncon()))
         if self.kind == "clever_symmetric" and self._pattern is None:
             # initialize!(::Clever_Symmetric_KKT_solver, it): compute_indicies(get_jac(it)), clever_symmetric.jl:53-61

@@ -191,6 +191,23 @@ class linear_solver_HIP(abstract_linear_system_solver):
         self._need()
         self._check(self._lib.okkt_solve_dev(self._h, C.c_void_p(d_rhs), C.c_void_p(d_sol), nrhs), "okkt_solve_dev")
 
+    def ls_solve_refine_dev(self, d_nzval, d_rhs, d_sol, nrhs=1, max_steps=3, tol=0.0):
+        """ls_solve_refine with every array resident in HBM (device pointers); returns (info dict, omega per rhs)."""
+        self._need()
+        info = L.OkktRefineInfo()
+        om = np.zeros(max(int(nrhs), 1))
+        self._check(self._lib.okkt_solve_refine_dev(self._h, C.c_void_p(d_nzval), C.c_void_p(d_rhs), C.c_void_p(d_sol), int(nrhs),
+                                                     int(max_steps), float(tol), C.byref(info), L.p_f64(om)), "okkt_solve_refine_dev")
+        return info.as_dict(), om[:nrhs]
+
+    def residual_dev(self, d_nzval, d_rhs, d_x, d_r, nrhs=1):
+        """r = b - A x (double-double, rounded once) with device pointers; returns omega per rhs."""
+        self._need()
+        om = np.zeros(max(int(nrhs), 1))
+        self._check(self._lib.okkt_residual_dev(self._h, C.c_void_p(d_nzval), C.c_void_p(d_rhs), C.c_void_p(d_x), C.c_void_p(d_r),
+                                                 int(nrhs), L.p_f64(om)), "okkt_residual_dev")
+        return om[:nrhs]
+
     def profile_dominant(self, enable):
         self._check(self._lib.okkt_profile_dominant(self._h, 1 if enable else 0), "okkt_profile_dominant")
 
@@ -241,3 +258,49 @@ class linear_solver_HIP(abstract_linear_system_solver):
         sol = np.empty(self._dim)
         self.ls_solve_b(np.asarray(my_rhs, dtype=np.float64).ravel(), sol, timer)
         return sol
+
+    # -- refinement with extra-precise residuals (not part of the reference interface)
+    def _values(self, nzval_or_matrix):
+        if isinstance(nzval_or_matrix, np.ndarray) and nzval_or_matrix.ndim == 1:
+            return L.f64(nzval_or_matrix)
+        return csc_arrays(nzval_or_matrix)[3]
+
+    @staticmethod
+    def _rhs_block(rhs, dim):
+        b = L.f64(rhs)
+        single = b.ndim == 1
+        B = L.f64(b.reshape(1, -1) if single else b)
+        if B.shape[1] != dim:
+            raise OkktError("rhs must have the factorised dimension (one right-hand side per row)")
+        return B, single
+
+    def ls_solve_refine(self, nzval_or_matrix, rhs, max_steps=3, tol=0.0):
+        """x with at most max_steps corrections from double-double residuals against A (its values in the analysed order, or
+        the matrix itself with the analysed pattern; the factor may be of a nearby matrix).  rhs: a vector or one right-hand
+        side per row.  Returns (x, info) with info = okkt_refine_info as a dict plus "omega_per_rhs"."""
+        self._need()
+        vals = self._values(nzval_or_matrix)
+        B, single = self._rhs_block(rhs, self._dim)
+        X = np.zeros_like(B)
+        om = np.zeros(B.shape[0])
+        info = L.OkktRefineInfo()
+        self._check(self._lib.okkt_solve_refine(self._h, L.p_f64(vals), L.p_f64(B), L.p_f64(X), B.shape[0], int(max_steps), float(tol),
+                                                 C.byref(info), L.p_f64(om)), "okkt_solve_refine")
+        d = info.as_dict()
+        d["omega_per_rhs"] = om
+        return (X[0] if single else X), d
+
+    def residual(self, nzval_or_matrix, rhs, x):
+        """(r, omega): r = b - A x accumulated in double-double and rounded once, omega the componentwise backward error
+        max_i |r_i| / (|A||x| + |b|)_i, per right-hand side."""
+        self._need()
+        vals = self._values(nzval_or_matrix)
+        B, single = self._rhs_block(rhs, self._dim)
+        Xv, _ = self._rhs_block(x, self._dim)
+        if Xv.shape != B.shape:
+            raise OkktError("rhs and x must have the same shape")
+        R = np.zeros_like(B)
+        om = np.zeros(B.shape[0])
+        self._check(self._lib.okkt_residual(self._h, L.p_f64(vals), L.p_f64(B), L.p_f64(Xv), L.p_f64(R), B.shape[0], L.p_f64(om)),
+                    "okkt_residual")
+        return (R[0] if single else R), (om[0] if single else om)
