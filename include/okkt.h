@@ -178,6 +178,43 @@ int okkt_solve_refine(okkt_handle h, const double* nzval, const double* rhs, dou
                       double tol, okkt_refine_info* info /* or NULL */, double* omega_out /* [nrhs] or NULL */);
 int okkt_solve_refine_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
                           double tol, okkt_refine_info* info, double* omega_out);
+/* Condition estimation and forward error bounds.  F is the matrix the handle factored: the symmetric matrix
+ * whose lower triangle nzval holds (read as the factorisation reads it: upper-triangle entries ignored, duplicates summed) plus the
+ * diagonal shift the factorisation adds at assembly (the delta that okkt_kkt_factor puts on the first n pivots; none at level 1).
+ * ||F^-1||_1 is estimated by the block 1-norm estimator of Higham and Tisseur (SIAM J. Matrix Anal. Appl. 21, 2000, Algorithm 2.4)
+ * with t columns (1..4; <= 0: 2; clamped to the order), at most 5 iterations, every product one multi-right-hand-side solve pass
+ * (F^-T = F^-1).  Deterministic: the starting block and the replacement of parallel sign columns come from a fixed generator, argmax
+ * ties go to the lowest index; two calls on the same factor give bitwise-identical results.  One small device-to-host read after each
+ * solve pass.  Refused (OKKT_ERR_INVALID) on partitioned handles, before a factorisation and after an early-exit factorisation that
+ * stopped short (as okkt_solve); a factorisation whose flag was 0 is accepted.  A solve that produces a non-finite value (an exact zero
+ * pivot) ends the estimate with status 3 and cond1 = inv_norm1 = Inf. */
+typedef struct {
+  double norm1;       /* ||F||_1 (= ||F||_inf: F symmetric), exact, computed from the values */
+  double inv_norm1;   /* estimate of ||F^-1||_1: a lower bound, attained by a returned vector */
+  double cond1;       /* norm1 * inv_norm1 (Inf when a solve produced a non-finite value) */
+  int32_t iterations; /* estimator iterations, <= 5 */
+  int32_t solves;     /* solve passes used (each carries t right-hand sides) */
+  int32_t status;     /* 0 converged, 1 iteration limit, 3 non-finite */
+} okkt_condest_info;
+
+int okkt_condest(okkt_handle h, const double* nzval, int32_t t /* 1..4, <=0: 2 */, okkt_condest_info* info);
+/* the same with nzval in device memory */
+int okkt_condest_dev(okkt_handle h, const double* d_nzval, int32_t t, okkt_condest_info* info);
+/* the unit vectors e_j the last estimate of this handle (okkt_condest or okkt_forward_error) used, in the order it used them; returns
+ * how many there were (at most cap are written), or < 0 on error */
+int64_t okkt_condest_indices(okkt_handle h, int64_t* ind_out, int64_t cap);
+/* LAPACK's forward error bound (xSYRFS FERR) for solutions x of A x = rhs the caller already has (from okkt_solve or
+ * okkt_solve_refine): ferr_q = || |F^-1| f ||_inf / ||x||_inf with f = |r| + (nz_i + 1) eps (|A||x| + |b|), r the double-double residual
+ * of okkt_residual against the values nzval, nz_i the entries of row i of the full symmetric A, eps = 2^-53 (||x||_inf = 0: the
+ * absolute bound).  The numerator is estimated as the 1-norm of diag(f) F^-1 (its transpose F^-1 diag(f)) with t = 2, for each
+ * right-hand side on its own.  It bounds the error of A's solution only when A is the factored matrix F; refining A with the factor of
+ * A + delta I gives an estimate, not a bound.  berr_out receives omega of the same residual pass (bitwise okkt_residual's).  Same
+ * refusals as okkt_condest. */
+int okkt_forward_error(okkt_handle h, const double* nzval, const double* rhs, const double* x, int64_t nrhs,
+                       double* ferr_out /* [nrhs] */, double* berr_out /* [nrhs] or NULL */);
+/* the same with device pointers for nzval, rhs and x; ferr_out and berr_out are host memory */
+int okkt_forward_error_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, const double* d_x, int64_t nrhs,
+                           double* ferr_out, double* berr_out);
 /* diag(F): the D of LDL^T in pivot (permuted) order, as `diag(solver._factor)` (julia.jl:72) */
 int okkt_get_diag(okkt_handle h, double* d_out /* [dim] */);
 /* L as CSC in permuted numbering (unit diagonal not stored), for parity tests; pass NULLs to size */
@@ -358,6 +395,14 @@ int okkt_kkt_get_schur_diag(okkt_kkt_handle k, double* out /* [n] */);
  * shifted K that was factored (max_steps corrections at most, stop at omega <= tol, tol <= 0: 2^-52).  max_steps = 0 (the default)
  * leaves the plain solve.  The other kinds refine through ItRefine_Num and refuse it with OKKT_ERR_INVALID. */
 int okkt_kkt_set_ls_refine(okkt_kkt_handle k, int32_t max_steps, double tol);
+/* okkt_condest for the system okkt_kkt_factor last factored: K with delta on its H block (symmetric kind); M as scaled and factored
+ * (clever-symmetric kind); Q + delta I (Schur kinds); with schur_dense_rows on, the bordered A (order n + k): then cond1 is kappa_1 of A,
+ * not of Q.  Refused (OKKT_ERR_INVALID) before a complete factorisation. */
+int okkt_kkt_condest(okkt_kkt_handle k, int32_t t, okkt_condest_info* info);
+/* OKKT_KKT_SYMMETRIC only: the forward error bound (okkt_forward_error) of the last okkt_kkt_compute_direction's solve, against the
+ * factored K + delta.  Refused until such a direction exists for the current factorisation and rhs; the other kinds refuse it as they
+ * refuse okkt_kkt_set_ls_refine. */
+int okkt_kkt_direction_error_bound(okkt_kkt_handle k, double* ferr);
 int okkt_kkt_get_dense_rows(okkt_kkt_handle k, int64_t* count_out, int64_t* rows_out /* [count] or NULL */);
 
 /* ---- Clever_Symmetric only -------------------------------------------------------

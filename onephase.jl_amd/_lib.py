@@ -144,6 +144,21 @@ class OkktRefineInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktCondestInfo(C.Structure):
+    """okkt_condest_info: ||F||_1, the estimate of ||F^-1||_1, their product (status 0 converged, 1 iteration limit, 3 non-finite)."""
+    _fields_ = [
+        ("norm1", C.c_double),
+        ("inv_norm1", C.c_double),
+        ("cond1", C.c_double),
+        ("iterations", C.c_int32),
+        ("solves", C.c_int32),
+        ("status", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/okkt.h declares, with its signature
 _i64p = C.POINTER(C.c_int64)
 _f64p = C.POINTER(C.c_double)
@@ -168,6 +183,11 @@ SIGNATURES = {
     "okkt_residual_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _f64p]),
     "okkt_solve_refine": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
     "okkt_solve_refine_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
+    "okkt_condest": (C.c_int, [_vp, _f64p, C.c_int32, C.POINTER(OkktCondestInfo)]),
+    "okkt_condest_dev": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OkktCondestInfo)]),
+    "okkt_condest_indices": (C.c_int64, [_vp, _i64p, C.c_int64]),
+    "okkt_forward_error": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, _f64p, _f64p]),
+    "okkt_forward_error_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _f64p, _f64p]),
     "okkt_get_diag": (C.c_int, [_vp, _f64p]),
     "okkt_get_factor_csc": (C.c_int, [_vp, _i64p, _i64p, _f64p, _i64p]),
     "okkt_dev_alloc": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp)]),
@@ -219,6 +239,8 @@ SIGNATURES = {
     "okkt_kkt_get_schur_diag": (C.c_int, [_vp, _f64p]),
     "okkt_kkt_get_dense_rows": (C.c_int, [_vp, _i64p, _i64p]),
     "okkt_kkt_set_ls_refine": (C.c_int, [_vp, C.c_int32, C.c_double]),
+    "okkt_kkt_condest": (C.c_int, [_vp, C.c_int32, C.POINTER(OkktCondestInfo)]),
+    "okkt_kkt_direction_error_bound": (C.c_int, [_vp, _f64p]),
     "okkt_kkt_compute_indicies": (C.c_int, [_vp, _f64p, C.POINTER(C.c_int64)]),
     "okkt_kkt_get_indicies": (C.c_int, [_vp, _i64p, _i64p, _i64p, _f64p, _f64p, _f64p, _f64p]),
     "okkt_kkt_set_rescale": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),

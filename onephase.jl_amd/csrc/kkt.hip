@@ -182,6 +182,12 @@ __global__ void k_shift_diag(int64_t n, const int64_t* __restrict__ diagA, doubl
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j < n) A[diagA[j]] = A[diagA[j]] + delta;
 }
+// the inverse of k_sym_split: the solution of the direction's solve from dx, dy (okkt_kkt_direction_error_bound)
+__global__ void k_sym_join(int64_t n, int64_t m, const double* dx, const double* dy, double* sol) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) sol[i] = dx[i];
+  else if (i < n + m) sol[i] = -dy[i - n];
+}
 __global__ void k_sym_split(int64_t n, int64_t m, const double* sol, double* dx, double* dy) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dx[i] = sol[i];
@@ -935,6 +941,7 @@ int okkt_kkt_form_system(okkt_kkt_handle k, const double* H_nzval, const double*
   if (k->kind == OKKT_KKT_CLEVER_SYMMETRIC && !k->indexed) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_compute_indicies has not been called (initialize!, clever_symmetric.jl:53-61)");
   if ((k->nnzH > 0 && !H_nzval) || (k->nnzJ > 0 && !J_nzval)) return OKKT_ERR_INVALID;
   k->have_dir = false;
+  k->sym_dir_ok = false;
   k->have_dxnorm = false;
   hipStream_t st = kk_stream(k);
   KK_TRY(k, hipSetDevice(k->ls->device));
@@ -1068,6 +1075,7 @@ int okkt_kkt_estimate_y_tilde(okkt_kkt_handle k, const double* g, double* y_out)
   KK_TRY(k, hipStreamSynchronize(st));
   KK_TRY(k, hipGetLastError());
   k->have_dir = false;
+  k->sym_dir_ok = false;
   return OKKT_OK;
 }
 
@@ -1084,6 +1092,7 @@ static int kkt_factor_impl(okkt_kkt_s* k, double delta, okkt_inertia* inertia_ou
   k->delta = delta;
   k->factored = false;
   k->have_dir = false;
+  k->sym_dir_ok = false;
   hipStream_t st = kk_stream(k);
   k->tm_factor.reset();
   const size_t e0 = k->tm_factor.mark(st);
@@ -1245,6 +1254,7 @@ int okkt_kkt_system_rhs(okkt_kkt_handle k, const double* J_nzval_cur, const doub
   KK_TRY(k, hipGetLastError());
   k->have_cur = true;
   k->have_rhs = true;
+  k->sym_dir_ok = false;
   return OKKT_OK;
 }
 
@@ -1283,6 +1293,7 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
   if (!k->ls->factored)
     return kk_fail(k, OKKT_ERR_INVALID, "the last factorisation was a discarded trial of the delta loop (it stopped early): factor! again before a direction");
   if (!host_rhs && !k->have_rhs) return kk_fail(k, OKKT_ERR_INVALID, "no resident rhs: okkt_kkt_system_rhs has not been called");
+  k->sym_dir_ok = false;
   const bool direct = k->kind == OKKT_KKT_SCHUR_DIRECT;
   if (direct && !k->have_cur) return kk_fail(k, OKKT_ERR_INVALID, "Schur_KKT_solver_direct reads current_it: kkt_associate_rhs! (okkt_kkt_system_rhs) has not been called");
   hipStream_t st = kk_stream(k);
@@ -1414,6 +1425,7 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
   if (err_out) *err_out = E;
   k->have_dir = true;
   k->have_dxnorm = false;
+  k->sym_dir_ok = k->kind == OKKT_KKT_SYMMETRIC;
   return OKKT_OK;
 }
 
@@ -1564,7 +1576,8 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
     E.ratio = E.overall / E.rhs_norm;
     err_out[q] = E;
   }
-  k->have_dir = false;     // the resident single direction of okkt_kkt_compute_direction is not touched; the step-side kernels keep refusing until it is set
+  k->have_dir = false;
+  k->sym_dir_ok = false;     // the resident single direction of okkt_kkt_compute_direction is not touched; the step-side kernels keep refusing until it is set
   return OKKT_OK;
 }
 
@@ -1751,6 +1764,37 @@ int okkt_kkt_get_matrix(okkt_kkt_handle k, int64_t* dim_out, int64_t* nnz_out, i
     if (k->nnzA) KK_TRY(k, hipMemcpy(nzval_out, k->Avals, (size_t)k->nnzA * 8, hipMemcpyDeviceToHost));
   }
   return OKKT_OK;
+}
+
+// condition estimate of the system the last okkt_kkt_factor factored: the assembled Avals plus the shift the factorisation adds
+int okkt_kkt_condest(okkt_kkt_handle k, int32_t t, okkt_condest_info* info) {
+  if (!k) return OKKT_ERR_INVALID;
+  if (!k->factored || !k->ls->factored)
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_condest: no complete factorisation (factor! first; a discarded trial of the delta loop does not count)");
+  const int rc = solver_condest_device(k->ls, k->Avals, t, info);
+  return rc < 0 ? kk_check_ls(k, rc, "condest") : rc;
+}
+
+// the forward error bound of the symmetric kind's last direction solve against the factored K + delta: the rhs rebuilt as
+// okkt_kkt_compute_direction built it, the solution [dx; dy] and the values of the refined solve
+int okkt_kkt_direction_error_bound(okkt_kkt_handle k, double* ferr) {
+  if (!k || !ferr) return OKKT_ERR_INVALID;
+  if (k->kind != OKKT_KKT_SYMMETRIC)
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_direction_error_bound: symmetric kind only (the Schur and clever-symmetric kinds refine through ItRefine_Num)");
+  if (!k->factored || !k->ls->factored || !k->sym_dir_ok)
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_direction_error_bound: no direction of okkt_kkt_compute_direction for the current factorisation and rhs");
+  hipStream_t st = kk_stream(k);
+  const int64_t n = k->n, m = k->m;
+  int rc;
+  if (!k->eb_rhs && ((rc = kk_alloc(k, (size_t)std::max<int64_t>(n + m, 1), &k->eb_rhs)) || (rc = kk_alloc(k, (size_t)std::max<int64_t>(n + m, 1), &k->eb_sol))))
+    return rc;
+  if (!k->rf_vals) { if ((rc = kk_alloc(k, (size_t)std::max<int64_t>(k->nnzA, 1), &k->rf_vals))) return rc; }
+  if (k->nnzA) KK_TRY(k, hipMemcpyAsync(k->rf_vals, k->Avals, (size_t)k->nnzA * 8, hipMemcpyDeviceToDevice, st));
+  if (n) hipLaunchKernelGGL(k_shift_diag, grid1(n), dim3(256), 0, st, n, k->diagA, k->delta, k->rf_vals);
+  if (n + m) hipLaunchKernelGGL(k_sym_rhs, grid1(n + m), dim3(256), 0, st, n, m, k->rD, k->rP, k->rC, k->y, k->eb_rhs);
+  if (n + m) hipLaunchKernelGGL(k_sym_join, grid1(n + m), dim3(256), 0, st, n, m, k->dx, k->dy, k->eb_sol);
+  rc = solver_forward_error_device(k->ls, k->rf_vals, k->eb_rhs, k->eb_sol, 1, ferr, nullptr);
+  return rc < 0 ? kk_check_ls(k, rc, "direction error bound") : rc;
 }
 
 int okkt_kkt_get_dense_rows(okkt_kkt_handle k, int64_t* count_out, int64_t* rows_out) {

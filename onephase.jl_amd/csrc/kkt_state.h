@@ -77,6 +77,10 @@ struct okkt_kkt_s {
   double ls_refine_tol = 0.0;
   double* rf_vals = nullptr;
   okkt_refine_info last_refine = {0, 0, 0.0, 0.0, 0.0};
+  // symmetric kind, okkt_kkt_direction_error_bound: rD, rP, rC, y, dx and dy still hold the rhs and the solution of the last
+  // okkt_kkt_compute_direction's solve (cleared by every call that writes one of them); the rhs and the solution reassembled
+  bool sym_dir_ok = false;
+  double *eb_rhs = nullptr, *eb_sol = nullptr;
   int64_t part_blocks = 0;
   // device timers: (tag, start, stop) event segments of the last call of each kind, summed per tag on request
   struct Timer {

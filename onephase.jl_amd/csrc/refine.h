@@ -37,6 +37,10 @@ struct ResidSet {
   double* r[4];
   double* om[4];
 };
+// optional per-row denominators (|A||x|)_i + |b_i| of the same pass (refine_residual_den_enqueue)
+struct DenSet {
+  double* d[4];
+};
 // masked correction: xp[q] = x[q]; x[q] += d[q]
 struct UpdateSet {
   double* x[4];
@@ -51,6 +55,8 @@ void refine_map_release(RefineMap& M);
 // enqueue functions: no allocation, no synchronisation
 void refine_gather_enqueue(const RefineMap& M, const double* d_nzval, hipStream_t st);
 void refine_residual_enqueue(const RefineMap& M, const ResidSet& S, int nr, hipStream_t st);
+// the same pass, storing the denominators as well (r and omega bitwise as refine_residual_enqueue gives them)
+void refine_residual_den_enqueue(const RefineMap& M, const ResidSet& S, const DenSet& D, int nr, hipStream_t st);
 void refine_update_enqueue(int64_t n, const UpdateSet& U, int nr, hipStream_t st);
 
 }  // namespace okkt

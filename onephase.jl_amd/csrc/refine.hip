@@ -6,6 +6,9 @@
 // (only a denominator), the componentwise backward error omega = max_i |r_i| / (|A||x| + |b|)_i (0 / 0 = 0, c / 0 = inf,
 // NaN where r_i or x_i is not finite) and ||r||_inf, as max-reductions over per-workgroup partials and one final pass.
 //
+// The same pass can store each row's denominator (|A||x|)_i + |b_i| (DenSet): the forward error bound of condest.hip weighs the
+// residual with it.
+//
 // This file is compiled with -ffp-contract=off (Makefile): a contracted or reassociated TwoSum is no longer exact.  Every fma
 // below is written out.
 //
@@ -92,9 +95,9 @@ __device__ __forceinline__ void block_max(double* w, double* ri, double* __restr
 }
 
 // rows of at most long_min entries: a group of LPR lanes per row; longer rows run the shuffles on an empty range (k_resid_long)
-template <int LPR, int R>
+template <int LPR, int R, bool DEN>
 __global__ __launch_bounds__(256) void k_resid_short(int64_t n, const int64_t* __restrict__ rowptr, const int* __restrict__ col,
-                                                     const double* __restrict__ vals, int64_t long_min, ResidSet S,
+                                                     const double* __restrict__ vals, int64_t long_min, ResidSet S, DenSet Dn,
                                                      double* __restrict__ part) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t row = t / LPR;
@@ -129,6 +132,7 @@ __global__ __launch_bounds__(256) void k_resid_short(int64_t n, const int64_t* _
       double r, ratio;
       row_finish(h[q], l[q], den[q], S.b[q][row], S.x[q][row], r, ratio);
       S.r[q][row] = r;
+      if (DEN) Dn.d[q][row] = den[q] + fabs(S.b[q][row]);
       w[q] = ratio;
       ri[q] = fabs(r);
     }
@@ -137,9 +141,9 @@ __global__ __launch_bounds__(256) void k_resid_short(int64_t n, const int64_t* _
 }
 
 // one workgroup per long row: 256 strided lanes, a butterfly inside each wave, the four waves added in order by thread 0
-template <int R>
+template <int R, bool DEN>
 __global__ __launch_bounds__(256) void k_resid_long(const int* __restrict__ long_rows, const int64_t* __restrict__ rowptr,
-                                                    const int* __restrict__ col, const double* __restrict__ vals, ResidSet S,
+                                                    const int* __restrict__ col, const double* __restrict__ vals, ResidSet S, DenSet Dn,
                                                     double* __restrict__ part) {
   __shared__ double sm[4][R][3];
   const int64_t row = long_rows[blockIdx.x];
@@ -175,6 +179,7 @@ __global__ __launch_bounds__(256) void k_resid_long(const int* __restrict__ long
       double r, ratio;
       row_finish(hh, ll, dd, S.b[q][row], S.x[q][row], r, ratio);
       S.r[q][row] = r;
+      if (DEN) Dn.d[q][row] = dd + fabs(S.b[q][row]);
       out[2 * q] = ratio;
       out[2 * q + 1] = fabs(r);
     }
@@ -252,19 +257,35 @@ std::string upload(RefineMap& M, const std::vector<T>& v, T** out) {
   return std::string();
 }
 
-template <int R>
-void launch_residual(const RefineMap& M, const ResidSet& S, hipStream_t st) {
+template <int R, bool DEN>
+void launch_residual(const RefineMap& M, const ResidSet& S, const DenSet& D, hipStream_t st) {
   const dim3 b(256), gs((unsigned)M.nb_short);
   switch (M.lpr) {
-    case 4: hipLaunchKernelGGL((k_resid_short<4, R>), gs, b, 0, st, M.n, M.rowptr, M.col, M.vals, M.long_min, S, M.part); break;
-    case 8: hipLaunchKernelGGL((k_resid_short<8, R>), gs, b, 0, st, M.n, M.rowptr, M.col, M.vals, M.long_min, S, M.part); break;
-    case 16: hipLaunchKernelGGL((k_resid_short<16, R>), gs, b, 0, st, M.n, M.rowptr, M.col, M.vals, M.long_min, S, M.part); break;
-    case 32: hipLaunchKernelGGL((k_resid_short<32, R>), gs, b, 0, st, M.n, M.rowptr, M.col, M.vals, M.long_min, S, M.part); break;
-    default: hipLaunchKernelGGL((k_resid_short<64, R>), gs, b, 0, st, M.n, M.rowptr, M.col, M.vals, M.long_min, S, M.part); break;
+    case 4: hipLaunchKernelGGL((k_resid_short<4, R, DEN>), gs, b, 0, st, M.n, M.rowptr, M.col, M.vals, M.long_min, S, D, M.part); break;
+    case 8: hipLaunchKernelGGL((k_resid_short<8, R, DEN>), gs, b, 0, st, M.n, M.rowptr, M.col, M.vals, M.long_min, S, D, M.part); break;
+    case 16: hipLaunchKernelGGL((k_resid_short<16, R, DEN>), gs, b, 0, st, M.n, M.rowptr, M.col, M.vals, M.long_min, S, D, M.part); break;
+    case 32: hipLaunchKernelGGL((k_resid_short<32, R, DEN>), gs, b, 0, st, M.n, M.rowptr, M.col, M.vals, M.long_min, S, D, M.part); break;
+    default: hipLaunchKernelGGL((k_resid_short<64, R, DEN>), gs, b, 0, st, M.n, M.rowptr, M.col, M.vals, M.long_min, S, D, M.part); break;
   }
   if (M.nlong)
-    hipLaunchKernelGGL((k_resid_long<R>), dim3((unsigned)M.nlong), b, 0, st, M.long_rows, M.rowptr, M.col, M.vals, S,
+    hipLaunchKernelGGL((k_resid_long<R, DEN>), dim3((unsigned)M.nlong), b, 0, st, M.long_rows, M.rowptr, M.col, M.vals, S, D,
                        M.part + (size_t)M.nb_short * 8);
+}
+
+template <bool DEN>
+void residual_enqueue(const RefineMap& M, const ResidSet& S, const DenSet& D, int nr, hipStream_t st) {
+  if (nr <= 0) return;
+  if (M.n == 0) {
+    for (int q = 0; q < nr; ++q) (void)hipMemsetAsync(S.om[q], 0, 2 * sizeof(double), st);
+    return;
+  }
+  switch (nr) {
+    case 1: launch_residual<1, DEN>(M, S, D, st); break;
+    case 2: launch_residual<2, DEN>(M, S, D, st); break;
+    case 3: launch_residual<3, DEN>(M, S, D, st); break;
+    default: launch_residual<4, DEN>(M, S, D, st); break;
+  }
+  hipLaunchKernelGGL(k_resid_final, dim3(1), dim3(256), 0, st, M.nb_short + M.nlong, std::min(nr, 4), M.part, S);
 }
 
 }  // namespace
@@ -383,18 +404,11 @@ void refine_gather_enqueue(const RefineMap& M, const double* d_nzval, hipStream_
 }
 
 void refine_residual_enqueue(const RefineMap& M, const ResidSet& S, int nr, hipStream_t st) {
-  if (nr <= 0) return;
-  if (M.n == 0) {
-    for (int q = 0; q < nr; ++q) (void)hipMemsetAsync(S.om[q], 0, 2 * sizeof(double), st);
-    return;
-  }
-  switch (nr) {
-    case 1: launch_residual<1>(M, S, st); break;
-    case 2: launch_residual<2>(M, S, st); break;
-    case 3: launch_residual<3>(M, S, st); break;
-    default: launch_residual<4>(M, S, st); break;
-  }
-  hipLaunchKernelGGL(k_resid_final, dim3(1), dim3(256), 0, st, M.nb_short + M.nlong, std::min(nr, 4), M.part, S);
+  residual_enqueue<false>(M, S, DenSet{{nullptr, nullptr, nullptr, nullptr}}, nr, st);
+}
+
+void refine_residual_den_enqueue(const RefineMap& M, const ResidSet& S, const DenSet& D, int nr, hipStream_t st) {
+  residual_enqueue<true>(M, S, D, nr, st);
 }
 
 void refine_update_enqueue(int64_t n, const UpdateSet& U, int nr, hipStream_t st) {

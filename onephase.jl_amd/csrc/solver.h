@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/okkt.h"
+#include "condest.h"
 #include "numeric.h"
 #include "refine.h"
 #include "symbolic.h"
@@ -54,6 +55,10 @@ struct okkt_solver_s {
   int64_t rf_work_len = 0;
   double* rf_om = nullptr;
   int64_t rf_om_len = 0;
+  // condition estimation (condest.hip): the estimator's blocks, allocated on the first estimate after an analysis and released with
+  // the refinement map; the unit vectors the last estimate used
+  okkt::CondestWork cd;
+  std::vector<int64_t> cd_hist;
 };
 
 namespace okkt {
@@ -75,4 +80,8 @@ int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* 
                          double tol, okkt_refine_info* info, double* omega_out, void (*lap)(void*, int) = nullptr, void* lap_ctx = nullptr,
                          int* n_solves_out = nullptr);
 void solver_refine_release(okkt_solver_s* h);
+// condition estimate of the factored F (the values d_nzval plus the factorisation's diagonal shift) and forward error bounds (api.cpp)
+int solver_condest_device(okkt_solver_s* h, const double* d_nzval, int32_t t, okkt_condest_info* info);
+int solver_forward_error_device(okkt_solver_s* h, const double* d_nzval, const double* d_b, const double* d_x, int64_t nrhs, double* ferr_out,
+                                double* berr_out);
 }  // namespace okkt

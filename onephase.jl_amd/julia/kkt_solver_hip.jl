@@ -68,6 +68,21 @@ function set_ls_refine!(k::HIP_KKT_solver, pars::Class_parameters)
     (steps != 0 || tol != 0.0) && set_ls_refine!(k, steps, tol)
 end
 
+# okkt_kkt_condest: kappa_1 of the system the last factor! factored (K + delta, M, Q + delta I or the bordered A with dense rows)
+function kkt_condest(k::HIP_KKT_solver; t::Integer=2)
+    info = Ref(OkktCondestInfo(0.0, 0.0, 0.0, 0, 0, 0))
+    kkt_hip_check(k, "okkt_kkt_condest", ccall((:okkt_kkt_condest, OKKT_LIB), Cint, (Ptr{Cvoid}, Int32, Ref{OkktCondestInfo}),
+                                               k.handle, Int32(t), info))
+    return info[]
+end
+# okkt_kkt_direction_error_bound (symmetric kind): the forward error bound of the last direction's solve against K + delta
+function direction_error_bound(k::HIP_KKT_solver)
+    ferr = Ref(0.0)
+    kkt_hip_check(k, "okkt_kkt_direction_error_bound", ccall((:okkt_kkt_direction_error_bound, OKKT_LIB), Cint, (Ptr{Cvoid}, Ref{Float64}),
+                                                             k.handle, ferr))
+    return ferr[]
+end
+
 # the rows of J (1-based, ascending) that okkt_opts.schur_dense_rows ("kkt!hip_schur_dense_rows", carried by okkt_opts_from_pars) moved out
 # of Q into the border of the factorised Schur system; empty with the option off and for the other kinds
 function dense_rows(k::HIP_KKT_solver)

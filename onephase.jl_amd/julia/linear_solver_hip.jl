@@ -158,6 +158,35 @@ function ls_solve_refine!(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,
     return info[]
 end
 
+struct OkktCondestInfo    # okkt_condest_info of include/okkt.h
+    norm1::Float64       # ||F||_1, exact
+    inv_norm1::Float64   # estimate of ||F^-1||_1 (a lower bound)
+    cond1::Float64
+    iterations::Int32
+    solves::Int32
+    status::Int32        # 0 converged, 1 iteration limit, 3 non-finite
+end
+
+# kappa_1 of the factored F (A.nzval plus the factorisation's diagonal shift), Higham-Tisseur block estimate with t columns (1..4).
+# Not part of the reference interface (DESIGN.md section 8.3).
+function ls_condest(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}; t::Integer=2)
+    info = Ref(OkktCondestInfo(0.0, 0.0, 0.0, 0, 0, 0))
+    rc = ccall((:okkt_condest, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ref{OkktCondestInfo}), solver.handle, A.nzval, Int32(t), info)
+    rc < 0 && okkt_error(solver, "okkt_condest", rc)
+    return info[]
+end
+
+# LAPACK's forward error bound (FERR) and the componentwise backward error (BERR) of a solution x of A x = rhs; a bound only when A
+# is the factored matrix
+function ls_forward_error(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}, my_rhs::Array{Float64,1}, x::Array{Float64,1})
+    ferr = zeros(1)
+    berr = zeros(1)
+    rc = ccall((:okkt_forward_error, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+               solver.handle, A.nzval, my_rhs, x, 1, ferr, berr)
+    rc < 0 && okkt_error(solver, "okkt_forward_error", rc)
+    return ferr[1], berr[1]
+end
+
 function ls_solve(solver::linear_solver_HIP, my_rhs::AbstractArray, timer::class_advanced_timer)
     rhs = Vector{Float64}(my_rhs)      # SparseVector rhs is densified, as in julia.jl:105-113
     sol = zeros(length(rhs))

@@ -501,6 +501,19 @@ class HIP_KKT_solver:
         self._check(self._lib.okkt_kkt_get_dense_rows(self._k, C.byref(cnt), L.p_i64(rows)), "okkt_kkt_get_dense_rows")
         return rows[: cnt.value]
 
+    def condest(self, t=2):
+        """okkt_kkt_condest: ||F||_1, the estimate of ||F^-1||_1 and cond1 of the system the last factor_b factored (K + delta for the
+        symmetric kind, M for the clever-symmetric kind, Q + delta I or, with dense rows, the bordered A for the Schur kinds)."""
+        info = L.OkktCondestInfo()
+        self._check(self._lib.okkt_kkt_condest(self._k, int(t), C.byref(info)), "okkt_kkt_condest")
+        return info.as_dict()
+
+    def direction_error_bound(self):
+        """okkt_kkt_direction_error_bound: the forward error bound of the symmetric kind's last direction solve against K + delta."""
+        f = C.c_double()
+        self._check(self._lib.okkt_kkt_direction_error_bound(self._k, C.byref(f)), "okkt_kkt_direction_error_bound")
+        return f.value
+
     def linear_solver_stats(self):
         st = L.OkktStats()
         h = self._lib.okkt_kkt_linear_solver(self._k)

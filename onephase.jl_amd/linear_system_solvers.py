@@ -304,3 +304,38 @@ class linear_solver_HIP(abstract_linear_system_solver):
         self._check(self._lib.okkt_residual(self._h, L.p_f64(vals), L.p_f64(B), L.p_f64(Xv), L.p_f64(R), B.shape[0], L.p_f64(om)),
                     "okkt_residual")
         return (R[0] if single else R), (om[0] if single else om)
+
+    # -- condition estimation and forward error bounds (not part of the reference interface)
+    def condest(self, nzval_or_matrix, t=2):
+        """okkt_condest: ||F||_1 (exact), the Higham-Tisseur estimate of ||F^-1||_1 (a lower bound) and their product cond1, for the
+        factored F (these values plus the factorisation's diagonal shift).  Returns okkt_condest_info as a dict."""
+        self._need()
+        vals = self._values(nzval_or_matrix)
+        info = L.OkktCondestInfo()
+        self._check(self._lib.okkt_condest(self._h, L.p_f64(vals), int(t), C.byref(info)), "okkt_condest")
+        return info.as_dict()
+
+    def condest_indices(self):
+        """The unit vectors e_j the last estimate used, in order (0-based)."""
+        self._need()
+        cnt = int(self._lib.okkt_condest_indices(self._h, None, 0))
+        if cnt < 0:
+            raise OkktError("okkt_condest_indices failed")
+        out = np.zeros(max(cnt, 1), dtype=np.int64)
+        self._lib.okkt_condest_indices(self._h, L.p_i64(out), cnt)
+        return out[:cnt]
+
+    def forward_error(self, nzval_or_matrix, rhs, x):
+        """(ferr, berr): LAPACK's forward error bound || |F^-1| f ||_inf / ||x||_inf with f = |r| + (nz_i + 1) eps (|A||x| + |b|), and the
+        componentwise backward error of the same residual pass, per right-hand side.  A bound only when A is the factored matrix."""
+        self._need()
+        vals = self._values(nzval_or_matrix)
+        B, single = self._rhs_block(rhs, self._dim)
+        Xv, _ = self._rhs_block(x, self._dim)
+        if Xv.shape != B.shape:
+            raise OkktError("rhs and x must have the same shape")
+        ferr = np.zeros(B.shape[0])
+        berr = np.zeros(B.shape[0])
+        self._check(self._lib.okkt_forward_error(self._h, L.p_f64(vals), L.p_f64(B), L.p_f64(Xv), B.shape[0], L.p_f64(ferr), L.p_f64(berr)),
+                    "okkt_forward_error")
+        return (ferr[0], berr[0]) if single else (ferr, berr)
