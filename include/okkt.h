@@ -330,7 +330,9 @@ const char* okkt_kkt_last_error(okkt_kkt_handle k);
 /* the underlying linear-solver handle (for stats / permutation queries) */
 okkt_handle okkt_kkt_linear_solver(okkt_kkt_handle k);
 /* structure of the iterate cache (Class_iterate.jl:4-20): H n x n CSC lower triangle only
- * (Class_cutest.jl:548), J m x n CSC.  Builds the pattern of Q or K, analyses it, builds maps. */
+ * (Class_cutest.jl:548), J m x n CSC.  Builds the pattern of Q or K, analyses it, builds maps.
+ * Both must be canonical, as sparse() leaves them: row indices strictly increasing within every column.  A duplicated or
+ * unsorted entry is refused, for every kind, with OKKT_ERR_INVALID and a message (okkt_kkt_last_error) naming the entry. */
 int okkt_kkt_set_structure(okkt_kkt_handle k, int64_t n, int64_t m,
                            const int64_t* H_colptr, const int64_t* H_rowval,
                            const int64_t* J_colptr, const int64_t* J_rowval, int index_base);

@@ -617,6 +617,19 @@ inline dim3 seg_grid(int64_t rows, int lpr) { return dim3((unsigned)std::max<int
 
 int kk_fail(okkt_kkt_s* k, int code, const std::string& msg) { k->err = msg; return code; }
 
+// OKKT_SCHUR_GROUPS in the environment: the largest column-group count of k_assemble_schur_lds that okkt_kkt_set_structure may pick
+// (16, 8, 4; 0 = always the contribution-list kernel k_assemble_schur).  Unset or any other value: 16, i.e. no cap
+int schur_groups_cap() {
+  static const int cap = [] {
+    const char* e = getenv("OKKT_SCHUR_GROUPS");
+    if (!e) return 16;
+    for (const int v : {8, 4, 0})
+      if (std::strcmp(e, std::to_string(v).c_str()) == 0) return v;
+    return 16;
+  }();
+  return cap;
+}
+
 int kk_check_ls(okkt_kkt_s* k, int rc, const char* what) {
   if (rc < 0) { k->err = std::string(what) + ": " + okkt_last_error(k->ls); }
   return rc;
@@ -718,15 +731,25 @@ int okkt_kkt_set_structure(okkt_kkt_handle k, int64_t n, int64_t m, const int64_
     std::vector<int64_t> Hp(n + 1), Jp(n + 1);
     std::vector<int> Hi(nnzH), Ji(nnzJ);
     for (int64_t j = 0; j <= n; ++j) { Hp[j] = H_colptr[j] - b; Jp[j] = J_colptr[j] - b; }
+    // canonical CSC only: a duplicated entry would be summed by one kind and overwritten by another (the Schur slots hold one
+    // source per entry), so it is refused here for every kind
+    auto unordered = [&](const char* mat, int64_t j, int64_t p, int64_t i_prev, int64_t i) {
+      return kk_fail(k, OKKT_ERR_INVALID, std::string(mat) + ": column " + std::to_string(j + b) + ", entry " + std::to_string(p + b) + ": row " +
+                                              std::to_string(i + b) + " after row " + std::to_string(i_prev + b) +
+                                              " (row indices must be strictly increasing within a column: no duplicate entries)");
+    };
     for (int64_t j = 0; j < n; ++j) {
+      if (Hp[j + 1] < Hp[j] || Jp[j + 1] < Jp[j]) return kk_fail(k, OKKT_ERR_INVALID, "column pointers must not decrease");
       for (int64_t p = Hp[j]; p < Hp[j + 1]; ++p) {
         const int64_t i = H_rowval[p] - b;
         if (i < j || i >= n) return kk_fail(k, OKKT_ERR_INVALID, "H must hold the lower triangle only (Class_cutest.jl:548)");
+        if (p > Hp[j] && i <= Hi[p - 1]) return unordered("H", j, p, Hi[p - 1], i);
         Hi[p] = (int)i;
       }
       for (int64_t p = Jp[j]; p < Jp[j + 1]; ++p) {
         const int64_t i = J_rowval[p] - b;
         if (i < 0 || i >= m) return kk_fail(k, OKKT_ERR_INVALID, "J row index out of range");
+        if (p > Jp[j] && i <= Ji[p - 1]) return unordered("J", j, p, Ji[p - 1], i);
         Ji[p] = (int)i;
       }
     }
@@ -838,7 +861,9 @@ int okkt_kkt_set_structure(okkt_kkt_handle k, int64_t n, int64_t m, const int64_
       int64_t maxcol = 1;
       for (int64_t j = 0; j < n; ++j) maxcol = std::max(maxcol, Ap[j + 1] - Ap[j]);
       // LDS-staged assembly (k_assemble_schur_lds) while a column of Q fits a 16-lane group's share of 64 KiB of LDS
-      const int G = maxcol <= 512 ? 16 : (maxcol <= 1024 ? 8 : (maxcol <= 2048 ? 4 : 0));
+      // OKKT_SCHUR_GROUPS=16|8|4|0 caps G (0: the contribution lists); it never raises it, the LDS holds G columns of maxcol
+      int G = maxcol <= 512 ? 16 : (maxcol <= 1024 ? 8 : (maxcol <= 2048 ? 4 : 0));
+      G = std::min(G, schur_groups_cap());
       k->schur_groups = G; k->schur_maxcol = (int)maxcol;
       if (G > 0) {
         // per CSC entry (i, b): where the columns >= b start in row i (rows are visited with growing b: one cursor per row), its

@@ -169,11 +169,12 @@ def _julia_max(*vals):
 
 def _csc(A):
     # (an iterate that already holds canonical CSC -- what the reference's cache holds, Class_iterate.jl:4-20 -- is taken as it is: building a
-    # new scipy matrix around the same arrays cost 1 ms per matrix at the metric size, twice per form_system_b)
-    if sp.isspmatrix_csc(A) and A.has_sorted_indices:
+    # new scipy matrix around the same arrays cost 1 ms per matrix at the metric size, twice per form_system_b).  Anything else is brought
+    # to canonical form, duplicates summed as sparse() sums them: okkt_kkt_set_structure refuses duplicated entries
+    if sp.isspmatrix_csc(A) and A.has_canonical_format:
         return A
-    A = sp.csc_matrix(A)
-    A.sort_indices()
+    A = sp.csc_matrix(A, copy=True)
+    A.sum_duplicates()
     return A
 
 
