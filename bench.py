@@ -9,14 +9,21 @@ section 8d (n = 40 000, m = 60 000, nnz(tril K) ~ 1.8e6, locality model w = 50, 
 N > 1: one process per GPU.  `python bench.py --gpus N` starts the N ranks itself (torch.distributed.run on 127.0.0.1,
 before anything touches a GPU; under torchrun it just runs as one rank).  Every rank factors+solves its own KKT system
 (different seed, same shape) -- replicas, weak scaling, no data-path collective; torch.distributed (RCCL) carries the
-barrier and the max-over-ranks of the elapsed time.  Behind the timed region the same ranks also run the
+barrier and the max-over-ranks of the elapsed time.  With --full, behind the timed region the same ranks also run the
 strong-scaling case of BASELINE config 5: ONE block-angular system (S-C5) with its elimination-tree subtrees sharded over
 the GPUs and an RCCL reduce of the parent-front contribution blocks; its numbers ride in config.sharded.
 
-One JSON line on rank 0 with `roofline` (dominant kernel = k_front_dataflow, the persistent launch that factors the big fronts of
-one level of the elimination tree -- FP64-MFMA tile tasks --, timed live with HIP events on the library's stream; plus `roofline.solve`, the HBM-bound triangular solves), `cpu_baseline` (the supernodal
-multifrontal CPU port on all host cores and on one, beside the simplicial oracle) and `parity` (HIP against the CPU
-oracle on BASELINE config 3 at full size).
+A plain run does what the headline figure needs and no more: set-up, warm-up, the timed steps, the correctness check of the
+last one, --dump-outputs, and one JSON line on rank 0 with `roofline` (dominant kernel = k_front_dataflow, the persistent launch
+that factors the big fronts of one level of the elimination tree -- FP64-MFMA tile tasks --, timed with HIP events on the
+library's stream during the timed steps; plus `roofline.solve`, the HBM-bound triangular solves; `traffic` quoted from the
+committed PMC summary).
+
+`--full` adds, behind the timed region, everything else the benchmark measures: the four-right-hand-side solve
+(`roofline.solve.batch4`), two live rocprofv3 passes for `roofline.traffic`, the KKT-level breakdown (`config.kkt_level`), the
+multi-GPU prediction (`config.sharded_model`, top-level `sharded`), `cpu_baseline` (the supernodal multifrontal CPU port on all
+host cores and on one, beside the simplicial oracle) with `parity` (HIP against the CPU oracle on BASELINE config 3 at full
+size), and at N > 1 the sharded strong-scaling leg.  The --no-* options skip single legs of a --full run.
 """
 import argparse
 import json
@@ -105,12 +112,16 @@ def units_for_rank(rank, world):
     return {"seed": rank, "systems_per_step": 1}
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="S-metric")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed region, also run every measurement and check beside the headline figure: the batched solve, "
+                         "live PMC passes, KKT-level breakdown, sharded model (N = 1) or sharded leg (N > 1, --mode both), CPU baselines "
+                         "and parity")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", default="S-C3")
     ap.add_argument("--no-kkt-level", action="store_true", help="skip the (untimed-region) KKT-level breakdown in config.kkt_level")
@@ -118,7 +129,7 @@ def main():
     ap.add_argument("--mode", default="both", choices=["both", "replicas", "sharded"],
                     help="N > 1: replicas = one KKT system per rank (weak scaling: the JSON line's value); sharded = ONE system, "
                          "elimination-tree subtrees over the ranks with an RCCL reduce of the contribution blocks (strong scaling, "
-                         "S-C5); both (default) = the replica line with the sharded numbers in config.sharded")
+                         "S-C5); both (default) = the replica line, with --full the sharded numbers in config.sharded")
     ap.add_argument("--sharded-config", default="S-C5")
     ap.add_argument("--no-sharded-model", action="store_true",
                     help="skip config.sharded_model: the measured multi-GPU prediction for BASELINE config 5 (per-part phases timed on this one GPU)")
@@ -128,6 +139,11 @@ def main():
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): the solution x, D of the "
                          "factor in pivot order, the inertia counts and the factorisation's flag; rank r > 0 adds the suffix _rank<r>; "
                          "--mode sharded: rank 0's x, inertia and flag of the sharded system")
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
@@ -204,13 +220,15 @@ def main():
     elapsed = max_over_ranks(elapsed, distributed)
     nlaunch, syrk_ms, syrk_flops = hip.get_profile()
     hip.profile_dominant(False)
-    # behind the timed region: the same solve with four right-hand sides in one batch (one pass over L for all four)
-    d_rhs4 = hip.dev_upload(np.tile(rhs, (4, 1)))
-    d_sol4 = hip.dev_alloc(8 * 4 * (n + m))
-    hip.ls_solve_dev(d_rhs4, d_sol4, 4)
-    hip.ls_solve_dev(d_rhs4, d_sol4, 4)
-    solve4_ms = hip.stats()["last_solve_ms"]
-    hip.dev_free(d_rhs4); hip.dev_free(d_sol4)
+    solve4_ms = None
+    if args.full:
+        # behind the timed region: the same solve with four right-hand sides in one batch (one pass over L for all four)
+        d_rhs4 = hip.dev_upload(np.tile(rhs, (4, 1)))
+        d_sol4 = hip.dev_alloc(8 * 4 * (n + m))
+        hip.ls_solve_dev(d_rhs4, d_sol4, 4)
+        hip.ls_solve_dev(d_rhs4, d_sol4, 4)
+        solve4_ms = hip.stats()["last_solve_ms"]
+        hip.dev_free(d_rhs4); hip.dev_free(d_sol4)
 
     # correctness of what was timed: inertia flag and residual of the last solve
     x = hip.dev_download(d_sol, (n + m,))
@@ -279,19 +297,21 @@ def main():
                 # the second kernel family of the step: the triangular solves, HBM-bound (L streamed once forward, once
                 # backward); achieved = algorithmic bytes / device time of the solve (HIP events on the library's stream)
                 "solve": {"bound": "hbm", "unit": "GB/s", "peak": 8000.0, "bytes": solve_bytes, "ms": solve_ms,
-                          "achieved": solve_bytes / (solve_ms * 1e-3) / 1e9, "frac": solve_bytes / (solve_ms * 1e-3) / 1e9 / 8000.0,
-                          "batch4": {"ms": solve4_ms, "ms_per_rhs": solve4_ms / 4, "achieved": 4 * solve_bytes / (solve4_ms * 1e-3) / 1e9,
-                                     "note": "four right-hand sides through one pass over L (okkt_solve with nrhs = 4)"}},
+                          "achieved": solve_bytes / (solve_ms * 1e-3) / 1e9, "frac": solve_bytes / (solve_ms * 1e-3) / 1e9 / 8000.0},
             },
         }
+        if solve4_ms is not None:
+            out["roofline"]["solve"]["batch4"] = {"ms": solve4_ms, "ms_per_rhs": solve4_ms / 4, "achieved": 4 * solve_bytes / (solve4_ms * 1e-3) / 1e9,
+                                                  "note": "four right-hand sides through one pass over L (okkt_solve with nrhs = 4)"}
     # the handle goes back before the KKT-level handles are created: they reuse its pooled stream set (api.cpp)
     hip.dev_free(d_vals); hip.dev_free(d_rhs); hip.dev_free(d_sol)
     inertia_final = hip.inertia
     perm_metric = hip.perm()
     gpu_metric = {"d": hip.diag(), "inertia": tuple(hip.inertia), "rhs": rhs, "x": x} if rank == 0 else None
     finalize_b(hip)
+    full_single = args.full and world == 1      # the --full legs of a one-GPU run
     if rank == 0:
-        if world == 1 and not args.no_live_pmc and "ROCPROFILER_REGISTER_LIBRARY" not in os.environ and "ROCP_TOOL_LIBRARIES" not in os.environ:
+        if full_single and not args.no_live_pmc and "ROCPROFILER_REGISTER_LIBRARY" not in os.environ and "ROCP_TOOL_LIBRARIES" not in os.environ:
             # HBM traffic of the dominant kernel measured in this run (not when this process is itself being profiled)
             live, detail = live_traffic(args.config)
             if live is not None:
@@ -300,9 +320,9 @@ def main():
             out["roofline"]["traffic_detail"] = detail
         else:
             out["roofline"]["traffic_detail"] = {"source": "committed summary profiles/r06_dataflow_pmc.json (scripts/profile_r06.sh)"}
-        if world == 1 and not args.no_kkt_level:
+        if full_single and not args.no_kkt_level:
             out["config"]["kkt_level"] = kkt_level_breakdown(prob, local_rank)
-        if world == 1 and not args.no_sharded_model:
+        if full_single and not args.no_sharded_model:
             # the strong-scaling case (BASELINE config 5) predicted from MEASURED components: every part's local phases and the
             # top of the tree timed alone on this GPU (scripts/sharded_model.py), not from flops
             try:
@@ -317,7 +337,7 @@ def main():
                                                 for p, v in sm.get("parts", {}).items()}}
             except Exception as exc:
                 out["config"]["sharded_model"] = {"error": f"{type(exc).__name__}: {str(exc)[:200]}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if full_single and not args.no_cpu_baseline:
             out["cpu_baseline"], out["parity"] = cpu_baseline(args.cpu_sample, st, K, perm_metric, n, m, local_rank, gpu_metric)
             # BASELINE.md holds no published number for this metric (the reference publishes none), so vs_baseline stays null.  The
             # ratio against the CPU port timed beside the GPU in this run is reported under its own name: it is a stand-in for the
@@ -328,7 +348,7 @@ def main():
                                               "permutation) on this host; not a speed-up over the reference's CHOLMOD path, which cannot run here"}
             if not args.no_kkt_level:
                 out["cpu_baseline"]["step_side_port"] = step_side_port(prob)
-    if distributed and args.mode == "both":
+    if args.full and distributed and args.mode == "both":
         # The sharded case rides behind the measured line and must never cost it: a watchdog prints the line without the
         # sharded numbers and ends the rank if the collectives of the sharded path do not come back (a rank that failed
         # would leave the others waiting in a reduce), and an exception is recorded instead of raised.

@@ -1,11 +1,11 @@
 #!/bin/bash
-# GPU box: the round-5 evidence in one call -- rocprofv3 statistics and PMC passes (profile_r05.sh), the default bench line, the task
+# GPU box: the round-5 evidence in one call -- rocprofv3 statistics and PMC passes (profile_r05.sh), the bench line with every leg (--full), the task
 # logs of the three configurations, the forward errors.  Everything lands in gpurun_out/profiles_r05/; copy what is to be judged to profiles/.
 export TMPDIR=/tmp
 OUT=gpurun_out/profiles_r05
 mkdir -p $OUT
 bash scripts/profile_r05.sh r05 > gpurun_out/profile_r05.log 2>&1
-timeout 900 python3 bench.py > $OUT/r05_bench.json 2> gpurun_out/r05_bench.err
+timeout 900 python3 bench.py --full > $OUT/r05_bench.json 2> $OUT/r05_bench.err
 for c in S-metric S-C3 S-C5; do
   rm -f /tmp/dflog.txt
   OKKT_DATAFLOW=1 OKKT_DEBUG_DATAFLOW=16 OKKT_DF_LOG=/tmp/dflog.txt timeout 600 python3 scripts/df_check.py --run $c /tmp/x.npz > /dev/null 2>&1

@@ -1,11 +1,11 @@
 #!/bin/bash
-# GPU box: the round-6 evidence in one call -- rocprofv3 statistics and PMC passes (profile_r06.sh), the default bench line, the task
+# GPU box: the round-6 evidence in one call -- rocprofv3 statistics and PMC passes (profile_r06.sh), the bench line with every leg (--full), the task
 # logs of the three configurations, the forward errors.  Everything lands in gpurun_out/profiles_r06/; copy what is to be judged to profiles/.
 export TMPDIR=/tmp
 OUT=gpurun_out/profiles_r06
 mkdir -p $OUT
 bash scripts/profile_r06.sh r06 > gpurun_out/profile_r06.log 2>&1
-timeout 900 python3 bench.py > $OUT/r06_bench.json 2> gpurun_out/r06_bench.err
+timeout 900 python3 bench.py --full > $OUT/r06_bench.json 2> $OUT/r06_bench.err
 for c in S-metric S-C3 S-C5; do
   rm -f /tmp/dflog.txt
   # (the task log is instrumentation the product library does not carry: libonephase_kkt_log.so = the product kernel + the log)

@@ -108,3 +108,56 @@ def test_dump_outputs_hold_the_last_timed_step(tmp_path):
     assert np.max(np.abs(M @ got["x"] - rhs)) <= 1e-8 * np.max(np.abs(rhs))
     assert got["inertia"].tolist() == [n, m, 0, 0] and got["flag"].tolist() == [1]
     assert np.sum(got["d"] > 0) == n and np.sum(got["d"] < 0) == m
+
+
+def test_a_plain_run_is_the_default_and_the_other_legs_need_full():
+    import bench
+    plain = bench.arg_parser().parse_args([])
+    assert plain.full is False
+    assert not (plain.no_cpu_baseline or plain.no_kkt_level or plain.no_live_pmc or plain.no_sharded_model)
+    assert bench.arg_parser().parse_args(["--full"]).full is True
+
+
+# what only --full adds to the line: measurements and checks beside the headline figure
+FULL_ONLY_KEYS = ("cpu_baseline", "parity", "vs_cpu_port", "sharded")
+FULL_ONLY_CONFIG_KEYS = ("kkt_level", "sharded_model", "sharded")
+
+
+@pytest.mark.gpu
+def test_plain_run_spends_little_outside_its_steps():
+    import subprocess
+    import time
+    steps, warmup = 2, 1
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)]
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config", "roofline"):
+        assert k in d, k
+    assert d["steps"] == steps and d["warmup"] == warmup and d["config"]["inertia_ok"]
+    assert abs(d["value"] - d["steps"] / (d["ms_per_step"] * d["steps"] / 1e3)) < 1e-6 * d["value"]
+    assert not [k for k in FULL_ONLY_KEYS if k in d] and not [k for k in FULL_ONLY_CONFIG_KEYS if k in d["config"]]
+    assert "batch4" not in d["roofline"]["solve"] and d["roofline"]["traffic_detail"]["source"].startswith("committed summary")
+    outside = wall - (steps + warmup) * d["ms_per_step"] / 1e3
+    assert outside < 30.0, f"{outside:.1f} s outside the warm-up and timed steps"
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_other_legs():
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "S-small", "--cpu-sample", "S-small", "--steps", "2", "--warmup", "1",
+           "--full", "--no-live-pmc", "--no-sharded-model"]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["config"]["inertia_ok"]
+    b4 = d["roofline"]["solve"]["batch4"]
+    assert b4["ms"] > 0 and b4["ms_per_rhs"] == b4["ms"] / 4
+    c = d["cpu_baseline"]
+    assert c["kind"] == "port" and c["unit"] == d["unit"] and c["value"] > 0 and c["ports_agree"] and "step_side_port" in c
+    assert d["parity"]["inertia_equal"] and d["parity"]["sign_D_equal"] and d["parity"]["rel_err_x"] <= d["parity"]["tolerance_x"]
+    assert d["vs_cpu_port"]["ratio"] > 0
+    assert set(d["config"]["kkt_level"]) >= {"symmetric", "schur", "step_side"}
+    assert "sharded_model" not in d["config"] and "sharded" not in d      # skipped on request
