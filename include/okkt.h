@@ -215,6 +215,38 @@ int okkt_forward_error(okkt_handle h, const double* nzval, const double* rhs, co
 /* the same with device pointers for nzval, rhs and x; ferr_out and berr_out are host memory */
 int okkt_forward_error_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, const double* d_x, int64_t nrhs,
                            double* ferr_out, double* berr_out);
+/* ---- Schur mode: partial factorisation with a dense Schur complement ----------------------------------
+ * A is the analysed symmetric matrix of order dim; the Schur set is idx[0..ns), distinct 0-based original indices, and orders the
+ * rows and columns of S; A11 is A without the set (the interior), A22 the set's block.  The handle factors A11 and assembles
+ * S = A22 - A21 A11^-1 A12 on the device without factoring it.
+ *   Definite kind: S is positive definite exactly when A is (A11 being positive definite).
+ *   Symmetric kind: inertia(A) = inertia(A11) + inertia(S) (Haynsworth inertia additivity).
+ *   Whenever S x2 = r2 with r2 from okkt_schur_condense, okkt_schur_expand returns the x that solves A x = b.
+ * On a handle in Schur mode okkt_factor(_dev), okkt_solve(_dev), okkt_solve_refine(_dev), okkt_condest(_dev),
+ * okkt_forward_error(_dev), okkt_dist_set_partition with nparts > 1 and the other okkt_dist_* calls return OKKT_ERR_INVALID (the handle
+ * stays usable); the Schur calls are refused the same way on a handle without a set.  Early exit (okkt_set_early_exit) does not apply
+ * to okkt_factor_schur.  A factor that completed with flag 0 can still be exported, condensed and expanded. */
+/* Call before okkt_analyze.  A different set forces a re-analysis; ns = 0 clears the set, and the handle then behaves exactly as
+ * one that never had a set.  Refused: duplicates, indices out of range, ns >= dim (checked by okkt_analyze), ns < 0.  The interior
+ * is ordered by opts.ordering on the pattern of A11; the set follows in idx order as one final supernode.  With ordering 2 the
+ * permutation must end with idx in order. */
+int okkt_set_schur(okkt_handle h, int64_t ns, const int64_t* idx);
+/* Factor A11 and assemble S.  n1 + m1 = dim - ns.  Returns 1 / 0 under the contract of okkt_factor applied to A11 (symmetric:
+ * pos == n1 && neg == m1 and nothing non-finite; definite: every pivot > 0), or < 0 on error.  The counts cover the dim - ns pivots
+ * of A11. */
+int okkt_factor_schur(okkt_handle h, const double* nzval, int64_t n1, int64_t m1, int sym_kind, okkt_inertia* inertia_out);
+int okkt_factor_schur_dev(okkt_handle h, const double* d_nzval, int64_t n1, int64_t m1, int sym_kind, okkt_inertia* inertia_out);
+/* S as a full symmetric ns x ns column-major matrix, rows and columns in idx order, leading dimension ld >= ns */
+int okkt_get_schur(okkt_handle h, double* S, int64_t ld);
+int okkt_get_schur_dev(okkt_handle h, double* d_S, int64_t ld);
+/* condense: r2 = b2 - A21 A11^-1 b1 for each right-hand side (rhs: dim x nrhs, original order; r2: ns x nrhs, idx order) */
+int okkt_schur_condense(okkt_handle h, const double* rhs, double* r2, int64_t nrhs);
+int okkt_schur_condense_dev(okkt_handle h, const double* d_rhs, double* d_r2, int64_t nrhs);
+/* expand: x[idx] = x2 and x1 = A11^-1 (b1 - A12 x2), x in original order (dim x nrhs).  Stateless: it does not rely on an earlier
+ * condense call.  rhs may alias x. */
+int okkt_schur_expand(okkt_handle h, const double* rhs, const double* x2, double* x, int64_t nrhs);
+int okkt_schur_expand_dev(okkt_handle h, const double* d_rhs, const double* d_x2, double* d_x, int64_t nrhs);
+
 /* diag(F): the D of LDL^T in pivot (permuted) order, as `diag(solver._factor)` (julia.jl:72) */
 int okkt_get_diag(okkt_handle h, double* d_out /* [dim] */);
 /* L as CSC in permuted numbering (unit diagonal not stored), for parity tests; pass NULLs to size */

@@ -188,6 +188,15 @@ SIGNATURES = {
     "okkt_condest_indices": (C.c_int64, [_vp, _i64p, C.c_int64]),
     "okkt_forward_error": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, _f64p, _f64p]),
     "okkt_forward_error_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _f64p, _f64p]),
+    "okkt_set_schur": (C.c_int, [_vp, C.c_int64, _i64p]),
+    "okkt_factor_schur": (C.c_int, [_vp, _f64p, C.c_int64, C.c_int64, C.c_int, C.POINTER(OkktInertia)]),
+    "okkt_factor_schur_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, C.POINTER(OkktInertia)]),
+    "okkt_get_schur": (C.c_int, [_vp, _f64p, C.c_int64]),
+    "okkt_get_schur_dev": (C.c_int, [_vp, _vp, C.c_int64]),
+    "okkt_schur_condense": (C.c_int, [_vp, _f64p, _f64p, C.c_int64]),
+    "okkt_schur_condense_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64]),
+    "okkt_schur_expand": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64]),
+    "okkt_schur_expand_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64]),
     "okkt_get_diag": (C.c_int, [_vp, _f64p]),
     "okkt_get_factor_csc": (C.c_int, [_vp, _i64p, _i64p, _f64p, _i64p]),
     "okkt_dev_alloc": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp)]),

@@ -58,12 +58,13 @@ int solver_factor_device(okkt_solver_s* h, const double* d_vals, int64_t n, int6
                          okkt_inertia* out, bool zero_tol) {
   int rc = solver_ensure_numeric(h);
   if (rc != OKKT_OK) return rc;
-  if (n < 0 || m < 0 || n + m != h->S.n) return solver_set_error(h, OKKT_ERR_INVALID, "n + m does not match the analysed dimension");
+  const int64_t order = h->S.n - h->S.nschur;     // the pivots factored: A11's in Schur mode (its front is assembled, not factored)
+  if (n < 0 || m < 0 || n + m != order) return solver_set_error(h, OKKT_ERR_INVALID, "n + m does not match the analysed dimension");
   if (sym_kind != OKKT_SYM_DEFINITE && sym_kind != OKKT_SYM_SYMMETRIC) return solver_set_error(h, OKKT_ERR_INVALID, "unknown sym_kind");
   if (sym_kind == OKKT_SYM_DEFINITE && m != 0) return solver_set_error(h, OKKT_ERR_INVALID, ":definite requires m == 0 (julia.jl:30)");
   const double tol = (sym_kind == OKKT_SYM_DEFINITE || zero_tol) ? 0.0 : h->opts.inertia_tol;
   h->factored = false;
-  h->N.early_check = h->early_exit;
+  h->N.early_check = h->early_exit && h->S.nschur == 0;
   h->N.early_device = h->early_exit && h->last_failed;   // the previous factorisation failed the inertia: this one is a retry
   h->N.early_n = n;
   h->N.early_m = m;
@@ -84,7 +85,7 @@ int solver_factor_device(okkt_solver_s* h, const double* d_vals, int64_t n, int6
   h->last_failed = true;
   if (h->N.early_exited || cnt[4] != 0) return 0;   // wrong inertia decided before the end: counts are partial, no factor to solve with
   h->factored = true;
-  if (in.pos + in.neg + in.zero + in.nonfinite != h->S.n)
+  if (in.pos + in.neg + in.zero + in.nonfinite != order)
     return solver_set_error(h, OKKT_ERR_INTERNAL, "pivot counts do not add up to the matrix order");
   if (in.nonfinite > 0) return 0;                       // julia.jl:77-89
   const int flag = sym_kind == OKKT_SYM_DEFINITE ? (in.pos == n ? 1 : 0)   // PosDefException <=> some pivot <= 0
@@ -143,6 +144,7 @@ static int refine_ready(okkt_solver_s* h, bool need_factor) {
   if (h->S.nparts > 1)
     return solver_set_error(h, OKKT_ERR_INVALID, "residuals and refinement are not available on a partitioned handle (okkt_dist_set_partition with nparts > 1)");
   if (need_factor) {
+    if (schur_mode(h)) return schur_refuse(h, "refinement");
     if ((rc = solver_ensure_numeric(h)) != OKKT_OK) return rc;
     if (!h->factored) return solver_set_error(h, OKKT_ERR_INVALID, "refinement called before a factorisation");
   }
@@ -322,6 +324,7 @@ int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* 
 
 // device, analysis, no partition, a complete factorisation; the refinement map and the estimator's blocks
 static int condest_ready(okkt_solver_s* h) {
+  if (schur_mode(h)) return schur_refuse(h, "the condition estimate / forward error bound");
   int rc = refine_ready(h, false);
   if (rc != OKKT_OK) return rc;
   if (!h->numeric_ready || !h->factored)
@@ -789,7 +792,7 @@ int okkt_analyze(okkt_handle h, int64_t dim, const int64_t* colptr, const int64_
     h->analyzed = false;
     h->factored = false;
     std::string e = analyze_pattern(dim, colptr, rowval, index_base, h->sopts,
-                                    h->opts.ordering == 2 ? h->user_perm.data() : nullptr, h->S);
+                                    h->opts.ordering == 2 ? h->user_perm.data() : nullptr, h->S, h->schur_idx.data(), (int64_t)h->schur_idx.size());
     if (!e.empty()) return solver_set_error(h, OKKT_ERR_INVALID, e);
     h->analyze_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     h->analyzed = true;
@@ -860,6 +863,7 @@ int okkt_get_stats(okkt_handle h, okkt_stats* out) {
 
 int okkt_factor_dev(okkt_handle h, const double* d_nzval, int64_t n, int64_t m, int sym_kind, okkt_inertia* out) {
   if (!h || (!d_nzval && h->S.nnz_in > 0)) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_factor_dev");
   try {
     return solver_factor_device(h, d_nzval, n, m, sym_kind, out);
   } catch (...) {
@@ -869,6 +873,7 @@ int okkt_factor_dev(okkt_handle h, const double* d_nzval, int64_t n, int64_t m, 
 
 int okkt_factor(okkt_handle h, const double* nzval, int64_t n, int64_t m, int sym_kind, okkt_inertia* out) {
   if (!h || (!nzval && h->S.nnz_in > 0)) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_factor");
   try {
     int rc = solver_ensure_numeric(h);
     if (rc != OKKT_OK) return rc;
@@ -882,8 +887,21 @@ int okkt_factor(okkt_handle h, const double* nzval, int64_t n, int64_t m, int sy
   }
 }
 
+// h->d_rhs_stage holds at least len doubles
+static int rhs_stage(okkt_solver_s* h, int64_t len) {
+  if (h->rhs_stage_len >= len) return OKKT_OK;
+  if (h->d_rhs_stage) (void)hipFree(h->d_rhs_stage);
+  h->d_rhs_stage = nullptr;
+  h->rhs_stage_len = 0;
+  if (hipMalloc((void**)&h->d_rhs_stage, (size_t)len * sizeof(double)) != hipSuccess)
+    return solver_set_error(h, OKKT_ERR_ALLOC, "rhs staging allocation failed");
+  h->rhs_stage_len = len;
+  return OKKT_OK;
+}
+
 int okkt_solve_dev(okkt_handle h, const double* d_rhs, double* d_sol, int64_t nrhs) {
   if (!h || !d_rhs || !d_sol) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_solve_dev");
   try {
     return solver_solve_device(h, d_rhs, d_sol, nrhs);
   } catch (...) {
@@ -893,20 +911,14 @@ int okkt_solve_dev(okkt_handle h, const double* d_rhs, double* d_sol, int64_t nr
 
 int okkt_solve(okkt_handle h, const double* rhs, double* sol, int64_t nrhs) {
   if (!h || !rhs || !sol) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_solve");
   try {
     int rc = solver_ensure_numeric(h);
     if (rc != OKKT_OK) return rc;
     if (!h->factored) return solver_set_error(h, OKKT_ERR_INVALID, "solve called before a factorisation");
     const int64_t len = h->S.n * std::max<int64_t>(nrhs, 0);
     if (len == 0) return OKKT_OK;
-    if (h->rhs_stage_len < len) {
-      if (h->d_rhs_stage) (void)hipFree(h->d_rhs_stage);
-      h->d_rhs_stage = nullptr;
-      h->rhs_stage_len = 0;
-      if (hipMalloc((void**)&h->d_rhs_stage, (size_t)len * sizeof(double)) != hipSuccess)
-        return solver_set_error(h, OKKT_ERR_ALLOC, "rhs staging allocation failed");
-      h->rhs_stage_len = len;
-    }
+    if ((rc = rhs_stage(h, len)) != OKKT_OK) return rc;
     hipError_t he = hipMemcpyAsync(h->d_rhs_stage, rhs, (size_t)len * sizeof(double), hipMemcpyHostToDevice, h->stream);
     if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("rhs upload: ") + hipGetErrorString(he));
     rc = solver_solve_device(h, h->d_rhs_stage, h->d_rhs_stage, nrhs);
@@ -1222,4 +1234,200 @@ int64_t okkt_debug_dataflow_queue(int32_t nfronts, const int32_t* f, const int32
   } catch (...) { return OKKT_ERR_ALLOC; }
 }
 
+// ---- Schur mode ------------------------------------------------------------------------------
+
+int okkt_set_schur(okkt_handle h, int64_t ns, const int64_t* idx) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (ns < 0) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_schur: ns < 0");
+  if (ns > 0 && !idx) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_schur: null idx");
+  try {
+    std::vector<int64_t> v(idx, idx + ns);
+    std::vector<int64_t> sorted(v);
+    std::sort(sorted.begin(), sorted.end());
+    if (ns > 0 && sorted[0] < 0) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_schur: negative index");
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_schur: duplicate index");
+    // the order of the analysed pattern is known: the range is checked now (okkt_analyze checks it against the pattern it is given)
+    if (h->analyzed && ns > 0 && (ns >= h->S.n || sorted.back() >= h->S.n))
+      return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_schur: index out of range or ns >= dim of the analysed pattern");
+    if (v == h->schur_idx) return OKKT_OK;
+    h->schur_idx.swap(v);
+    h->analyzed = false;      // the plan changes: okkt_analyze builds it again
+    h->factored = false;
+    return OKKT_OK;
+  } catch (const std::bad_alloc&) {
+    return solver_set_error(h, OKKT_ERR_ALLOC, "out of host memory in okkt_set_schur");
+  }
+}
+
+// Schur mode, analysed, device plan ready; need_factor: a complete okkt_factor_schur
+static int schur_ready(okkt_solver_s* h, bool need_factor) {
+  if (!schur_mode(h)) return solver_set_error(h, OKKT_ERR_INVALID, "the handle is not in Schur mode (okkt_set_schur before okkt_analyze)");
+  int rc = solver_ensure_numeric(h);
+  if (rc != OKKT_OK) return rc;
+  if (h->S.nschur != (int64_t)h->schur_idx.size() || h->N.schur_sn < 0) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_analyze has not been called since okkt_set_schur");
+  if (need_factor && !h->factored) return solver_set_error(h, OKKT_ERR_INVALID, "no complete okkt_factor_schur");
+  return OKKT_OK;
+}
+
+int okkt_factor_schur_dev(okkt_handle h, const double* d_nzval, int64_t n1, int64_t m1, int sym_kind, okkt_inertia* out) {
+  if (!h || (!d_nzval && h->S.nnz_in > 0)) return OKKT_ERR_INVALID;
+  try {
+    int rc = schur_ready(h, false);
+    if (rc != OKKT_OK) return rc;
+    return solver_factor_device(h, d_nzval, n1, m1, sym_kind, out);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_factor_schur_dev");
+  }
+}
+
+int okkt_factor_schur(okkt_handle h, const double* nzval, int64_t n1, int64_t m1, int sym_kind, okkt_inertia* out) {
+  if (!h || (!nzval && h->S.nnz_in > 0)) return OKKT_ERR_INVALID;
+  try {
+    int rc = schur_ready(h, false);
+    if (rc != OKKT_OK) return rc;
+    if (h->S.nnz_in > 0) {
+      hipError_t he = hipMemcpyAsync(h->N.vals_owned, nzval, (size_t)h->S.nnz_in * sizeof(double), hipMemcpyHostToDevice, h->stream);
+      if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("nzval upload: ") + hipGetErrorString(he));
+    }
+    return solver_factor_device(h, h->N.vals_owned, n1, m1, sym_kind, out);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_factor_schur");
+  }
+}
+
+// a device buffer for the length of one host-side call
+namespace {
+struct DevTemp {
+  double* p = nullptr;
+  ~DevTemp() { if (p) (void)hipFree(p); }
+  bool alloc(int64_t n) { return n <= 0 || hipMalloc((void**)&p, (size_t)n * sizeof(double)) == hipSuccess; }
+};
+}  // namespace
+
+static int schur_sync(okkt_solver_s* h, const char* what) {
+  hipError_t he = hipGetLastError();
+  if (he == hipSuccess) he = hipStreamSynchronize(h->stream);
+  if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string(what) + " failed: " + hipGetErrorString(he));
+  return OKKT_OK;
+}
+
+int okkt_get_schur_dev(okkt_handle h, double* d_S, int64_t ld) {
+  if (!h || !d_S) return OKKT_ERR_INVALID;
+  try {
+    int rc = schur_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    if (ld < h->S.nschur) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_get_schur: ld < ns");
+    schur_export_enqueue(h->N, d_S, ld);
+    return schur_sync(h, "Schur complement export");
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_get_schur_dev");
+  }
+}
+
+int okkt_get_schur(okkt_handle h, double* S, int64_t ld) {
+  if (!h || !S) return OKKT_ERR_INVALID;
+  try {
+    int rc = schur_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    const int64_t ns = h->S.nschur;
+    if (ld < ns) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_get_schur: ld < ns");
+    DevTemp t;
+    if (!t.alloc(ns * ns)) return solver_set_error(h, OKKT_ERR_ALLOC, "Schur complement staging allocation failed");
+    schur_export_enqueue(h->N, t.p, ns);
+    if ((rc = schur_sync(h, "Schur complement export")) != OKKT_OK) return rc;
+    if (hipMemcpy2D(S, (size_t)ld * sizeof(double), t.p, (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), (size_t)ns, hipMemcpyDeviceToHost) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "Schur complement download failed");
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_get_schur");
+  }
+}
+
+// batches of up to kMaxRhs right-hand sides, as solver_solve_enqueue; d_x2 == nullptr: condense into d_r2, else expand into d_x
+static int schur_sweeps(okkt_solver_s* h, const double* d_rhs, double* d_r2, const double* d_x2, double* d_x, int64_t nrhs) {
+  const int64_t n = h->S.n, ns = h->S.nschur;
+  for (int64_t r = 0; r < nrhs;) {
+    const int nr = (int)std::min<int64_t>(nrhs - r, kMaxRhs);
+    const int R = nr >= 3 ? 4 : nr;
+    solve_permute_in(h->N, d_rhs + r * n, n, nr, R);
+    std::string e = d_x2 ? schur_expand_enqueue(h->N, d_x2 + r * ns, nr, R) : schur_condense_enqueue(h->N, d_r2 + r * ns, nr, R);
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
+    if (d_x2) solve_permute_out(h->N, d_x + r * n, n, nr, R, false);
+    r += nr;
+  }
+  return schur_sync(h, d_x2 ? "Schur expand" : "Schur condense");
+}
+
+int okkt_schur_condense_dev(okkt_handle h, const double* d_rhs, double* d_r2, int64_t nrhs) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  if (nrhs > 0 && (!d_rhs || !d_r2)) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+  try {
+    int rc = schur_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    return schur_sweeps(h, d_rhs, d_r2, nullptr, nullptr, nrhs);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_condense_dev");
+  }
+}
+
+int okkt_schur_condense(okkt_handle h, const double* rhs, double* r2, int64_t nrhs) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  if (nrhs > 0 && (!rhs || !r2)) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+  try {
+    int rc = schur_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    const int64_t len = h->S.n * nrhs, len2 = h->S.nschur * nrhs;
+    if (len == 0) return OKKT_OK;
+    if ((rc = rhs_stage(h, len)) != OKKT_OK) return rc;
+    DevTemp t;
+    if (!t.alloc(len2)) return solver_set_error(h, OKKT_ERR_ALLOC, "Schur condense staging allocation failed");
+    if (hipMemcpyAsync(h->d_rhs_stage, rhs, (size_t)len * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "rhs upload failed");
+    if ((rc = schur_sweeps(h, h->d_rhs_stage, t.p, nullptr, nullptr, nrhs)) != OKKT_OK) return rc;
+    if (hipMemcpy(r2, t.p, (size_t)len2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, "r2 download failed");
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_condense");
+  }
+}
+
+int okkt_schur_expand_dev(okkt_handle h, const double* d_rhs, const double* d_x2, double* d_x, int64_t nrhs) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  if (nrhs > 0 && (!d_rhs || !d_x2 || !d_x)) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+  try {
+    int rc = schur_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    return schur_sweeps(h, d_rhs, nullptr, d_x2, d_x, nrhs);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_expand_dev");
+  }
+}
+
+int okkt_schur_expand(okkt_handle h, const double* rhs, const double* x2, double* x, int64_t nrhs) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  if (nrhs > 0 && (!rhs || !x2 || !x)) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+  try {
+    int rc = schur_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    const int64_t len = h->S.n * nrhs, len2 = h->S.nschur * nrhs;
+    if (len == 0) return OKKT_OK;
+    if ((rc = rhs_stage(h, len)) != OKKT_OK) return rc;
+    DevTemp t;
+    if (!t.alloc(len2)) return solver_set_error(h, OKKT_ERR_ALLOC, "Schur expand staging allocation failed");
+    hipError_t he = hipMemcpyAsync(h->d_rhs_stage, rhs, (size_t)len * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(t.p, x2, (size_t)len2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, "Schur expand upload failed");
+    if ((rc = schur_sweeps(h, h->d_rhs_stage, nullptr, t.p, h->d_rhs_stage, nrhs)) != OKKT_OK) return rc;
+    if (hipMemcpy(x, h->d_rhs_stage, (size_t)len * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, "x download failed");
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_expand");
+  }
+}
+
 }  // extern "C"
+

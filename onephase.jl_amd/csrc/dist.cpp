@@ -39,6 +39,7 @@ extern "C" {
 
 int okkt_dist_set_partition(okkt_handle h, int nparts, int part_id) {
   if (!h || nparts < 1 || part_id < 0 || part_id >= nparts) return OKKT_ERR_INVALID;
+  if (nparts > 1 && schur_mode(h)) return schur_refuse(h, "okkt_dist_set_partition with nparts > 1");
   if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_analyze has not been called");
   if (h->numeric_ready) {
     (void)hipSetDevice(h->device);
@@ -56,6 +57,7 @@ int okkt_dist_set_partition(okkt_handle h, int nparts, int part_id) {
 int okkt_dist_info(okkt_handle h, int64_t* cb_doubles, int64_t* cv_doubles, int64_t* n_boundary,
                    double* part_flops_out, double* top_flops_out) {
   if (!h) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_info");
   if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "not analysed");
   const Symbolic& S = h->S;
   if (cb_doubles) *cb_doubles = S.boundary_cb.empty() ? 0 : S.boundary_cb.back();
@@ -68,6 +70,7 @@ int okkt_dist_info(okkt_handle h, int64_t* cb_doubles, int64_t* cv_doubles, int6
 
 int okkt_dist_get_owner(okkt_handle h, int64_t* sn_owner_out, int64_t* col_owner_out, int64_t* sn_parent_out) {
   if (!h) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_get_owner");
   if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "not analysed");
   const Symbolic& S = h->S;
   for (int s = 0; s < S.nsuper; ++s) {
@@ -81,6 +84,7 @@ int okkt_dist_get_owner(okkt_handle h, int64_t* sn_owner_out, int64_t* col_owner
 
 int okkt_dist_factor_local(okkt_handle h, const double* d_nzval, int64_t n, int64_t m, int sym_kind) {
   if (!h || (!d_nzval && h->S.nnz_in > 0)) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_factor_local");
   int rc = need_dist(h);
   if (rc != OKKT_OK) return rc;
   if (n < 0 || m < 0 || n + m != h->S.n) return solver_set_error(h, OKKT_ERR_INVALID, "n + m does not match the analysed dimension");
@@ -100,6 +104,7 @@ int okkt_dist_factor_local(okkt_handle h, const double* d_nzval, int64_t n, int6
 
 int okkt_dist_cb(okkt_handle h, double* d_buf, int unpack) {
   if (!h || !d_buf) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_cb");
   int rc = need_dist(h);
   if (rc != OKKT_OK) return rc;
   std::string e = numeric_dist_pack(h->N, 0, unpack, d_buf);
@@ -109,6 +114,7 @@ int okkt_dist_cb(okkt_handle h, double* d_buf, int unpack) {
 
 int okkt_dist_factor_top(okkt_handle h) {
   if (!h) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_factor_top");
   int rc = need_dist(h);
   if (rc != OKKT_OK) return rc;
   std::string e = numeric_factor_enqueue(h->N, h->dist_vals, h->dist_tol, 1, false);
@@ -118,6 +124,7 @@ int okkt_dist_factor_top(okkt_handle h) {
 
 int okkt_dist_counts(okkt_handle h, int64_t out[4]) {
   if (!h || !out) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_counts");
   int rc = need_dist(h);
   if (rc != OKKT_OK) return rc;
   unsigned long long cnt[6];
@@ -132,6 +139,7 @@ int okkt_dist_counts(okkt_handle h, int64_t out[4]) {
 
 int okkt_dist_finish(okkt_handle h, const int64_t total[4]) {
   if (!h || !total) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_finish");
   h->factored = true;
   if (total[0] + total[1] + total[2] + total[3] != h->S.n)
     return solver_set_error(h, OKKT_ERR_INTERNAL, "pivot counts do not add up to the matrix order");
@@ -142,6 +150,7 @@ int okkt_dist_finish(okkt_handle h, const int64_t total[4]) {
 
 int okkt_dist_solve_begin(okkt_handle h, const double* d_rhs) {
   if (!h || !d_rhs) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_solve_begin");
   int rc = need_dist(h);
   if (rc != OKKT_OK) return rc;
   if (!h->factored) return solver_set_error(h, OKKT_ERR_INVALID, "solve called before a factorisation");
@@ -153,6 +162,7 @@ int okkt_dist_solve_begin(okkt_handle h, const double* d_rhs) {
 
 int okkt_dist_cv(okkt_handle h, double* d_buf, int unpack) {
   if (!h || !d_buf) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_cv");
   int rc = need_dist(h);
   if (rc != OKKT_OK) return rc;
   std::string e = numeric_dist_pack(h->N, 1, unpack, d_buf);
@@ -162,6 +172,7 @@ int okkt_dist_cv(okkt_handle h, double* d_buf, int unpack) {
 
 int okkt_dist_solve_top(okkt_handle h) {
   if (!h) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_solve_top");
   int rc = need_dist(h);
   if (rc != OKKT_OK) return rc;
   std::string e = solve_fwd_enqueue(h->N, 1, 1);
@@ -172,6 +183,7 @@ int okkt_dist_solve_top(okkt_handle h) {
 
 int okkt_dist_x(okkt_handle h, double* d_buf, int mode) {
   if (!h || !d_buf || mode < 0 || mode > 2) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_x");
   int rc = need_dist(h);
   if (rc != OKKT_OK) return rc;
   std::string e = numeric_dist_x(h->N, mode, d_buf);
@@ -181,6 +193,7 @@ int okkt_dist_x(okkt_handle h, double* d_buf, int mode) {
 
 int okkt_dist_solve_end(okkt_handle h) {
   if (!h) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_solve_end");
   int rc = need_dist(h);
   if (rc != OKKT_OK) return rc;
   std::string e = solve_bwd_enqueue(h->N, 0, 1);
@@ -256,6 +269,7 @@ int okkt_dist_unique_id(void* id_out) {
 
 int okkt_dist_comm_init(okkt_handle h, int nranks, int rank, const void* id) {
   if (!h || !id || nranks < 1 || rank < 0 || rank >= nranks) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_comm_init");
   RcclApi& a = rccl();
   if (!a.err.empty()) return solver_set_error(h, OKKT_ERR_NO_DEVICE, a.err);
   if (!h->device_ready) return solver_set_error(h, OKKT_ERR_NO_DEVICE, "no HIP device");
@@ -319,6 +333,7 @@ int okkt_dist_comm_destroy(okkt_handle h) {
 
 int okkt_dist_factor(okkt_handle h, const double* d_nzval, int64_t n, int64_t m, int sym_kind, okkt_inertia* inertia_out) {
   if (!h || (!d_nzval && h->S.nnz_in > 0)) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_factor");
   if (!h->rccl_comm) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_dist_comm_init has not been called");
   int rc = need_dist(h);
   if (rc != OKKT_OK) return rc;
@@ -362,6 +377,7 @@ int okkt_dist_factor(okkt_handle h, const double* d_nzval, int64_t n, int64_t m,
 
 int okkt_dist_solve(okkt_handle h, const double* d_rhs, double* d_sol) {
   if (!h || !d_rhs || !d_sol) return OKKT_ERR_INVALID;
+  if (schur_mode(h)) return schur_refuse(h, "okkt_dist_solve");
   if (!h->rccl_comm) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_dist_comm_init has not been called");
   int rc = need_dist(h);
   if (rc != OKKT_OK) return rc;

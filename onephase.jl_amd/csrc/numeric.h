@@ -242,6 +242,11 @@ struct Numeric {
   std::vector<std::pair<int, int>> big_fk;  // (f, k) of sched entries (host copy, big fronts only need it)
   std::vector<int> sched_host;
   std::vector<int> sn_f, sn_k;           // per supernode
+  // Schur mode (Symbolic::nschur > 0): the Schur front (the last supernode; -1: off), its first big-column index (extend-add lists)
+  // and a one-entry device list holding it
+  int schur_sn = -1;
+  int64_t schur_gcb = 0;
+  int* schur_list = nullptr;
 };
 
 // returns "" or an error message
@@ -266,6 +271,13 @@ std::string numeric_dist_pack(Numeric& N, int what, int unpack, double* d_buf);
 std::string numeric_dist_x(Numeric& N, int mode, double* d_buf);
 // out[0..3] = pos, neg, zero, nonfinite summed over the counter slots, on the device (no synchronisation)
 void numeric_sum_counts_device(Numeric& N, long long* d_out4);
+// Schur mode (solve.hip), R right-hand sides already permuted into d.xwork, nr of them wanted:
+// condense: the forward sweep over the interior, then r2 (ns x nr, Schur-set order) = the Schur front's gathered right-hand side;
+// expand: the forward sweep over the interior, x2 (ns x nr) into the Schur columns of xwork, the backward sweep over the interior
+std::string schur_condense_enqueue(Numeric& N, double* d_r2, int nr, int R);
+std::string schur_expand_enqueue(Numeric& N, const double* d_x2, int nr, int R);
+// S (lower triangle of the assembled Schur front) -> d_S full and symmetric, leading dimension ld
+void schur_export_enqueue(Numeric& N, double* d_S, int64_t ld);
 // enqueue forward/diagonal/backward solves for the R right-hand sides already stored (permuted) in d.xwork
 std::string numeric_solve_enqueue(Numeric& N, int R);
 // diagadd[iperm] = (orig index < nshift) ? delta : 0, via perm

@@ -1099,6 +1099,10 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
   auto fof = [&](int s2) { return (int)(S.row_ptr[s2 + 1] - S.row_ptr[s2]); };
   // forbid[s]: front s is a unit of its own (neither the root nor a member of a multi-front task); see the second pass below
   std::vector<char> forbid(ns, 0);
+  // Schur mode: the last supernode is the Schur front -- a unit of its own that no schedule holds (assembled by numeric_factor_enqueue
+  // behind the interior, never factored, left out of the solve sweeps)
+  N.schur_sn = S.nschur > 0 ? ns - 1 : -1;
+  if (N.schur_sn >= 0) forbid[N.schur_sn] = 1;
   auto form_units = [&]() {
     std::fill(ulevel.begin(), ulevel.end(), 0);
     std::vector<char> allsmall(ns), assigned(ns, 0);
@@ -1164,14 +1168,15 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
     if (any) form_units();
   }
   int nulev = 0;
-  for (int s2 = 0; s2 < ns; ++s2) if (unit_root[s2] == s2) nulev = std::max(nulev, ulevel[s2] + 1);
+  for (int s2 = 0; s2 < ns; ++s2) if (unit_root[s2] == s2 && s2 != N.schur_sn) nulev = std::max(nulev, ulevel[s2] + 1);
   std::vector<std::vector<int>> units_at(nulev);
-  for (int s2 = 0; s2 < ns; ++s2) if (unit_root[s2] == s2) units_at[ulevel[s2]].push_back(s2);
+  for (int s2 = 0; s2 < ns; ++s2) if (unit_root[s2] == s2 && s2 != N.schur_sn) units_at[ulevel[s2]].push_back(s2);
   {
     // the latest level boundary that still has >= 30 % of the factorisation's flops above it (the root of S-metric: 81 %)
     std::vector<double> lev_flops(nulev, 0.0);
     double tot = 0.0;
     for (int s2 = 0; s2 < ns; ++s2) {
+      if (s2 == N.schur_sn) continue;
       const double f = (double)(S.row_ptr[s2 + 1] - S.row_ptr[s2]), k = (double)(S.sn_col0[s2 + 1] - S.sn_col0[s2]);
       const double fl = k * f * f - k * k * f + k * k * k / 3.0;
       lev_flops[ulevel[unit_root[s2]]] += fl;
@@ -1276,6 +1281,7 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
     for (int s2 = 0; s2 < ns; ++s2) {
       if (unit_root[s2] != s2 || S.sn_parent[s2] < 0) continue;
       const int up = unit_root[S.sn_parent[s2]];
+      if (up == N.schur_sn) continue;      // the Schur front is in no sweep: its children's tasks wait for nobody
       if (ulevel[up] < N.flow_levels && (!parted || S.sn_owner[up] == S.sn_owner[s2])) unit_parent[s2] = up;     // a parent in the top schedule of a partitioned plan is not part of the launch
     }
     if (!(e = upload(N, unit_parent, &d.unit_parent)).empty()) return e;
@@ -1311,7 +1317,7 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
       if (f == k) continue;
       const int p2 = S.sn_parent[s2];
       born[epoch_of(s2)].push_back(s2);
-      dies[p2 >= 0 ? epoch_of(p2) : nep - 1].push_back(s2);
+      dies[p2 >= 0 && p2 != N.schur_sn ? epoch_of(p2) : nep - 1].push_back(s2);      // (the Schur front is assembled behind every epoch)
     }
     // free list: offset -> size, coalesced; best fit
     std::map<int64_t, int64_t> freeb;
@@ -1364,6 +1370,8 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
   if (!(e = upload(N, fpos, &d.front_pos)).empty()) return e;
   if (!(e = upload(N, cbshift, &d.cb_shift)).empty()) return e;
   for (int s2 = 0; s2 < ns; ++s2) if (wpos[s2] >= 0 && wparity[s2]) wpos[s2] += wregion[0];
+  // the Schur front is a big front for the assembly (extend-add lists, A-entry ranges below); it owns no W
+  if (N.schur_sn >= 0) wpos[N.schur_sn] = 0;
   const int64_t wtotal = wregion[0] + wregion[1];
   if (!(e = upload(N, wpos, &d.wbuf_pos)).empty()) return e;
   N.sched_host = sched;
@@ -1401,6 +1409,7 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
         const int64_t k = S.sn_col0[s + 1] - S.sn_col0[s];
         bigcol_base[s] = nbigcols;
         nbigcols += f;
+        if (s == N.schur_sn) continue;      // no diagonal-block inverses: the front is not factored
         invl_pos[s] = invl_total;
         invl_total += ((k + N.nb - 1) / N.nb) * (int64_t)N.nb * N.nb;
       }
@@ -1475,6 +1484,10 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
     }
     if (!(e = upload(N, cutv, &d.cutv)).empty()) return e;
     if (!(e = upload(N, acol_lo, &d.acol_lo)).empty()) return e;
+    if (N.schur_sn >= 0) {
+      N.schur_gcb = bigcol_base[N.schur_sn];
+      if (!(e = upload(N, std::vector<int>{N.schur_sn}, &N.schur_list)).empty()) return e;
+    }
     // zero-filled once: the parts of a block beyond a front's last pivot column are never written and are read as zeros
     if (!(e = dalloc(N, (size_t)invl_total, &d.invl, true)).empty()) return e;
   }
@@ -1612,6 +1625,16 @@ std::string numeric_factor_enqueue(Numeric& N, const double* d_vals, double tol,
     e = factor_sched(N, P, which == 0 ? N.levels : N.levels_top, which == 0 ? N.slevels : N.slevels_top, ss, tol,
                      which == 0 && N.levels_top.empty(), inv_on_aux);
     if (!e.empty()) return e;
+  }
+  if (which == 0 && N.schur_sn >= 0) {
+    // Schur mode: the Schur front is assembled -- A22 plus the extend-add of its children's contribution blocks -- and not factored:
+    // the assembled front is S = A22 - A21 A11^-1 A12 (lower triangle).  The big-front assembly kernels, one front.
+    const int f = N.sn_f[N.schur_sn];
+    if (f > 2048) hipLaunchKernelGGL(k_big_assemble_chunked, dim3((f + 3) / 4, 1, (f + kAsmChunk - 1) / kAsmChunk), dim3(256), 0, st, P, N.schur_list);
+    else {
+      const int lcol = std::max(256, (f + 63) / 64 * 64);
+      hipLaunchKernelGGL(k_big_assemble<true>, dim3((f + 3) / 4, 1), dim3(256), (size_t)4 * lcol * sizeof(double), st, P, N.schur_list, lcol);
+    }
   }
   const bool per_level = which == 0 && N.levels_top.empty() && !N.inv_level_pending.empty();
   if (inv_on_aux && !per_level) {    // the next solve waits for the block inversions that are still running on the auxiliary stream

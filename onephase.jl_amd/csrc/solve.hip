@@ -1337,6 +1337,56 @@ __global__ __launch_bounds__(kMidThreads) void k_bwd_mid(DevPlan P, const int* _
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Schur mode: the Schur front is never factored -- the solves stop at it and start from it
+// ------------------------------------------------------------------------------------------------------------------
+// condense: r2 = the Schur front's forward right-hand side (b2 plus its children's contribution vectors, gathered as the forward
+// kernels gather a front before eliminating it), Schur-set order, nr of R right-hand sides (r2 is ns x nr)
+template <int R>
+__global__ __launch_bounds__(256) void k_schur_gather(DevPlan P, int64_t gcb, int col0, int ns, int nr, double* __restrict__ r2) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= ns) return;
+  double w[R];
+  fwd_gather<R>(P, gcb, col0, ns, r, w);
+#pragma unroll
+  for (int q = 0; q < R; ++q) if (q < nr) r2[(size_t)q * ns + r] = w[q];
+}
+// expand: x2 (ns x nr) into the Schur columns of xwork, where the backward sweep reads the ancestors' solution (zeros for the padding)
+template <int R>
+__global__ __launch_bounds__(256) void k_schur_put(DevPlan P, int col0, int ns, int nr, const double* __restrict__ x2) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= ns) return;
+#pragma unroll
+  for (int q = 0; q < R; ++q) P.xwork[(size_t)q * P.xw_stride + col0 + r] = q < nr ? x2[(size_t)q * ns + r] : 0.0;
+}
+// S = the assembled front (column-major, leading dimension ns, lower triangle valid) -> full symmetric, leading dimension ld.  One
+// workgroup per 64 x 64 tile (ti, tj) of the lower triangle: the tile is read once, written in place and, through LDS, transposed
+// into (tj, ti) -- every read and write is a 64-lane column segment.
+__global__ __launch_bounds__(256) void k_schur_export(const double* __restrict__ F, int ns, double* __restrict__ S, int64_t ld) {
+  __shared__ double t[64][65];
+  const int64_t b = blockIdx.x;
+  int ti = (int)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
+  while ((int64_t)ti * (ti + 1) / 2 > b) --ti;
+  while ((int64_t)(ti + 1) * (ti + 2) / 2 <= b) ++ti;
+  const int tj = (int)(b - (int64_t)ti * (ti + 1) / 2);
+  const int i0 = ti * 64, j0 = tj * 64;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int c = wv; c < 64; c += 4) {
+    const int i = i0 + lane, j = j0 + c;
+    t[lane][c] = (i < ns && j < ns && i >= j) ? F[(size_t)j * ns + i] : 0.0;
+  }
+  __syncthreads();
+  for (int c = wv; c < 64; c += 4) {
+    const int i = i0 + lane, j = j0 + c;
+    if (i < ns && j < ns) S[(size_t)j * ld + i] = (ti != tj || lane >= c) ? t[lane][c] : t[c][lane];
+  }
+  if (ti == tj) return;
+  for (int c = wv; c < 64; c += 4) {
+    const int i = j0 + lane, j = i0 + c;
+    if (i < ns && j < ns) S[(size_t)j * ld + i] = t[c][lane];
+  }
+}
+
 template <int R>
 __global__ void k_permute_in_r(int n, int nr, int64_t stride_in, const int* __restrict__ perm, const double* __restrict__ rhs, double* __restrict__ x, int64_t xs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1654,6 +1704,36 @@ std::string solve_fwd_enqueue(Numeric& N, int which, int R) {
 }
 std::string solve_bwd_enqueue(Numeric& N, int which, int R) {
   return sweep_which(N, false, which, R);
+}
+
+std::string schur_condense_enqueue(Numeric& N, double* d_r2, int nr, int R) {
+  std::string e = solve_fwd_enqueue(N, 0, R);
+  if (!e.empty()) return e;
+  const int ns = N.sn_k[N.schur_sn], col0 = N.d.n - ns;
+  const dim3 g((ns + 255) / 256), b(256);
+  if (R == 1) hipLaunchKernelGGL(k_schur_gather<1>, g, b, 0, N.stream, N.d, N.schur_gcb, col0, ns, nr, d_r2);
+  else if (R == 2) hipLaunchKernelGGL(k_schur_gather<2>, g, b, 0, N.stream, N.d, N.schur_gcb, col0, ns, nr, d_r2);
+  else hipLaunchKernelGGL(k_schur_gather<4>, g, b, 0, N.stream, N.d, N.schur_gcb, col0, ns, nr, d_r2);
+  OKKT_HIP_TRY(hipGetLastError());
+  return "";
+}
+
+std::string schur_expand_enqueue(Numeric& N, const double* d_x2, int nr, int R) {
+  std::string e = solve_fwd_enqueue(N, 0, R);
+  if (!e.empty()) return e;
+  const int ns = N.sn_k[N.schur_sn], col0 = N.d.n - ns;
+  const dim3 g((ns + 255) / 256), b(256);
+  if (R == 1) hipLaunchKernelGGL(k_schur_put<1>, g, b, 0, N.stream, N.d, col0, ns, nr, d_x2);
+  else if (R == 2) hipLaunchKernelGGL(k_schur_put<2>, g, b, 0, N.stream, N.d, col0, ns, nr, d_x2);
+  else hipLaunchKernelGGL(k_schur_put<4>, g, b, 0, N.stream, N.d, col0, ns, nr, d_x2);
+  OKKT_HIP_TRY(hipGetLastError());
+  return solve_bwd_enqueue(N, 0, R);
+}
+
+void schur_export_enqueue(Numeric& N, double* d_S, int64_t ld) {
+  const int ns = N.sn_k[N.schur_sn];
+  const int64_t T = (ns + 63) / 64;
+  hipLaunchKernelGGL(k_schur_export, dim3((unsigned)(T * (T + 1) / 2)), dim3(256), 0, N.stream, N.d.arena + N.front_pos_host[N.schur_sn], ns, d_S, ld);
 }
 
 void solve_permute_in(const Numeric& N, const double* d_rhs, int64_t stride, int nr, int R) {

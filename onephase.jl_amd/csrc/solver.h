@@ -31,6 +31,7 @@ struct okkt_solver_s {
   hipStream_t stream_aux = nullptr;    // second panel stream: the part of the in-group updates that k_big_diag does not wait for
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<int64_t> user_perm;
+  std::vector<int64_t> schur_idx;   // Schur set (okkt_set_schur); empty: not in Schur mode
   std::vector<int64_t> pat_colptr, pat_rowval;   // the analysed pattern as the caller passed it (exact re-use test in okkt_analyze)
   std::string err;
   double analyze_seconds = 0, last_factor_ms = 0, last_solve_ms = 0;
@@ -72,6 +73,12 @@ int solver_solve_device(okkt_solver_s* h, const double* d_rhs, double* d_sol, in
 // accumulate: d_sol += F \ d_rhs
 int solver_solve_enqueue(okkt_solver_s* h, const double* d_rhs, double* d_sol, int64_t nrhs, bool accumulate);
 int solver_set_error(okkt_solver_s* h, int code, const std::string& msg);
+// Schur mode (okkt_set_schur): the calls that need a factor of the whole of A refuse with OKKT_ERR_INVALID
+inline bool schur_mode(const okkt_solver_s* h) { return !h->schur_idx.empty(); }
+inline int schur_refuse(okkt_solver_s* h, const char* what) {
+  return solver_set_error(h, OKKT_ERR_INVALID, std::string(what) + " needs a factor of the whole matrix: the handle is in Schur mode (okkt_set_schur; "
+                                                   "use okkt_factor_schur / okkt_schur_condense / okkt_schur_expand, or clear the set with ns = 0)");
+}
 int solver_ensure_numeric(okkt_solver_s* h);
 // refinement driver (api.cpp): x = F \ b, then corrections from the double-double residual against d_nzval until omega <= tol,
 // stagnation, a non-finite value or max_steps.  d_rhs, d_sol: nrhs x n on the device (they may alias).  lap(tag), if given, is called at

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <chrono>
 #include <algorithm>
+#include <climits>
 #include <atomic>
 #include <functional>
 #include <cstring>
@@ -73,7 +74,7 @@ static std::string analyze_one(int64_t n64, const int64_t* colptr, const int64_t
                                int index_base, const SymbolicOptions& opts,
                                const int64_t* user_perm, Symbolic& S,
                                const std::vector<int>* forced_order = nullptr, bool stats_only = false,
-                               const std::atomic<bool>* cancel = nullptr) {
+                               const std::atomic<bool>* cancel = nullptr, int nschur = 0) {
   if (n64 < 0 || n64 > 0x7ffffff0) return "matrix order out of range";
   if (index_base != 0 && index_base != 1) return "index_base must be 0 or 1";
   const int n = (int)n64;
@@ -306,6 +307,10 @@ static std::string analyze_one(int64_t n64, const int64_t* colptr, const int64_t
     if (!perr.empty()) return perr;
     column_counts(parent0, post1, cp, ci, count0);
   }
+  // Schur mode: the last nschur positions of the order are the Schur set, taken as dense -- a chain in the tree with the counts of a
+  // full lower triangle.  The interior columns keep their parents and counts (their structure does not depend on the S block).
+  const int n1 = n - nschur;
+  for (int p = n1; p < n; ++p) { parent0[p] = p + 1 < n ? p + 1 : -1; count0[p] = n - p; }
 
   lap("etree + colcounts");
   // ---- postorder, heaviest child last (it is the amalgamation candidate of its parent)
@@ -318,15 +323,17 @@ static std::string analyze_one(int64_t n64, const int64_t* colptr, const int64_t
     std::vector<int> ch(chp[n]);
     std::vector<int64_t> fill(chp.begin(), chp.end() - 1);
     for (int j = 0; j < n; ++j) if (parent0[j] >= 0) ch[fill[parent0[j]]++] = j;
+    // (Schur mode: the Schur chain is visited last everywhere, so that it stays the tail of the postorder)
+    auto key = [&](int a) { return a >= n1 ? INT_MAX : count0[a]; };
     for (int j = 0; j < n; ++j)
       std::stable_sort(ch.begin() + chp[j], ch.begin() + chp[j + 1],
-                       [&](int a, int b) { return count0[a] < count0[b]; });
+                       [&](int a, int b) { return key(a) < key(b); });
     std::vector<int> stack;
     std::vector<int64_t> next_child(n);
     for (int j = 0; j < n; ++j) next_child[j] = chp[j];
     std::vector<int> roots;
     for (int j = 0; j < n; ++j) if (parent0[j] < 0) roots.push_back(j);
-    std::stable_sort(roots.begin(), roots.end(), [&](int a, int b) { return count0[a] < count0[b]; });
+    std::stable_sort(roots.begin(), roots.end(), [&](int a, int b) { return key(a) < key(b); });
     for (int r : roots) {
       stack.push_back(r);
       while (!stack.empty()) {
@@ -339,6 +346,9 @@ static std::string analyze_one(int64_t n64, const int64_t* colptr, const int64_t
   S.perm.resize(n);
   S.iperm.resize(n);
   for (int k = 0; k < n; ++k) { S.perm[k] = order[post[k]]; S.iperm[S.perm[k]] = k; }
+  for (int k = n1; k < n; ++k)
+    if (post[k] != k) return "internal error: the Schur set is not the tail of the postorder";
+  S.nschur = nschur;
   // The postorder is a relabelling along the tree: the elimination tree and the column counts of the renumbered matrix are the
   // relabelled ones (no second pass over the pattern for them); only the column lists are built again, in the new numbering.
   {
@@ -375,7 +385,7 @@ static std::string analyze_one(int64_t n64, const int64_t* colptr, const int64_t
   std::vector<int> col0;  // first column of each supernode
   col0.reserve(n + 1);
   for (int j = 0; j < n; ++j) {
-    bool join = j > 0 && parent[j - 1] == j && cc[j - 1] == cc[j] + 1;
+    bool join = j > 0 && parent[j - 1] == j && cc[j - 1] == cc[j] + 1 && !(nschur > 0 && j == n1);
     if (!join) col0.push_back(j);
   }
   col0.push_back(n);
@@ -395,6 +405,7 @@ static std::string analyze_one(int64_t n64, const int64_t* colptr, const int64_t
       int last = col0[s + 1] - 1;
       if (parent[last] != last + 1) continue;  // parent supernode is not the next one
       int p = s + 1;
+      if (nschur > 0 && p == ns - 1) continue;   // nothing is amalgamated into the Schur supernode
       int64_t kc = width[s], kp = width[p];
       int64_t fp = cc[col0[p]];  // front order of the parent: count of its first column
       int64_t fm = kc + fp, km = kc + kp;
@@ -663,7 +674,60 @@ static std::string analyze_one(int64_t n64, const int64_t* colptr, const int64_t
 //    fill stays small in absolute terms (such systems carry a few MFLOP; the chain length, not the flop count, is their cost).
 std::string analyze_pattern(int64_t n64, const int64_t* colptr, const int64_t* rowval,
                             int index_base, const SymbolicOptions& opts,
-                            const int64_t* user_perm, Symbolic& S) {
+                            const int64_t* user_perm, Symbolic& S, const int64_t* schur_idx, int64_t nschur) {
+  if (nschur > 0) {
+    // Schur mode: the interior's order comes from the plain analysis of A11 (every ordering rule, the automatic choice included,
+    // applied to that pattern), the set is appended in the caller's order, and the plan is built once more on the whole pattern
+    if (n64 < 0 || n64 > 0x7ffffff0) return "matrix order out of range";
+    if (nschur >= n64) return "the Schur set must leave at least one interior variable";
+    const int n = (int)n64, ns = (int)nschur, n1 = n - ns;
+    std::vector<int> pos(n, -1);        // original index -> position in the Schur set
+    for (int t = 0; t < ns; ++t) {
+      const int64_t v = schur_idx[t];
+      if (v < 0 || v >= n64 || pos[v] >= 0) return "the Schur set holds an index out of range or twice";
+      pos[v] = t;
+    }
+    std::vector<int> order;
+    order.reserve(n);
+    Symbolic S1;
+    if (opts.ordering == 2) {
+      if (!user_perm) return "ordering=user but no permutation was supplied";
+      for (int t = 0; t < ns; ++t)
+        if (user_perm[n1 + t] != schur_idx[t]) return "ordering=user in Schur mode: the permutation must end with the Schur set in its order";
+      for (int k = 0; k < n; ++k) {
+        if (user_perm[k] < 0 || user_perm[k] >= n64) return "user permutation is not a permutation of 0..n-1";
+        order.push_back((int)user_perm[k]);
+      }
+    } else {
+      std::vector<int> inner;      // interior index -> original index
+      std::vector<int64_t> loc(n, -1);
+      for (int i = 0; i < n; ++i) if (pos[i] < 0) { loc[i] = (int64_t)inner.size(); inner.push_back(i); }
+      std::vector<int64_t> cp1(n1 + 1, index_base), ri1;
+      ri1.reserve((size_t)(colptr[n] - colptr[0]));
+      for (int j = 0; j < n; ++j) {
+        if (pos[j] >= 0) continue;
+        for (int64_t p = colptr[j] - index_base; p < colptr[j + 1] - index_base; ++p) {
+          const int64_t i = rowval[p] - index_base;
+          if (i < 0 || i >= n64) return "row index out of range";
+          if (pos[i] < 0) ri1.push_back(loc[i] + index_base);
+        }
+        cp1[loc[j] + 1] = index_base + (int64_t)ri1.size();
+      }
+      std::string e = analyze_pattern(n1, cp1.data(), ri1.data(), index_base, opts, nullptr, S1);
+      if (!e.empty()) return e;
+      for (int k = 0; k < n1; ++k) order.push_back(inner[S1.perm[k]]);
+      for (int t = 0; t < ns; ++t) order.push_back((int)schur_idx[t]);
+    }
+    std::string e = analyze_one(n64, colptr, rowval, index_base, opts, user_perm, S, &order, false, nullptr, ns);
+    if (!e.empty()) return e;
+    if (opts.ordering != 2) {
+      S.ordering_used = S1.ordering_used;
+      S.top_separator = S1.top_separator;
+      S.amd_skipped = S1.amd_skipped;
+      S.flops_other = S1.flops_other;
+    }
+    return "";
+  }
   const bool dbg = getenv("OKKT_DEBUG_ANALYZE") != nullptr;
   const int64_t mlnd_min_n = getenv("OKKT_MLND_MIN_N") ? atoll(getenv("OKKT_MLND_MIN_N")) : 10000;
   if (opts.ordering == 0 && n64 >= mlnd_min_n && n64 <= 0x7ffffff0) {

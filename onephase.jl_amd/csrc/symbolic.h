@@ -106,6 +106,9 @@ struct Symbolic {
   int max_front = 0;
   int ordering_used = 0;     // 0 = AMD, 1 = natural, 2 = user, 4 = level-structure nested dissection
   int64_t critical_pivots = 0;   // pivots on the longest leaf-to-root path of the supernodal tree (n for a path)
+  // Schur mode (okkt_set_schur): the last nschur columns are the Schur set in the caller's order, held as ONE final supernode
+  // (k = f = nschur, no relaxation into it) that the numeric factorisation assembles and does not factor.  0: off
+  int64_t nschur = 0;
   uint64_t pattern_hash = 0;
 
   // subtree-to-GPU partition (multi-GPU row of SURVEY 8e): owner part of every supernode, -1 = "top"
@@ -126,10 +129,13 @@ void partition_tree(Symbolic& S, int nparts);
 
 // colptr/rowval: CSC of a square matrix in either index base; only row >= col is used.
 // user_perm (size n, perm[new]=old, 0-based) is read when opts.ordering == 2.
+// schur_idx (nschur distinct 0-based indices, 0 < nschur < n): Schur mode -- the interior is ordered by opts on the pattern of A
+// without those rows and columns, the set follows in the given order as one supernode; a user permutation must end with it.
 // Returns "" on success, otherwise an error message.
 std::string analyze_pattern(int64_t n, const int64_t* colptr, const int64_t* rowval,
                             int index_base, const SymbolicOptions& opts,
-                            const int64_t* user_perm, Symbolic& S);
+                            const int64_t* user_perm, Symbolic& S,
+                            const int64_t* schur_idx = nullptr, int64_t nschur = 0);
 
 uint64_t hash_pattern(int64_t n, const int64_t* colptr, const int64_t* rowval);
 

@@ -67,6 +67,7 @@ class linear_solver_HIP(abstract_linear_system_solver):
         self._lib = None
         self.inertia = None  # (pos, neg, zero, nonfinite) of the last factorisation
         self._dim = 0
+        self._ns = 0  # Schur set size (set_schur)
 
     # -- initialize! / finalize!
     def _initialize(self):
@@ -339,3 +340,69 @@ class linear_solver_HIP(abstract_linear_system_solver):
         self._check(self._lib.okkt_forward_error(self._h, L.p_f64(vals), L.p_f64(B), L.p_f64(Xv), B.shape[0], L.p_f64(ferr), L.p_f64(berr)),
                     "okkt_forward_error")
         return (ferr[0], berr[0]) if single else (ferr, berr)
+
+    # -- Schur mode: partial factorisation with a dense Schur complement (not part of the reference interface)
+    def set_schur(self, idx):
+        """Hold the variables idx (0-based, distinct) back: the next analyze() orders the rest and puts them last as one front that
+        ls_factor_schur assembles into S = A22 - A21 A11^-1 A12 and does not factor.  An empty idx clears the set."""
+        self._need()
+        p = L.i64(np.asarray(idx, dtype=np.int64).ravel())
+        self._check(self._lib.okkt_set_schur(self._h, len(p), L.p_i64(p) if len(p) else None), "okkt_set_schur")
+        self._ns = len(p)
+
+    def _kind(self):
+        return L.OKKT_SYM_DEFINITE if self.sym == "definite" else L.OKKT_SYM_SYMMETRIC
+
+    def ls_factor_schur(self, nzval_or_matrix, n1, m1):
+        """Factor A11 (n1 + m1 = dim - ns) and assemble S; 1 / 0 under the contract of ls_factor_b applied to A11.  The values in
+        the analysed order, or the matrix itself with the analysed pattern."""
+        self._need()
+        vals = self._values(nzval_or_matrix)
+        inert = L.OkktInertia()
+        rc = self._check(self._lib.okkt_factor_schur(self._h, L.p_f64(vals), n1, m1, self._kind(), C.byref(inert)), "okkt_factor_schur")
+        self.inertia = inert.as_tuple()
+        return int(rc)
+
+    def ls_factor_schur_dev(self, d_nzval, n1, m1):
+        self._need()
+        inert = L.OkktInertia()
+        rc = self._check(self._lib.okkt_factor_schur_dev(self._h, C.c_void_p(d_nzval), n1, m1, self._kind(), C.byref(inert)), "okkt_factor_schur_dev")
+        self.inertia = inert.as_tuple()
+        return int(rc)
+
+    def schur(self):
+        """S as a dense symmetric ns x ns NumPy array, rows and columns in the order of the set."""
+        self._need()
+        ns = self._ns
+        S = np.zeros((ns, ns))
+        self._check(self._lib.okkt_get_schur(self._h, L.p_f64(S), ns), "okkt_get_schur")
+        return S      # column-major with ld = ns is the transpose of this C-order array, and S is symmetric
+
+    def schur_dev(self, d_S, ld):
+        self._need()
+        self._check(self._lib.okkt_get_schur_dev(self._h, C.c_void_p(d_S), int(ld)), "okkt_get_schur_dev")
+
+    def schur_condense(self, rhs):
+        """r2 = b2 - A21 A11^-1 b1 (set order); rhs: a vector or one right-hand side per row, original order."""
+        self._need()
+        B, single = self._rhs_block(rhs, self._dim)
+        R2 = np.zeros((B.shape[0], self._ns))
+        self._check(self._lib.okkt_schur_condense(self._h, L.p_f64(B), L.p_f64(R2), B.shape[0]), "okkt_schur_condense")
+        return R2[0] if single else R2
+
+    def schur_condense_dev(self, d_rhs, d_r2, nrhs=1):
+        self._need()
+        self._check(self._lib.okkt_schur_condense_dev(self._h, C.c_void_p(d_rhs), C.c_void_p(d_r2), int(nrhs)), "okkt_schur_condense_dev")
+
+    def schur_expand(self, rhs, x2):
+        """x with x[idx] = x2 and x1 = A11^-1 (b1 - A12 x2); rhs as in schur_condense, x2 one row of ns per right-hand side."""
+        self._need()
+        B, single = self._rhs_block(rhs, self._dim)
+        X2 = L.f64(np.asarray(x2, dtype=np.float64).reshape(B.shape[0], self._ns))
+        X = np.zeros_like(B)
+        self._check(self._lib.okkt_schur_expand(self._h, L.p_f64(B), L.p_f64(X2), L.p_f64(X), B.shape[0]), "okkt_schur_expand")
+        return X[0] if single else X
+
+    def schur_expand_dev(self, d_rhs, d_x2, d_x, nrhs=1):
+        self._need()
+        self._check(self._lib.okkt_schur_expand_dev(self._h, C.c_void_p(d_rhs), C.c_void_p(d_x2), C.c_void_p(d_x), int(nrhs)), "okkt_schur_expand_dev")
