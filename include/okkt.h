@@ -246,6 +246,41 @@ int okkt_schur_condense_dev(okkt_handle h, const double* d_rhs, double* d_r2, in
  * condense call.  rhs may alias x. */
 int okkt_schur_expand(okkt_handle h, const double* rhs, const double* x2, double* x, int64_t nrhs);
 int okkt_schur_expand_dev(okkt_handle h, const double* d_rhs, const double* d_x2, double* d_x, int64_t nrhs);
+/* ---- Selected inversion: entries of F^-1 on the pattern of the factor ----------------------------------
+ * F is the matrix the handle factored (as for okkt_condest: the values plus the factorisation's diagonal shift).  okkt_selinv computes
+ * Z = F^-1 = L^-T D^-1 L^-1 at every entry of the stored supernodal pattern of L (relaxation zeros included) and at the diagonal, on
+ * the device, and keeps it there; the exports below read it.  Deterministic: no floating-point atomics and fixed summation orders, so
+ * two calls on one factor give bitwise-identical Z.  Z belongs to the factorisation it was computed from: the next okkt_factor* makes
+ * it stale, and the exports then return OKKT_ERR_INVALID until okkt_selinv runs again.  The device memory (the Z panels and a scratch
+ * region reused level by level) is allocated by the first call after an analysis and released with the analysis.
+ * Refused with OKKT_ERR_INVALID (the handle stays usable): before a factorisation, after an early-exit factorisation that stopped
+ * short, on a handle in Schur mode and on partitioned handles; host_symbolic_only handles get OKKT_ERR_NO_DEVICE.  A factorisation
+ * whose flag was 0 is accepted: non-finite entries of Z (an exact zero pivot) are counted in info.nonfinite and status is 1.
+ * No existing call changes: okkt_solve after okkt_selinv is bitwise what it was before. */
+typedef struct {
+  double seconds_device;   /* the device time of the computation (HIP events around it) */
+  int64_t arena_bytes;     /* device memory held for Z: the Z panels, the scratch region and the plan's index arrays */
+  int64_t nonfinite;       /* non-finite entries of Z on the stored pattern */
+  int32_t status;          /* 0 every entry finite, 1 some entry non-finite */
+  double flops;            /* floating-point operations of the block products (2 m^2 w + 2 m w^2 per block of w columns, m rows below) */
+} okkt_selinv_info;
+int okkt_selinv(okkt_handle h, okkt_selinv_info* info /* or NULL */);
+/* diag(F^-1) in the original order (d_out: dim doubles, host / device memory) */
+int okkt_get_inverse_diag(okkt_handle h, double* d_out);
+int okkt_get_inverse_diag_dev(okkt_handle h, double* d_out);
+/* (F^-1)_ij at every entry (i, j) of the analysed input pattern, in nzval layout (nnz of the analysed colptr / rowval).  Every entry
+ * takes the value at its position mirrored into the lower triangle of the permuted matrix: a lower-triangle entry always lies on
+ * the pattern of L; an upper-triangle entry (ignored at analysis) gets the value of its mirrored entry when that position is on the
+ * pattern of L, NaN otherwise.  Duplicate entries get the same value at every copy.  *nnz (if given) receives the count; a NULL zval
+ * asks for the count only. */
+int okkt_get_inverse_on_pattern(okkt_handle h, double* zval, int64_t* nnz);
+int okkt_get_inverse_on_pattern_dev(okkt_handle h, double* d_zval);
+/* the lower triangle of F^-1 in the permuted numbering as 0-based CSC: the pattern of okkt_get_factor_csc plus the diagonal, each
+ * column's rows ascending (diagonal first); nnz = that of okkt_get_factor_csc + dim.  NULL arrays: *nnz only. */
+int okkt_get_inverse_csc(okkt_handle h, int64_t* colptr, int64_t* rowval, double* val, int64_t* nnz);
+/* log |det F| and its sign from D, summed in pivot order on the host (deterministic); sign 0 and -Inf when a pivot is 0.  Needs a
+ * complete factorisation (not okkt_selinv); same refusals otherwise. */
+int okkt_logdet(okkt_handle h, double* logabsdet, int32_t* sign);
 
 /* diag(F): the D of LDL^T in pivot (permuted) order, as `diag(solver._factor)` (julia.jl:72) */
 int okkt_get_diag(okkt_handle h, double* d_out /* [dim] */);

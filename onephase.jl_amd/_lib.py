@@ -159,6 +159,20 @@ class OkktCondestInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktSelinvInfo(C.Structure):
+    """okkt_selinv_info: device seconds, bytes held for Z, non-finite entries of Z (status 1 when there are any)."""
+    _fields_ = [
+        ("seconds_device", C.c_double),
+        ("arena_bytes", C.c_int64),
+        ("nonfinite", C.c_int64),
+        ("status", C.c_int32),
+        ("flops", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/okkt.h declares, with its signature
 _i64p = C.POINTER(C.c_int64)
 _f64p = C.POINTER(C.c_double)
@@ -197,6 +211,13 @@ SIGNATURES = {
     "okkt_schur_condense_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64]),
     "okkt_schur_expand": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64]),
     "okkt_schur_expand_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64]),
+    "okkt_selinv": (C.c_int, [_vp, C.POINTER(OkktSelinvInfo)]),
+    "okkt_get_inverse_diag": (C.c_int, [_vp, _f64p]),
+    "okkt_get_inverse_diag_dev": (C.c_int, [_vp, _vp]),
+    "okkt_get_inverse_on_pattern": (C.c_int, [_vp, _f64p, _i64p]),
+    "okkt_get_inverse_on_pattern_dev": (C.c_int, [_vp, _vp]),
+    "okkt_get_inverse_csc": (C.c_int, [_vp, _i64p, _i64p, _f64p, _i64p]),
+    "okkt_logdet": (C.c_int, [_vp, _f64p, C.POINTER(C.c_int32)]),
     "okkt_get_diag": (C.c_int, [_vp, _f64p]),
     "okkt_get_factor_csc": (C.c_int, [_vp, _i64p, _i64p, _f64p, _i64p]),
     "okkt_dev_alloc": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp)]),

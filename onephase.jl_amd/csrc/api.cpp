@@ -64,6 +64,7 @@ int solver_factor_device(okkt_solver_s* h, const double* d_vals, int64_t n, int6
   if (sym_kind == OKKT_SYM_DEFINITE && m != 0) return solver_set_error(h, OKKT_ERR_INVALID, ":definite requires m == 0 (julia.jl:30)");
   const double tol = (sym_kind == OKKT_SYM_DEFINITE || zero_tol) ? 0.0 : h->opts.inertia_tol;
   h->factored = false;
+  ++h->factor_seq;     // a selected inverse of the previous factor is stale from here on
   h->N.early_check = h->early_exit && h->S.nschur == 0;
   h->N.early_device = h->early_exit && h->last_failed;   // the previous factorisation failed the inertia: this one is a retry
   h->N.early_n = n;
@@ -129,6 +130,7 @@ int solver_solve_device(okkt_solver_s* h, const double* d_rhs, double* d_sol, in
 void solver_refine_release(okkt_solver_s* h) {
   refine_map_release(h->rf);
   condest_release(h->cd);
+  selinv_release(h->sl);
   h->cd_hist.clear();
   if (h->rf_work) (void)hipFree(h->rf_work);
   if (h->rf_om) (void)hipFree(h->rf_om);
@@ -778,7 +780,7 @@ int okkt_analyze(okkt_handle h, int64_t dim, const int64_t* colptr, const int64_
     if (h->opts.ordering == 2 && (int64_t)h->user_perm.size() != dim)
       return solver_set_error(h, OKKT_ERR_INVALID, "ordering=user: okkt_set_perm must supply dim entries first");
     auto t0 = std::chrono::steady_clock::now();
-    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X)) {   // the refinement map belongs to the old pattern
+    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned)) {   // the refinement map (and Z) belong to the old pattern
       (void)hipSetDevice(h->device);
       (void)hipStreamSynchronize(h->stream);
       solver_refine_release(h);
@@ -1426,6 +1428,197 @@ int okkt_schur_expand(okkt_handle h, const double* rhs, const double* x2, double
     return OKKT_OK;
   } catch (...) {
     return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_expand");
+  }
+}
+
+// ---- selected inversion (selinv.hip) --------------------------------------------------------------------
+
+// device, analysis, no partition, not Schur mode, a complete factorisation; need_z: a Z computed from that factorisation
+static int selinv_ready(okkt_solver_s* h, bool need_z) {
+  int rc = ensure_device(h);
+  if (rc != OKKT_OK) return rc;
+  if (schur_mode(h)) return schur_refuse(h, "selected inversion");
+  if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_analyze has not been called");
+  if (h->S.nparts > 1)
+    return solver_set_error(h, OKKT_ERR_INVALID, "selected inversion is not available on a partitioned handle (okkt_dist_set_partition with nparts > 1)");
+  if ((rc = solver_ensure_numeric(h)) != OKKT_OK) return rc;
+  if (!h->factored)
+    return solver_set_error(h, OKKT_ERR_INVALID, "selected inversion needs a complete factorisation (none yet, or an early exit stopped it)");
+  if (need_z && (!h->sl.planned || h->sl.factor_seq != h->factor_seq))
+    return solver_set_error(h, OKKT_ERR_INVALID, "no selected inverse of the current factorisation: call okkt_selinv after okkt_factor");
+  return OKKT_OK;
+}
+
+static int selinv_sync(okkt_solver_s* h, const char* what) {
+  hipError_t he = hipGetLastError();
+  if (he == hipSuccess) he = hipStreamSynchronize(h->stream);
+  if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string(what) + " failed: " + hipGetErrorString(he));
+  return OKKT_OK;
+}
+
+int okkt_selinv(okkt_handle h, okkt_selinv_info* info) {
+  if (!h) return OKKT_ERR_INVALID;
+  try {
+    int rc = selinv_ready(h, false);
+    if (rc != OKKT_OK) return rc;
+    SelinvWork& W = h->sl;
+    if (!W.planned || W.analysis != h->n_analyze_calls || W.arena != h->N.d.arena) {
+      (void)hipStreamSynchronize(h->stream);
+      std::string e = selinv_setup(h->S, h->N, h->pat_colptr.data(), h->pat_rowval.data(), W);
+      if (!e.empty()) { selinv_release(W); return solver_set_error(h, OKKT_ERR_ALLOC, "selected inversion set-up: " + e); }
+      W.analysis = h->n_analyze_calls;
+      W.arena = h->N.d.arena;
+    }
+    W.factor_seq = -1;
+    (void)hipEventRecord(h->ev0, h->stream);
+    std::string e = selinv_enqueue(h->N, W);
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
+    (void)hipEventRecord(h->ev1, h->stream);
+    unsigned long long nf = 0;
+    hipError_t he = hipMemcpyAsync(&nf, W.count, sizeof(nf), hipMemcpyDeviceToHost, h->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(h->stream);
+    if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("selected inversion failed: ") + hipGetErrorString(he));
+    W.factor_seq = h->factor_seq;
+    if (info) {
+      float ms = 0;
+      info->seconds_device = hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess ? ms * 1e-3 : 0.0;
+      info->arena_bytes = W.bytes;
+      info->nonfinite = (int64_t)nf;
+      info->status = nf ? 1 : 0;
+      info->flops = W.flops;
+    }
+    return OKKT_OK;
+  } catch (const std::bad_alloc&) {
+    return solver_set_error(h, OKKT_ERR_ALLOC, "out of host memory in okkt_selinv");
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_selinv");
+  }
+}
+
+int okkt_get_inverse_diag_dev(okkt_handle h, double* d_out) {
+  if (!h || !d_out) return OKKT_ERR_INVALID;
+  try {
+    int rc = selinv_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    selinv_diag_enqueue(h->N, h->sl, h->S.n, d_out, h->stream);
+    return selinv_sync(h, "inverse diagonal export");
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_get_inverse_diag_dev");
+  }
+}
+
+int okkt_get_inverse_diag(okkt_handle h, double* d_out) {
+  if (!h || !d_out) return OKKT_ERR_INVALID;
+  try {
+    int rc = selinv_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    const int64_t n = h->S.n;
+    if (n == 0) return OKKT_OK;
+    if ((rc = rhs_stage(h, n)) != OKKT_OK) return rc;
+    selinv_diag_enqueue(h->N, h->sl, n, h->d_rhs_stage, h->stream);
+    if ((rc = selinv_sync(h, "inverse diagonal export")) != OKKT_OK) return rc;
+    if (hipMemcpy(d_out, h->d_rhs_stage, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "inverse diagonal download failed");
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_get_inverse_diag");
+  }
+}
+
+int okkt_get_inverse_on_pattern_dev(okkt_handle h, double* d_zval) {
+  if (!h || (!d_zval && h->S.nnz_in > 0)) return OKKT_ERR_INVALID;
+  try {
+    int rc = selinv_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    selinv_pattern_enqueue(h->sl, h->S.nnz_in, d_zval, h->stream);
+    return selinv_sync(h, "inverse export on the input pattern");
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_get_inverse_on_pattern_dev");
+  }
+}
+
+int okkt_get_inverse_on_pattern(okkt_handle h, double* zval, int64_t* nnz_out) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "not analysed");
+  if (nnz_out) *nnz_out = h->S.nnz_in;
+  if (!zval) return nnz_out ? OKKT_OK : OKKT_ERR_INVALID;
+  try {
+    int rc = selinv_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    const int64_t nnz = h->S.nnz_in;
+    if (nnz == 0) return OKKT_OK;
+    DevTemp t;
+    if (!t.alloc(nnz)) return solver_set_error(h, OKKT_ERR_ALLOC, "inverse export staging allocation failed");
+    selinv_pattern_enqueue(h->sl, nnz, t.p, h->stream);
+    if ((rc = selinv_sync(h, "inverse export on the input pattern")) != OKKT_OK) return rc;
+    if (hipMemcpy(zval, t.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "inverse export download failed");
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_get_inverse_on_pattern");
+  }
+}
+
+int okkt_get_inverse_csc(okkt_handle h, int64_t* colptr_out, int64_t* rowval_out, double* val_out, int64_t* nnz_out) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "not analysed");
+  const Symbolic& S = h->S;
+  if (nnz_out) *nnz_out = S.nnzL_stored;
+  if (!colptr_out || !rowval_out || !val_out) return OKKT_OK;
+  try {
+    int rc = selinv_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    const SelinvWork& W = h->sl;
+    std::vector<double> z((size_t)W.z_doubles);
+    if ((rc = selinv_sync(h, "inverse export")) != OKKT_OK) return rc;
+    if (W.z_doubles > 0 && hipMemcpy(z.data(), W.Z, (size_t)W.z_doubles * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "download of Z failed");
+    int64_t q = 0;
+    for (int s = 0; s < S.nsuper; ++s) {
+      const int64_t f = S.row_ptr[s + 1] - S.row_ptr[s];
+      const int64_t k = S.sn_col0[s + 1] - S.sn_col0[s];
+      const double* zf = z.data() + W.zpos_host[s];
+      for (int64_t lc = 0; lc < k; ++lc) {
+        colptr_out[S.sn_col0[s] + lc] = q;
+        for (int64_t i = lc; i < f; ++i) {
+          rowval_out[q] = S.rows[S.row_ptr[s] + i];
+          val_out[q] = zf[i + lc * f];
+          ++q;
+        }
+      }
+    }
+    colptr_out[S.n] = q;
+    return OKKT_OK;
+  } catch (const std::bad_alloc&) {
+    return solver_set_error(h, OKKT_ERR_ALLOC, "out of host memory in okkt_get_inverse_csc");
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_get_inverse_csc");
+  }
+}
+
+int okkt_logdet(okkt_handle h, double* logabsdet, int32_t* sign) {
+  if (!h || !logabsdet || !sign) return OKKT_ERR_INVALID;
+  try {
+    int rc = selinv_ready(h, false);
+    if (rc != OKKT_OK) return rc;
+    const int64_t n = h->S.n;
+    std::vector<double> d((size_t)n);
+    if ((rc = selinv_sync(h, "logdet")) != OKKT_OK) return rc;
+    if (n > 0 && hipMemcpy(d.data(), h->N.d.dvals, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "download of D failed");
+    double acc = 0.0;
+    int32_t sg = 1;
+    for (int64_t i = 0; i < n; ++i) {
+      const double v = d[(size_t)i];
+      if (v < 0) sg = -sg;
+      else if (!(v > 0)) sg = 0;   // zero or NaN
+      acc += std::log(std::fabs(v));
+    }
+    *logabsdet = acc;
+    *sign = sg;
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_logdet");
   }
 }
 

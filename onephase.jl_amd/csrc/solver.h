@@ -9,6 +9,7 @@
 #include "condest.h"
 #include "numeric.h"
 #include "refine.h"
+#include "selinv.h"
 #include "symbolic.h"
 
 struct okkt_solver_s {
@@ -60,6 +61,10 @@ struct okkt_solver_s {
   // the refinement map; the unit vectors the last estimate used
   okkt::CondestWork cd;
   std::vector<int64_t> cd_hist;
+  // selected inversion (selinv.hip): its plan and Z, allocated on the first okkt_selinv after an analysis and released with it;
+  // factor_seq counts the factorisations started, so that Z is known stale after the next one
+  okkt::SelinvWork sl;
+  int64_t factor_seq = 0;
 };
 
 namespace okkt {

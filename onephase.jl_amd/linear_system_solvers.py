@@ -68,6 +68,7 @@ class linear_solver_HIP(abstract_linear_system_solver):
         self.inertia = None  # (pos, neg, zero, nonfinite) of the last factorisation
         self._dim = 0
         self._ns = 0  # Schur set size (set_schur)
+        self._borrowed = False  # a view on a handle another object owns (of_kkt): finalize does not destroy it
 
     # -- initialize! / finalize!
     def _initialize(self):
@@ -91,7 +92,8 @@ class linear_solver_HIP(abstract_linear_system_solver):
 
     def _finalize(self):
         if self._h is not None:
-            self._lib.okkt_destroy(self._h)
+            if not self._borrowed:
+                self._lib.okkt_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -406,3 +408,68 @@ class linear_solver_HIP(abstract_linear_system_solver):
     def schur_expand_dev(self, d_rhs, d_x2, d_x, nrhs=1):
         self._need()
         self._check(self._lib.okkt_schur_expand_dev(self._h, C.c_void_p(d_rhs), C.c_void_p(d_x2), C.c_void_p(d_x), int(nrhs)), "okkt_schur_expand_dev")
+
+    # -- selected inversion: entries of F^-1 on the pattern of the factor (not part of the reference interface)
+    @classmethod
+    def of_kkt(cls, kkt):
+        """The level-1 handle of a KKT solver (okkt_kkt_linear_solver) as a linear_solver_HIP that does not own it: its selected
+        inverse, inverse diagonal and log-determinant are those of the matrix okkt_kkt_factor last factored."""
+        self = cls("symmetric")
+        self._lib = kkt._lib
+        self._h = C.c_void_p(kkt._lib.okkt_kkt_linear_solver(kkt._k))
+        self._borrowed = True
+        self._dim = kkt.linear_solver_stats()["n"]
+        return self
+
+    def selinv(self):
+        """okkt_selinv: Z = F^-1 on the stored pattern of L, kept on the device for the exports below.  Returns okkt_selinv_info as a
+        dict (seconds_device, arena_bytes, nonfinite, status)."""
+        self._need()
+        info = L.OkktSelinvInfo()
+        self._check(self._lib.okkt_selinv(self._h, C.byref(info)), "okkt_selinv")
+        return info.as_dict()
+
+    def inverse_diag(self):
+        """diag(F^-1), original order."""
+        self._need()
+        out = np.zeros(self._dim)
+        self._check(self._lib.okkt_get_inverse_diag(self._h, L.p_f64(out)), "okkt_get_inverse_diag")
+        return out
+
+    def inverse_diag_dev(self, d_out):
+        self._need()
+        self._check(self._lib.okkt_get_inverse_diag_dev(self._h, C.c_void_p(d_out)), "okkt_get_inverse_diag_dev")
+
+    def inverse_on_pattern(self):
+        """(F^-1)_ij at every entry of the analysed input pattern, nzval layout (NaN for an upper-triangle entry whose mirror is
+        outside the pattern of L)."""
+        self._need()
+        nnz = C.c_int64()
+        self._check(self._lib.okkt_get_inverse_on_pattern(self._h, None, C.byref(nnz)), "okkt_get_inverse_on_pattern")
+        out = np.zeros(max(nnz.value, 1))
+        self._check(self._lib.okkt_get_inverse_on_pattern(self._h, L.p_f64(out), C.byref(nnz)), "okkt_get_inverse_on_pattern")
+        return out[: nnz.value]
+
+    def inverse_on_pattern_dev(self, d_zval):
+        self._need()
+        self._check(self._lib.okkt_get_inverse_on_pattern_dev(self._h, C.c_void_p(d_zval)), "okkt_get_inverse_on_pattern_dev")
+
+    def inverse_csc(self):
+        """The lower triangle of F^-1 (diagonal included, permuted numbering) on the pattern of L, as scipy CSC."""
+        self._need()
+        nnz = C.c_int64()
+        self._check(self._lib.okkt_get_inverse_csc(self._h, None, None, None, C.byref(nnz)), "okkt_get_inverse_csc")
+        colptr = np.zeros(self._dim + 1, dtype=np.int64)
+        rowval = np.zeros(max(nnz.value, 1), dtype=np.int64)
+        val = np.zeros(max(nnz.value, 1))
+        self._check(self._lib.okkt_get_inverse_csc(self._h, L.p_i64(colptr), L.p_i64(rowval), L.p_f64(val), C.byref(nnz)),
+                    "okkt_get_inverse_csc")
+        return sp.csc_matrix((val[: nnz.value], rowval[: nnz.value], colptr), shape=(self._dim, self._dim))
+
+    def logdet(self):
+        """(log |det F|, sign) from D."""
+        self._need()
+        v = C.c_double()
+        s = C.c_int32()
+        self._check(self._lib.okkt_logdet(self._h, C.byref(v), C.byref(s)), "okkt_logdet")
+        return v.value, int(s.value)
