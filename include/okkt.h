@@ -178,6 +178,40 @@ int okkt_solve_refine(okkt_handle h, const double* nzval, const double* rhs, dou
                       double tol, okkt_refine_info* info /* or NULL */, double* omega_out /* [nrhs] or NULL */);
 int okkt_solve_refine_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
                           double tol, okkt_refine_info* info, double* omega_out);
+/* GMRES-based iterative refinement (GMRES-IR; Carson and Higham, SIAM J. Sci. Comput. 2017/2018): solves
+ * A x = b accurately when the handle holds the factor of a nearby F (A + delta I, a static-pivot factor, the factor of an earlier
+ * iterate), where okkt_solve_refine converges only when rho(I - F^-1 A) < 1 and then only at that rate.  A, nzval and the residual
+ * are as for okkt_solve_refine.  Per right-hand side: x = F \ b; then outer steps, each one double-double residual r = b - A x with
+ * omega, stopping at omega <= tol (<= 0: 2^-52; status 0), at a non-finite value (3), at omega > omega_prev / 2 after a cycle (2) or
+ * when the iterations reach max_iters (1); otherwise one cycle of right-preconditioned GMRES on A d = r: v_1 = r / ||r||_2, each
+ * iteration w = A (F^-1 v_j) with A z accumulated in double-double and rounded once, classical Gram-Schmidt with one full
+ * reorthogonalisation, Givens rotations on the host.  A cycle ends when the Arnoldi residual estimate is <= OKKT_GMRES_INNER_TOL times
+ * ||r||_2, at restart iterations, on a happy breakdown or at the iteration cap; then x += F^-1 (V y) (one more solve per cycle).
+ * Right-hand sides run in lockstep in groups of up to four (one multi-right-hand-side solve pass per preconditioner application);
+ * one small device-to-host read per iteration decides.  Deterministic (no floating-point atomics, fixed summation orders): two calls
+ * give identical bits.  Each right-hand side returns the iterate with the smallest finite omega it reached; max_iters = 0 returns
+ * the x of okkt_solve and omega0.  Returns OKKT_OK whenever it ran: the outcome is in info.status.  rhs may alias sol.  The device
+ * workspace ((restart + 1) x 4 + 8 vectors of dim doubles) is allocated on the first call after an analysis, grown for a larger
+ * restart and released with the analysis.  Refusals as okkt_solve_refine: OKKT_ERR_INVALID for nrhs < 0, max_iters < 0,
+ * restart > 64, before a factorisation, after an early-exit factorisation that stopped short, on partitioned handles and in Schur
+ * mode (the handle stays usable); OKKT_ERR_NO_DEVICE on host_symbolic_only handles. */
+#define OKKT_GMRES_INNER_TOL 1e-10   /* relative tolerance of a GMRES cycle on ||A d - r||_2 / ||r||_2 */
+typedef struct {
+  int32_t iterations; /* preconditioned operator applications inside GMRES cycles, max over the right-hand sides */
+  int32_t cycles;     /* outer steps (one double-double residual + one GMRES cycle each), max over the right-hand sides */
+  int32_t status;     /* worst over the right-hand sides: 0 omega <= tol, 1 iteration limit, 2 stagnated, 3 non-finite */
+  int32_t solves;     /* solve passes with the factor (each carries up to 4 right-hand sides) */
+  double omega0;      /* max over rhs: omega of the plain solve x0 = F \ b */
+  double omega;       /* max over rhs: omega of the returned solutions */
+  double resid_inf;   /* max over rhs: ||b - A x||_inf of the returned solutions */
+  int64_t work_bytes; /* device workspace the call held */
+} okkt_gmres_info;
+int okkt_solve_gmres(okkt_handle h, const double* nzval, const double* rhs, double* sol, int64_t nrhs,
+                     int32_t restart /* 1..64, <= 0: 30 */, int32_t max_iters /* >= 0 */, double tol /* <= 0: 2^-52 */,
+                     okkt_gmres_info* info /* or NULL */, double* omega_out /* [nrhs] or NULL */);
+/* the same with device pointers for nzval, rhs and sol; info and omega_out are host memory */
+int okkt_solve_gmres_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
+                         int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out);
 /* Condition estimation and forward error bounds.  F is the matrix the handle factored: the symmetric matrix
  * whose lower triangle nzval holds (read as the factorisation reads it: upper-triangle entries ignored, duplicates summed) plus the
  * diagonal shift the factorisation adds at assembly (the delta that okkt_kkt_factor puts on the first n pivots; none at level 1).

@@ -144,6 +144,23 @@ class OkktRefineInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktGmresInfo(C.Structure):
+    """okkt_gmres_info: outcome of okkt_solve_gmres (status 0 omega <= tol, 1 iteration limit, 2 stagnated, 3 non-finite)."""
+    _fields_ = [
+        ("iterations", C.c_int32),
+        ("cycles", C.c_int32),
+        ("status", C.c_int32),
+        ("solves", C.c_int32),
+        ("omega0", C.c_double),
+        ("omega", C.c_double),
+        ("resid_inf", C.c_double),
+        ("work_bytes", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class OkktCondestInfo(C.Structure):
     """okkt_condest_info: ||F||_1, the estimate of ||F^-1||_1, their product (status 0 converged, 1 iteration limit, 3 non-finite)."""
     _fields_ = [
@@ -197,6 +214,9 @@ SIGNATURES = {
     "okkt_residual_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _f64p]),
     "okkt_solve_refine": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
     "okkt_solve_refine_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
+    "okkt_solve_gmres": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(OkktGmresInfo),
+                                   _f64p]),
+    "okkt_solve_gmres_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(OkktGmresInfo), _f64p]),
     "okkt_condest": (C.c_int, [_vp, _f64p, C.c_int32, C.POINTER(OkktCondestInfo)]),
     "okkt_condest_dev": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OkktCondestInfo)]),
     "okkt_condest_indices": (C.c_int64, [_vp, _i64p, C.c_int64]),

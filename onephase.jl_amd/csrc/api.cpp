@@ -131,6 +131,7 @@ void solver_refine_release(okkt_solver_s* h) {
   refine_map_release(h->rf);
   condest_release(h->cd);
   selinv_release(h->sl);
+  krylov_release(h->kr);
   h->cd_hist.clear();
   if (h->rf_work) (void)hipFree(h->rf_work);
   if (h->rf_om) (void)hipFree(h->rf_om);
@@ -319,6 +320,251 @@ int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* 
   if (n_solves_out) *n_solves_out = nsolves;
   he = hipStreamSynchronize(st);
   if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("refinement: ") + hipGetErrorString(he));
+  return OKKT_OK;
+}
+
+// ---- GMRES-based iterative refinement (krylov.hip) ---------------------------------------------
+
+namespace {
+constexpr double kGmresInnerTol = OKKT_GMRES_INNER_TOL;
+
+// the host side of one right-hand side's GMRES cycle: the rotated Hessenberg columns, the rotations and the rotated beta e_1
+struct GmresCycle {
+  std::vector<double> H;     // column j at j * kKryCol: R's column after the rotations
+  std::vector<double> cs, sn, g;
+  double beta = 0;
+  int m = 0;                 // columns kept (the correction uses V[0..m))
+  int cap = 0;               // iterations this cycle may take
+  bool live = false;
+};
+
+// take column j (h[0..j+1]) into the cycle; false when the cycle ends with it (the column is kept only if it is usable)
+bool gmres_take_column(GmresCycle& c, int j, const double* h) {
+  for (int i = 0; i <= j + 1; ++i)
+    if (!std::isfinite(h[i])) return false;    // not kept: the correction uses the columns before it
+  double* col = c.H.data() + (size_t)j * kKryCol;
+  for (int i = 0; i <= j + 1; ++i) col[i] = h[i];
+  for (int i = 0; i < j; ++i) {
+    const double t = c.cs[(size_t)i] * col[i] + c.sn[(size_t)i] * col[i + 1];
+    col[i + 1] = -c.sn[(size_t)i] * col[i] + c.cs[(size_t)i] * col[i + 1];
+    col[i] = t;
+  }
+  const double d = std::hypot(col[j], col[j + 1]);
+  if (!(d > 0.0) || !std::isfinite(d)) return false;
+  c.cs[(size_t)j] = col[j] / d;
+  c.sn[(size_t)j] = col[j + 1] / d;
+  col[j] = d;
+  col[j + 1] = 0.0;
+  c.g[(size_t)j + 1] = -c.sn[(size_t)j] * c.g[(size_t)j];
+  c.g[(size_t)j] = c.cs[(size_t)j] * c.g[(size_t)j];
+  c.m = j + 1;
+  const bool happy = !(h[j + 1] > 0.0);
+  return !(std::fabs(c.g[(size_t)j + 1]) <= kGmresInnerTol * c.beta || c.m >= c.cap || happy);
+}
+
+// y = R^-1 g[0..m) by back substitution
+void gmres_solve_y(const GmresCycle& c, double* y) {
+  for (int i = c.m - 1; i >= 0; --i) {
+    double s = c.g[(size_t)i];
+    for (int k = i + 1; k < c.m; ++k) s -= c.H[(size_t)k * kKryCol + i] * y[k];
+    y[i] = s / c.H[(size_t)i * kKryCol + i];
+  }
+}
+}  // namespace
+
+int solver_gmres_device(okkt_solver_s* h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
+                        int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out) {
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  if (max_iters < 0) return solver_set_error(h, OKKT_ERR_INVALID, "max_iters < 0");
+  if (restart > kKryMaxRestart) return solver_set_error(h, OKKT_ERR_INVALID, "restart > 64");
+  if (restart <= 0) restart = 30;
+  int rc = refine_ready(h, true);
+  if (rc != OKKT_OK) return rc;
+  if (!(tol > 0.0)) tol = std::ldexp(1.0, -52);
+  const int64_t n = h->S.n;
+  okkt_gmres_info I;
+  std::memset(&I, 0, sizeof(I));
+  if (nrhs == 0 || n == 0) {
+    I.work_bytes = h->kr.bytes;
+    if (info) *info = I;
+    if (omega_out) for (int64_t q = 0; q < nrhs; ++q) omega_out[q] = 0.0;
+    return OKKT_OK;
+  }
+  std::string e = krylov_alloc(n, restart, h->kr);
+  if (!e.empty()) return solver_set_error(h, OKKT_ERR_ALLOC, "GMRES workspace: " + e);
+  const KrylovWork& K = h->kr;
+  hipStream_t st = h->stream;
+  const int64_t vstride = 4 * n;    // V is [restart + 1][4][n]
+  auto hip_fail = [&](hipError_t he, const char* what) { return solver_set_error(h, OKKT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(he)); };
+  refine_gather_enqueue(h->rf, d_nzval, st);
+  const size_t Q = (size_t)nrhs;
+  std::vector<double> w0(Q, 0.0), wbest(Q, 0.0), rbest(Q, 0.0);
+  std::vector<int> iters(Q, 0), cycles(Q, 0), status(Q, 0);
+  std::vector<double> rd(4 * kKryCol + 16);     // the one read of a step: K.col and, behind it, K.om
+  int nsolves = 0;
+  for (int64_t q0 = 0; q0 < nrhs; q0 += 4) {
+    const int G = (int)std::min<int64_t>(4, nrhs - q0);
+    double* X = d_sol + q0 * n;                  // system g of the group: column q0 + g
+    hipError_t he = hipMemcpyAsync(K.B, d_rhs + q0 * n, (size_t)(G * n) * sizeof(double), hipMemcpyDeviceToDevice, st);
+    if (he != hipSuccess) return hip_fail(he, "GMRES rhs copy");
+    if ((rc = solver_solve_enqueue(h, K.B, X, G, false)) != OKKT_OK) return rc;   // x = F \ b: okkt_solve's batch
+    ++nsolves;
+    double wprev[4] = {0, 0, 0, 0}, rprev[4] = {0, 0, 0, 0};
+    std::vector<int> act;                        // systems of the group that go on; outer slot k belongs to act[k]
+    for (int g = 0; g < G; ++g) act.push_back(g);
+    GmresCycle cyc[4];
+    for (int it = 0; !act.empty(); ++it) {
+      const int na = (int)act.size();
+      ResidSet S;
+      KrySet NS;
+      for (int s = 0; s < 4; ++s) {
+        const int k = std::min(s, na - 1), g = act[(size_t)k];
+        S.b[s] = K.B + g * n; S.x[s] = X + g * n; S.r[s] = K.R + k * n; S.om[s] = K.om + 2 * k;
+        NS.v[s] = K.V; NS.w[s] = K.R + k * n;
+      }
+      NS.vstride = vstride;
+      refine_residual_enqueue(h->rf, S, na, st);
+      krylov_norm_enqueue(K, NS, na, st);        // ||r||_2 to K.col[k][0]
+      he = hipMemcpyAsync(rd.data(), K.col, rd.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+      if (he == hipSuccess) he = hipStreamSynchronize(st);    // the one device-to-host read of an outer step
+      if (he != hipSuccess) return hip_fail(he, "GMRES residual");
+      const double* om = rd.data() + 4 * kKryCol;
+      std::vector<int> next, next_slot;
+      for (int k = 0; k < na; ++k) {
+        const int g = act[(size_t)k];
+        const size_t q = (size_t)(q0 + g);
+        const double w = om[2 * k], ri = om[2 * k + 1], beta = rd[(size_t)k * kKryCol];
+        if (it == 0) w0[q] = w;
+        auto restore = [&]() -> int {      // the previous iterate is the better one: the last correction is undone
+          hipError_t e2 = hipMemcpyAsync(X + g * n, K.XP + g * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st);
+          if (e2 != hipSuccess) return hip_fail(e2, "GMRES restore");
+          wbest[q] = wprev[g]; rbest[q] = rprev[g];
+          return OKKT_OK;
+        };
+        if (!std::isfinite(w) || !std::isfinite(ri) || !std::isfinite(beta)) {
+          status[q] = 3;
+          if (it > 0) { if ((rc = restore()) != OKKT_OK) return rc; }
+          else { wbest[q] = w; rbest[q] = ri; }
+        } else if (w <= tol) {
+          status[q] = 0; wbest[q] = w; rbest[q] = ri;
+        } else if (it > 0 && w > 0.5 * wprev[g]) {
+          status[q] = 2;
+          if (w > wprev[g]) { if ((rc = restore()) != OKKT_OK) return rc; }
+          else { wbest[q] = w; rbest[q] = ri; }
+        } else if (iters[q] >= max_iters) {
+          status[q] = 1; wbest[q] = w; rbest[q] = ri;
+        } else {
+          wprev[g] = w; rprev[g] = ri;
+          next.push_back(g);
+          next_slot.push_back(k);
+        }
+      }
+      if (next.empty()) break;
+      // one GMRES cycle for the systems that go on; cycle slot c belongs to next[c].  v_0 = r / ||r||_2
+      const int C = (int)next.size();
+      KryScale SC;
+      for (int s = 0; s < 4; ++s) {
+        const int c = std::min(s, C - 1);
+        SC.src[s] = K.R + next_slot[(size_t)c] * n; SC.dst[s] = K.V + c * n; SC.div[s] = K.col + (size_t)next_slot[(size_t)c] * kKryCol;
+      }
+      for (int c = 0; c < C; ++c) {
+        const size_t q = (size_t)(q0 + next[(size_t)c]);
+        GmresCycle& cy = cyc[c];
+        cy.H.assign((size_t)restart * kKryCol, 0.0);
+        cy.cs.assign((size_t)restart, 0.0); cy.sn.assign((size_t)restart, 0.0); cy.g.assign((size_t)restart + 1, 0.0);
+        cy.beta = rd[(size_t)next_slot[(size_t)c] * kKryCol];
+        cy.g[0] = cy.beta;
+        cy.m = 0;
+        cy.cap = std::min(restart, max_iters - iters[q]);
+        cy.live = true;
+        ++cycles[q];
+      }
+      krylov_scale_enqueue(n, SC, C, st);
+      for (int j = 0;; ++j) {
+        std::vector<int> live;
+        for (int c = 0; c < C; ++c) if (cyc[c].live) live.push_back(c);
+        if (live.empty()) break;
+        const int nl = (int)live.size();
+        const double* Vj = K.V + (int64_t)j * vstride;
+        const double* zin = Vj;               // the live systems' v_j, contiguous when they are a prefix of the slots
+        if (live.back() != nl - 1) {
+          for (int k = 0; k < nl; ++k) {
+            he = hipMemcpyAsync(K.P + k * n, Vj + live[(size_t)k] * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st);
+            if (he != hipSuccess) return hip_fail(he, "GMRES pack");
+          }
+          zin = K.P;
+        }
+        if ((rc = solver_solve_enqueue(h, zin, K.Z, nl, false)) != OKKT_OK) return rc;   // z = F^-1 v_j
+        ++nsolves;
+        ResidSet OS;
+        KrySet AS;
+        for (int s = 0; s < 4; ++s) {
+          const int k = std::min(s, nl - 1);
+          OS.b[s] = K.zero; OS.x[s] = K.Z + k * n; OS.r[s] = K.W + k * n; OS.om[s] = K.om + 8 + 2 * k;
+          AS.v[s] = K.V + live[(size_t)k] * n; AS.w[s] = K.W + k * n;
+        }
+        AS.vstride = vstride;
+        refine_residual_enqueue(h->rf, OS, nl, st);   // W = 0 - A z: -(A z) in double-double, rounded once
+        krylov_dots_enqueue(K, AS, nl, j + 1, true, st);
+        krylov_orth_dots_enqueue(K, AS, nl, j + 1, true, st);
+        krylov_orth_norm_enqueue(K, AS, nl, j + 1, st);
+        he = hipMemcpyAsync(rd.data(), K.col, (size_t)nl * kKryCol * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess) he = hipStreamSynchronize(st);    // the one device-to-host read of an iteration
+        if (he != hipSuccess) return hip_fail(he, "GMRES iteration");
+        KryScale NV;
+        int nn = 0;
+        for (int k = 0; k < nl; ++k) {
+          const int c = live[(size_t)k];
+          GmresCycle& cy = cyc[c];
+          const bool more = gmres_take_column(cy, j, rd.data() + (size_t)k * kKryCol);
+          ++iters[(size_t)(q0 + next[(size_t)c])];
+          if (!more) { cy.live = false; continue; }
+          NV.src[nn] = K.W + k * n; NV.dst[nn] = K.V + (int64_t)(j + 1) * vstride + c * n; NV.div[nn] = K.col + (size_t)k * kKryCol + (j + 1);
+          ++nn;
+        }
+        for (int s = nn; s < 4; ++s) { NV.src[s] = NV.src[0]; NV.dst[s] = NV.dst[0]; NV.div[s] = NV.div[0]; }
+        if (nn > 0) krylov_scale_enqueue(n, NV, nn, st);   // v_j+1 = w / h_j+1,j
+      }
+      // x += F^-1 (V y) for the systems whose cycle kept a column
+      KryCombine CB;
+      CB.vstride = vstride;
+      std::vector<int> upd;
+      for (int c = 0; c < C; ++c) {
+        if (cyc[c].m == 0) continue;
+        const int e2 = (int)upd.size();
+        CB.v[e2] = K.V + c * n; CB.u[e2] = K.U + e2 * n; CB.m[e2] = cyc[c].m;
+        gmres_solve_y(cyc[c], CB.y[e2]);
+        upd.push_back(c);
+      }
+      const int ne = (int)upd.size();
+      if (ne > 0) {
+        for (int s = ne; s < 4; ++s) { CB.v[s] = CB.v[0]; CB.u[s] = CB.u[0]; CB.m[s] = 0; }
+        krylov_combine_enqueue(n, CB, ne, st);
+        if ((rc = solver_solve_enqueue(h, K.U, K.Z, ne, false)) != OKKT_OK) return rc;   // d = F^-1 (V y)
+        ++nsolves;
+        UpdateSet U;
+        for (int s = 0; s < 4; ++s) {
+          const int k = std::min(s, ne - 1), g = next[(size_t)upd[(size_t)k]];
+          U.x[s] = X + g * n; U.xp[s] = K.XP + g * n; U.d[s] = K.Z + k * n;
+        }
+        refine_update_enqueue(n, U, ne, st);
+      }
+      act.swap(next);
+    }
+  }
+  for (size_t q = 0; q < Q; ++q) {
+    if (q == 0) { I.omega0 = w0[q]; I.omega = wbest[q]; I.resid_inf = rbest[q]; }
+    else { I.omega0 = nan_max(I.omega0, w0[q]); I.omega = nan_max(I.omega, wbest[q]); I.resid_inf = nan_max(I.resid_inf, rbest[q]); }
+    I.iterations = std::max(I.iterations, iters[q]);
+    I.cycles = std::max(I.cycles, cycles[q]);
+    I.status = std::max(I.status, status[q]);
+    if (omega_out) omega_out[q] = wbest[q];
+  }
+  I.solves = nsolves;
+  I.work_bytes = K.bytes;
+  if (info) *info = I;
+  hipError_t he = hipStreamSynchronize(st);
+  if (he != hipSuccess) return hip_fail(he, "GMRES");
   return OKKT_OK;
 }
 
@@ -780,7 +1026,7 @@ int okkt_analyze(okkt_handle h, int64_t dim, const int64_t* colptr, const int64_
     if (h->opts.ordering == 2 && (int64_t)h->user_perm.size() != dim)
       return solver_set_error(h, OKKT_ERR_INVALID, "ordering=user: okkt_set_perm must supply dim entries first");
     auto t0 = std::chrono::steady_clock::now();
-    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned)) {   // the refinement map (and Z) belong to the old pattern
+    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned || h->kr.V)) {   // the refinement map (and Z) belong to the old pattern
       (void)hipSetDevice(h->device);
       (void)hipStreamSynchronize(h->stream);
       solver_refine_release(h);
@@ -1141,6 +1387,55 @@ int okkt_solve_refine(okkt_handle h, const double* nzval, const double* rhs, dou
     return OKKT_OK;
   } catch (...) {
     return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_solve_refine");
+  }
+}
+
+int okkt_solve_gmres_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
+                         int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs > 0 && (!d_rhs || !d_sol || (!d_nzval && h->S.nnz_in > 0))) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+  try {
+    return solver_gmres_device(h, d_nzval, d_rhs, d_sol, nrhs, restart, max_iters, tol, info, omega_out);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_solve_gmres_dev");
+  }
+}
+
+int okkt_solve_gmres(okkt_handle h, const double* nzval, const double* rhs, double* sol, int64_t nrhs, int32_t restart, int32_t max_iters,
+                     double tol, okkt_gmres_info* info, double* omega_out) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  if (max_iters < 0) return solver_set_error(h, OKKT_ERR_INVALID, "max_iters < 0");
+  if (restart > kKryMaxRestart) return solver_set_error(h, OKKT_ERR_INVALID, "restart > 64");
+  if (nrhs > 0 && (!rhs || !sol || (!nzval && h->S.nnz_in > 0))) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+  try {
+    int rc = refine_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    const int64_t len = h->S.n * nrhs;
+    if (len == 0) return solver_gmres_device(h, nullptr, nullptr, nullptr, nrhs, restart, max_iters, tol, info, omega_out);
+    std::string e = refine_stage_alloc(h->rf);
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_ALLOC, "nzval staging: " + e);
+    if (h->rhs_stage_len < len) {
+      (void)hipStreamSynchronize(h->stream);
+      if (h->d_rhs_stage) (void)hipFree(h->d_rhs_stage);
+      h->d_rhs_stage = nullptr;
+      h->rhs_stage_len = 0;
+      if (hipMalloc((void**)&h->d_rhs_stage, (size_t)len * sizeof(double)) != hipSuccess)
+        return solver_set_error(h, OKKT_ERR_ALLOC, "rhs staging allocation failed");
+      h->rhs_stage_len = len;
+    }
+    hipStream_t st = h->stream;
+    hipError_t he = hipSuccess;
+    if (h->S.nnz_in > 0) he = hipMemcpyAsync(h->rf.nz_stage, nzval, (size_t)h->S.nnz_in * sizeof(double), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(h->d_rhs_stage, rhs, (size_t)len * sizeof(double), hipMemcpyHostToDevice, st);
+    if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("GMRES upload: ") + hipGetErrorString(he));
+    rc = solver_gmres_device(h, h->rf.nz_stage, h->d_rhs_stage, h->d_rhs_stage, nrhs, restart, max_iters, tol, info, omega_out);
+    if (rc != OKKT_OK) return rc;
+    if (hipMemcpy(sol, h->d_rhs_stage, (size_t)len * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "sol download failed");
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_solve_gmres");
   }
 }
 

@@ -7,6 +7,7 @@
 
 #include "../../include/okkt.h"
 #include "condest.h"
+#include "krylov.h"
 #include "numeric.h"
 #include "refine.h"
 #include "selinv.h"
@@ -65,6 +66,9 @@ struct okkt_solver_s {
   // factor_seq counts the factorisations started, so that Z is known stale after the next one
   okkt::SelinvWork sl;
   int64_t factor_seq = 0;
+  // GMRES-based refinement (krylov.hip): the basis and the vectors of one group of right-hand sides, allocated on the first
+  // okkt_solve_gmres after an analysis (grown for a larger restart) and released with the refinement map
+  okkt::KrylovWork kr;
 };
 
 namespace okkt {
@@ -92,6 +96,11 @@ int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* 
                          double tol, okkt_refine_info* info, double* omega_out, void (*lap)(void*, int) = nullptr, void* lap_ctx = nullptr,
                          int* n_solves_out = nullptr);
 void solver_refine_release(okkt_solver_s* h);
+// GMRES-based refinement driver (api.cpp): x = F \ b, then outer steps of one double-double residual and one
+// right-preconditioned GMRES(restart) cycle on A d = r each, right-hand sides in lockstep groups of up to four.  Pointers as
+// solver_refine_device's
+int solver_gmres_device(okkt_solver_s* h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
+                        int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out);
 // condition estimate of the factored F (the values d_nzval plus the factorisation's diagonal shift) and forward error bounds (api.cpp)
 int solver_condest_device(okkt_solver_s* h, const double* d_nzval, int32_t t, okkt_condest_info* info);
 int solver_forward_error_device(okkt_solver_s* h, const double* d_nzval, const double* d_b, const double* d_x, int64_t nrhs, double* ferr_out,

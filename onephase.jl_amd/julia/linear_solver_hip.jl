@@ -158,6 +158,30 @@ function ls_solve_refine!(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,
     return info[]
 end
 
+struct OkktGmresInfo      # okkt_gmres_info of include/okkt.h
+    iterations::Int32    # preconditioned operator applications inside GMRES cycles
+    cycles::Int32        # outer steps (one double-double residual + one GMRES cycle each)
+    status::Int32        # 0 omega <= tol, 1 iteration limit, 2 stagnated, 3 non-finite
+    solves::Int32        # solve passes with the factor
+    omega0::Float64
+    omega::Float64
+    resid_inf::Float64
+    work_bytes::Int64
+end
+
+# sol for A sol = rhs with the held factor F ~ A as the preconditioner of GMRES(restart) cycles on the correction equation, the
+# residual in double-double (GMRES-IR): converges where ls_solve_refine! stalls because F is too far from A.  Not part of the
+# reference interface (DESIGN.md section 8.6).
+function ls_solve_gmres(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}, my_rhs::Array{Float64,1}, my_sol::Array{Float64,1};
+                        restart::Integer=30, max_iters::Integer=200, tol::Float64=0.0)
+    info = Ref(OkktGmresInfo(0, 0, 0, 0, 0.0, 0.0, 0.0, 0))
+    rc = ccall((:okkt_solve_gmres, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Float64,
+                                                    Ref{OkktGmresInfo}, Ptr{Float64}),
+               solver.handle, A.nzval, my_rhs, my_sol, 1, Int32(restart), Int32(max_iters), tol, info, C_NULL)
+    rc < 0 && okkt_error(solver, "okkt_solve_gmres", rc)
+    return info[]
+end
+
 struct OkktCondestInfo    # okkt_condest_info of include/okkt.h
     norm1::Float64       # ||F||_1, exact
     inv_norm1::Float64   # estimate of ||F^-1||_1 (a lower bound)

@@ -293,6 +293,33 @@ class linear_solver_HIP(abstract_linear_system_solver):
         d["omega_per_rhs"] = om
         return (X[0] if single else X), d
 
+    def ls_solve_gmres(self, nzval_or_matrix, rhs, restart=30, max_iters=200, tol=0.0):
+        """GMRES-based refinement (okkt_solve_gmres): x for A x = b with the held factor F ~ A as the
+        preconditioner of GMRES(restart) cycles on the correction equation, the residual in double-double.  A as for ls_solve_refine
+        (its values in the analysed order, or the matrix itself).  rhs: a vector or one right-hand side per row.  Returns (x, info)
+        with info = okkt_gmres_info as a dict plus "omega_per_rhs"."""
+        self._need()
+        vals = self._values(nzval_or_matrix)
+        B, single = self._rhs_block(rhs, self._dim)
+        X = np.zeros_like(B)
+        om = np.zeros(B.shape[0])
+        info = L.OkktGmresInfo()
+        self._check(self._lib.okkt_solve_gmres(self._h, L.p_f64(vals), L.p_f64(B), L.p_f64(X), B.shape[0], int(restart), int(max_iters),
+                                                float(tol), C.byref(info), L.p_f64(om)), "okkt_solve_gmres")
+        d = info.as_dict()
+        d["omega_per_rhs"] = om
+        return (X[0] if single else X), d
+
+    def ls_solve_gmres_dev(self, d_nzval, d_rhs, d_sol, nrhs=1, restart=30, max_iters=200, tol=0.0):
+        """ls_solve_gmres with every array resident in HBM (device pointers); returns (info dict, omega per rhs)."""
+        self._need()
+        info = L.OkktGmresInfo()
+        om = np.zeros(max(int(nrhs), 1))
+        self._check(self._lib.okkt_solve_gmres_dev(self._h, C.c_void_p(d_nzval), C.c_void_p(d_rhs), C.c_void_p(d_sol), int(nrhs),
+                                                    int(restart), int(max_iters), float(tol), C.byref(info), L.p_f64(om)),
+                    "okkt_solve_gmres_dev")
+        return info.as_dict(), om[: int(nrhs)]
+
     def residual(self, nzval_or_matrix, rhs, x):
         """(r, omega): r = b - A x accumulated in double-double and rounded once, omega the componentwise backward error
         max_i |r_i| / (|A||x| + |b|)_i, per right-hand side."""
