@@ -520,6 +520,11 @@ int okkt_kkt_compute_indicies(okkt_kkt_handle k, const double* J_nzval, int64_t*
  * group's combined u (update_indicies!, clever_symmetric.jl:262-287).  Any pointer may be NULL. */
 int okkt_kkt_get_indicies(okkt_kkt_handle k, int64_t* first_para_indicies, int64_t* group_ptr, int64_t* member_ind,
                           double* member_ratio, double* member_u, double* member_g, double* group_u);
+/* read-only, for tests: diag_rescale [n + m_new] of the last okkt_kkt_form_system and, of the last okkt_kkt_compute_direction,
+ * symmetric_primal_rhs [m], the combined rhs of the groups [m_new], the refined solution of the scaled system [n + m_new] and
+ * v [m_new], the group part of the unscaled solution (clever_symmetric.jl:417-474).  Any pointer may be NULL.  The last four are
+ * refused (OKKT_ERR_INVALID) unless that direction is the last thing computed on the handle; the other kinds refuse the call. */
+int okkt_kkt_get_clever_vectors(okkt_kkt_handle k, double* diag_rescale, double* symrhs, double* crhs, double* sol, double* v);
 /* diag_rescale used by the next okkt_kkt_form_system: mode OKKT_RESCALE_*, mu = iter.point.mu,
  * x_norm_inf = norm(iter.point.x, Inf) (create_diag_rescale_*, clever_symmetric.jl:307-319); default NONE */
 int okkt_kkt_set_rescale(okkt_kkt_handle k, int mode, double mu, double x_norm_inf);

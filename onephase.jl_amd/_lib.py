@@ -293,6 +293,7 @@ SIGNATURES = {
     "okkt_kkt_direction_error_bound": (C.c_int, [_vp, _f64p]),
     "okkt_kkt_compute_indicies": (C.c_int, [_vp, _f64p, C.POINTER(C.c_int64)]),
     "okkt_kkt_get_indicies": (C.c_int, [_vp, _i64p, _i64p, _i64p, _f64p, _f64p, _f64p, _f64p]),
+    "okkt_kkt_get_clever_vectors": (C.c_int, [_vp, _f64p, _f64p, _f64p, _f64p, _f64p]),
     "okkt_kkt_set_rescale": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),
     "okkt_kkt_set_direction": (C.c_int, [_vp, _f64p, _f64p, _f64p]),
     "okkt_kkt_max_step_primal": (C.c_int, [_vp, _f64p, C.c_double, _f64p, _f64p]),

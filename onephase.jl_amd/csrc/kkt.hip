@@ -967,6 +967,7 @@ int okkt_kkt_form_system(okkt_kkt_handle k, const double* H_nzval, const double*
   if ((k->nnzH > 0 && !H_nzval) || (k->nnzJ > 0 && !J_nzval)) return OKKT_ERR_INVALID;
   k->have_dir = false;
   k->sym_dir_ok = false;
+  k->clever_vecs_ok = false;
   k->have_dxnorm = false;
   hipStream_t st = kk_stream(k);
   KK_TRY(k, hipSetDevice(k->ls->device));
@@ -1101,6 +1102,7 @@ int okkt_kkt_estimate_y_tilde(okkt_kkt_handle k, const double* g, double* y_out)
   KK_TRY(k, hipGetLastError());
   k->have_dir = false;
   k->sym_dir_ok = false;
+  k->clever_vecs_ok = false;
   return OKKT_OK;
 }
 
@@ -1118,6 +1120,7 @@ static int kkt_factor_impl(okkt_kkt_s* k, double delta, okkt_inertia* inertia_ou
   k->factored = false;
   k->have_dir = false;
   k->sym_dir_ok = false;
+  k->clever_vecs_ok = false;
   hipStream_t st = kk_stream(k);
   k->tm_factor.reset();
   const size_t e0 = k->tm_factor.mark(st);
@@ -1280,6 +1283,7 @@ int okkt_kkt_system_rhs(okkt_kkt_handle k, const double* J_nzval_cur, const doub
   k->have_cur = true;
   k->have_rhs = true;
   k->sym_dir_ok = false;
+  k->clever_vecs_ok = false;
   return OKKT_OK;
 }
 
@@ -1319,6 +1323,7 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
     return kk_fail(k, OKKT_ERR_INVALID, "the last factorisation was a discarded trial of the delta loop (it stopped early): factor! again before a direction");
   if (!host_rhs && !k->have_rhs) return kk_fail(k, OKKT_ERR_INVALID, "no resident rhs: okkt_kkt_system_rhs has not been called");
   k->sym_dir_ok = false;
+  k->clever_vecs_ok = false;
   const bool direct = k->kind == OKKT_KKT_SCHUR_DIRECT;
   if (direct && !k->have_cur) return kk_fail(k, OKKT_ERR_INVALID, "Schur_KKT_solver_direct reads current_it: kkt_associate_rhs! (okkt_kkt_system_rhs) has not been called");
   hipStream_t st = kk_stream(k);
@@ -1451,6 +1456,7 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
   k->have_dir = true;
   k->have_dxnorm = false;
   k->sym_dir_ok = k->kind == OKKT_KKT_SYMMETRIC;
+  k->clever_vecs_ok = k->kind == OKKT_KKT_CLEVER_SYMMETRIC;
   return OKKT_OK;
 }
 
@@ -1602,6 +1608,7 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
     err_out[q] = E;
   }
   k->have_dir = false;
+  k->clever_vecs_ok = false;
   k->sym_dir_ok = false;     // the resident single direction of okkt_kkt_compute_direction is not touched; the step-side kernels keep refusing until it is set
   return OKKT_OK;
 }
@@ -1655,7 +1662,8 @@ int okkt_kkt_compute_indicies(okkt_kkt_handle k, const double* J_nzval, int64_t*
     };
     std::vector<int64_t> sorted_cols(m);
     std::iota(sorted_cols.begin(), sorted_cols.end(), (int64_t)0);
-    std::sort(sorted_cols.begin(), sorted_cols.end(), before);
+    // stable, as the reference's sort is: empty rows are equivalent under `before`, and the lowest of them has to lead their group
+    std::stable_sort(sorted_cols.begin(), sorted_cols.end(), before);
     // columns_are_same on the UNscaled matrix (clever_symmetric.jl:63-88)
     auto same = [&](int64_t i, int64_t j) -> bool {
       if (len(i) != len(j)) return false;
@@ -1773,6 +1781,25 @@ int okkt_kkt_get_indicies(okkt_kkt_handle k, int64_t* first_para_indicies, int64
     }
     if (group_u && k->m_new) KK_TRY(k, hipMemcpy(group_u, k->gU, (size_t)k->m_new * 8, hipMemcpyDeviceToHost));
   }
+  return OKKT_OK;
+}
+
+// the intermediate vectors of the clever-symmetric kind (tests): diag_rescale of the last form_system; symmetric_primal_rhs, the
+// combined rhs, the refined solution of the scaled system and v of the last okkt_kkt_compute_direction (vm1, crhs, big2, the head
+// of big4: no later call has written them)
+int okkt_kkt_get_clever_vectors(okkt_kkt_handle k, double* diag_rescale, double* symrhs, double* crhs, double* sol, double* v) {
+  if (!k) return OKKT_ERR_INVALID;
+  if (k->kind != OKKT_KKT_CLEVER_SYMMETRIC) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_get_clever_vectors applies to the clever-symmetric solver only");
+  if (!k->formed) return kk_fail(k, OKKT_ERR_INVALID, "diag_rescale exists after form_system");
+  if ((symrhs || crhs || sol || v) && !k->clever_vecs_ok)
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_get_clever_vectors: no direction of okkt_kkt_compute_direction for the current factorisation and rhs");
+  KK_TRY(k, hipStreamSynchronize(kk_stream(k)));
+  const int64_t dim = k->n + k->m_new;
+  if (diag_rescale && dim) KK_TRY(k, hipMemcpy(diag_rescale, k->Dres, (size_t)dim * 8, hipMemcpyDeviceToHost));
+  if (symrhs && k->m) KK_TRY(k, hipMemcpy(symrhs, k->vm1, (size_t)k->m * 8, hipMemcpyDeviceToHost));
+  if (crhs && k->m_new) KK_TRY(k, hipMemcpy(crhs, k->crhs, (size_t)k->m_new * 8, hipMemcpyDeviceToHost));
+  if (sol && dim) KK_TRY(k, hipMemcpy(sol, k->big2, (size_t)dim * 8, hipMemcpyDeviceToHost));
+  if (v && k->m_new) KK_TRY(k, hipMemcpy(v, k->big4, (size_t)k->m_new * 8, hipMemcpyDeviceToHost));
   return OKKT_OK;
 }
 

@@ -80,6 +80,9 @@ struct okkt_kkt_s {
   // symmetric kind, okkt_kkt_direction_error_bound: rD, rP, rC, y, dx and dy still hold the rhs and the solution of the last
   // okkt_kkt_compute_direction's solve (cleared by every call that writes one of them); the rhs and the solution reassembled
   bool sym_dir_ok = false;
+  // clever-symmetric kind, okkt_kkt_get_clever_vectors: vm1, crhs and big4 still hold symmetric_primal_rhs, the combined rhs and v of
+  // the last okkt_kkt_compute_direction (cleared where sym_dir_ok is)
+  bool clever_vecs_ok = false;
   double *eb_rhs = nullptr, *eb_sol = nullptr;
   int64_t part_blocks = 0;
   // device timers: (tag, start, stop) event segments of the last call of each kind, summed per tag on request

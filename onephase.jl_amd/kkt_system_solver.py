@@ -272,6 +272,17 @@ class HIP_KKT_solver:
                 for g in range(mn)]
         return [int(v) for v in first], info
 
+    def clever_vectors(self, direction=True):
+        """The clever-symmetric solver's intermediates (tests): dict(D = diag_rescale of the last form_system_b and, with direction,
+        symrhs = symmetric_primal_rhs, crhs = the groups' combined rhs, sol = the refined solution of the scaled system, v = the group
+        part of the unscaled solution of the last compute_direction_b).  Refused for the other kinds and, with direction, unless that direction is the last thing computed."""
+        mn = self.m_new if self.kind == "clever_symmetric" else 0
+        dim = (self._pattern[0] if self._pattern is not None else 0) + mn
+        D, symrhs, crhs, sol, v = np.zeros(dim), np.zeros(self._m), np.zeros(mn), np.zeros(dim), np.zeros(mn)
+        a = (L.p_f64(symrhs), L.p_f64(crhs), L.p_f64(sol), L.p_f64(v)) if direction else (None, None, None, None)
+        self._check(self._lib.okkt_kkt_get_clever_vectors(self._k, L.p_f64(D), *a), "okkt_kkt_get_clever_vectors")
+        return dict(D=D, symrhs=symrhs, crhs=crhs, sol=sol, v=v) if direction else dict(D=D)
+
     def finalize_b(self):
         if self._k is not None:
             self._lib.okkt_kkt_destroy(self._k)

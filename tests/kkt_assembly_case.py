@@ -1,6 +1,6 @@
 """Helper of test_gpu_kkt_assembly.py (run as a subprocess: OKKT_SCHUR_GROUPS and OKKT_DENSE_DOT are read once per process).
 argv: output .npz, mode, design names of kkt_designs.DESIGNS.  mode "q": the Schur kind's matrix only; "full": for the schur,
-schur_direct and symmetric kinds the matrix of two form_system calls and schur_diag, then (designs with factor = True) one factor
+schur_direct, symmetric and clever_symmetric kinds the matrix of two form_system calls and schur_diag, then (designs with factor = True) one factor
 at kkt_designs.shift, System_rhs of a moved current iterate and its direction with the N err.  The test checks the arrays against
 kkt_exact."""
 import json
@@ -24,7 +24,7 @@ def iterate(d, J=None, s=None, y=None, seed=0):
 
 
 def run(d, kind, res, tag, full, last=0.0, grad_nan=False):
-    opts = {"schur_dense_rows": d.dense} if kind != "symmetric" and d.dense else {}
+    opts = {"schur_dense_rows": d.dense} if kind in ("schur", "schur_direct") and d.dense else {}
     k = KS.HIP_KKT_solver(kind, **opts)
     it = iterate(d)
     k.initialize_b(it)
@@ -63,7 +63,7 @@ for name in names:
         continue
     d = KD.DESIGNS[name]
     print(f"okkt-case: design {name}", file=sys.stderr, flush=True)
-    for kind in (("schur",) if mode == "q" else ("schur", "schur_direct", "symmetric")):
+    for kind in (("schur",) if mode == "q" else ("schur", "schur_direct", "symmetric", "clever_symmetric")):
         run(d, kind, res, f"{name}/{kind}", mode == "full")
 np.savez(out, **res)
 print("CASE_OK", json.dumps(len(res)))

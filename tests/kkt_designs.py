@@ -256,3 +256,143 @@ def moved(d, seed=0, last=0.0):
         s2[-1] *= 3.0
         y2[-1] /= 3.0
     return J2, s2, y2
+
+
+# ---- designs of the clever-symmetric kind: rows of J that are exact multiples of each other -------------------------------------
+@dataclass
+class CleverDesign(Design):
+    """A Design plus what compute_indicies (clever_symmetric.jl:200-260) has to find in its J: groups = [(members in ls order,
+    their ratios to the leader)], sorted by leader (= members[0], the group's first row in the sorted order of the rescaled rows)."""
+    groups: list = field(default_factory=list)
+
+    @property
+    def m_new(self):
+        return len(self.groups)
+
+
+def _three_pair(rng, k):
+    """Values v of a k-entry row such that the rows v and 3 v (a) differ after rescaling by their first value, so the sort -- not
+    the row number -- decides which of them leads, and (b) still merge under columns_are_same's 1e-16 test (clever_symmetric.jl:63-88,
+    107-155 restated; tests/test_kkt_clever_designs.py pins what the oracle itself decides).  Returns (v, 3 v, True if 3 v leads)."""
+    for _ in range(10000):
+        a = _vals(rng, k)
+        b = 3.0 * a
+        ra, rb = a / a[0], b / b[0]
+        if np.array_equal(ra, rb):
+            continue
+        p = int(np.nonzero(ra != rb)[0][0])
+        three_leads = bool(rb[p] < ra[p])
+        lead, other = (b, a) if three_leads else (a, b)
+        if np.sqrt(np.sum((lead - other * (lead[0] / other[0])) ** 2)) < 1e-16:
+            return a, b, three_leads
+    raise AssertionError("no merging ratio-3 pair found")
+
+
+def clever_family(name, why, n, seed, singles=0, pow2=(), three=0, near=0, pattern=0, empty=0, empty_cols=0, h=3.0, no_diag=0.2, r=4):
+    """A clever design from families of rows, scattered through the row order by a random permutation:
+    singles: rows of their own; pow2: one group per entry, its members the given power-of-two multiples (both signs) of one base row
+    -- their rescaled rows are bitwise equal, the lowest row leads; three: pairs (v, 3 v) whose leader is the HIGHER row (_three_pair);
+    near: pairs (v, v with one entry off by a relative 1e-12) that must not merge; pattern: pairs with one pattern and unrelated
+    values; empty: empty rows (one group).  Every non-empty row has at least two entries and every family a pattern of its own."""
+    rng = np.random.default_rng(seed)
+    live = np.sort(rng.choice(n, size=n - empty_cols, replace=False))
+    seen = set()
+
+    def pat():
+        while True:
+            k = int(np.clip(round(rng.uniform(0.6, 1.4) * r), 2, len(live)))
+            c = tuple(np.sort(rng.choice(live, size=k, replace=False)))
+            if c not in seen:
+                seen.add(c)
+                return np.array(c, np.int64)
+
+    rows, fams = [], []           # rows: (cols, vals); fams: [(row ids of a family, kind, data)]
+    for _ in range(singles):
+        c = pat(); rows.append((c, _vals(rng, len(c)))); fams.append(([len(rows) - 1], "group", [1.0]))
+    for fac in pow2:
+        c = pat(); v = _vals(rng, len(c))
+        ids = []
+        for f in fac:
+            rows.append((c, f * v)); ids.append(len(rows) - 1)
+        fams.append((ids, "group", list(fac)))
+    for _ in range(three):
+        c = pat(); a, b, three_leads = _three_pair(rng, 2)
+        c = c[:2]
+        rows.append((c, a)); rows.append((c, b))
+        fams.append(([len(rows) - 2, len(rows) - 1], "three", three_leads))
+    for _ in range(near):
+        c = pat(); v = _vals(rng, len(c)); w = v.copy(); w[-1] *= 1.0 + 1e-12
+        rows.append((c, v)); rows.append((c, 2.0 * w))
+        fams.append(([len(rows) - 2], "group", [1.0])); fams.append(([len(rows) - 1], "group", [1.0]))
+    for _ in range(pattern):
+        c = pat()
+        for _ in range(2):
+            rows.append((c, _vals(rng, len(c)))); fams.append(([len(rows) - 1], "group", [1.0]))
+    ids = []
+    for _ in range(empty):
+        rows.append((np.zeros(0, np.int64), np.zeros(0))); ids.append(len(rows) - 1)
+    if ids:
+        fams.append((ids, "group", [1.0] * len(ids)))
+    m = len(rows)
+    place = rng.permutation(m)                      # row t of the list above becomes row place[t] of J
+    groups = []
+    for ids, kind, data in fams:
+        at = [int(place[t]) for t in ids]
+        if kind == "three":                         # the leader takes the higher of the two places
+            lead = 1 if data else 0
+            hi, lo = max(at), min(at)
+            place[ids[lead]], place[ids[1 - lead]] = hi, lo
+            vl, vo = rows[ids[lead]][1], rows[ids[1 - lead]][1]
+            groups.append(([hi, lo], [1.0, float(vo[0] / vl[0])]))
+        else:
+            order = np.argsort(at)                  # equal rescaled rows: the sort falls back on the row number
+            groups.append(([at[i] for i in order], [float(data[i] / data[order[0]]) for i in order]))
+    groups.sort(key=lambda g: g[0][0])
+    ri = np.concatenate([np.full(len(c), place[t], np.int64) for t, (c, _) in enumerate(rows)] + [np.zeros(0, np.int64)])
+    ci = np.concatenate([c for c, _ in rows] + [np.zeros(0, np.int64)])
+    vv = np.concatenate([v for _, v in rows] + [np.zeros(0)])
+    J = sp.csc_matrix((vv, (ri, ci)), shape=(m, n))
+    J.sum_duplicates()
+    H = _h(rng, n, h, no_diag=no_diag) if h else sp.csc_matrix((n, n))
+    s, y = _sy(rng, m)
+    return CleverDesign(name, why, H.tocsc(), J, s, y, groups=groups)
+
+
+def singleton_groups(d):
+    """The grouping of a design whose non-empty rows are pairwise non-parallel: every row its own group, the empty rows one group led
+    by the lowest of them."""
+    empty = [int(i) for i in np.nonzero(np.diff(d.J.tocsr().indptr) == 0)[0]]
+    g = [([i], [1.0]) for i in range(d.m) if i not in set(empty)]
+    if empty:
+        g.append((empty, [1.0] * len(empty)))
+    return sorted(g, key=lambda t: t[0][0])
+
+
+def _clever_list():
+    P = lambda *e: tuple(2.0 ** k * sg for k, sg in e)     # (exponent, sign) -> factor
+    out = [
+        clever_family("cg_mix", "groups of 1, 2, 3, 5 and 7 scattered through 293 rows, both signs, a ratio-3 pair led by its higher row, a "
+                      "near-parallel pair, a same-pattern pair, 5 empty rows, 7 empty columns; m_new = 210 < 256 < m", 211, 61, singles=150,
+                      pow2=[P((0, 1), (e, sg)) for e, sg in zip([1, -1, 2, -3, 5, -6, 10, -10] * 5, [1, -1] * 20)]
+                      + [P((0, 1), (1, -1), (-2, 1)), P((0, -1), (3, 1), (-1, -1)), P((2, 1), (0, 1), (-2, -1))] * 3 + [P((1, 1), (0, -1), (4, 1))]
+                      + [P((0, 1), (1, 1), (-1, -1), (2, -1), (-3, 1))] * 3 + [P((0, 1), (-1, -1), (1, 1), (-2, 1), (2, -1), (3, 1), (-4, -1))],
+                      three=1, near=1, pattern=1, empty=5, empty_cols=7, h=3.0, no_diag=0.3),
+        clever_family("cg_big", "m_new = 283 > 256 (two workgroups of groups, the second partial), no H column has its diagonal", 150, 62,
+                      singles=240, pow2=[P((0, 1), (1, -1))] * 15 + [P((-1, 1), (2, 1))] * 15 + [P((0, -1), (1, 1), (-1, 1))] * 10
+                      + [P((0, 1), (1, -1), (2, 1), (-1, -1), (-2, 1), (3, -1))] * 2, empty=3, h=3.0, no_diag=1.0, r=5),
+        clever_family("cg_h0", "nnz(H) = 0", 60, 63, singles=20, pow2=[P((0, 1), (-1, -1))] * 5 + [P((1, 1), (0, -1), (-1, 1))] * 2
+                      + [P((0, 1), (1, 1), (2, -1), (-1, 1), (-2, -1))], empty=2, empty_cols=3, h=0),
+    ]
+    rng = np.random.default_rng(64)
+    a = _vals(rng, 1)[0]
+    out.append(CleverDesign("cg_n1m2", "n = 1, m = 2, the two rows parallel: m_new = 1", sp.csc_matrix(np.array([[_vals(rng, 1)[0]]])),
+                            sp.csc_matrix(np.array([[a], [-2.0 * a]])), *_sy(rng, 2), groups=[([0, 1], [1.0, -2.0])]))
+    # the existing designs, as they are: random rows, so every group is a singleton (the empty rows of b8 merge); m = 0
+    for name in ("b8", "b64", "jc64_tiny", "m0"):
+        d = DESIGNS[name]
+        out.append(CleverDesign(name, d.why, d.H, d.J, d.s, d.y, groups=singleton_groups(d)))
+    return out
+
+
+CLEVER_DESIGNS = {d.name: d for d in _clever_list()}
+RESCALES = ("none", "u_only", "u_and_x")

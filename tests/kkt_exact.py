@@ -224,9 +224,159 @@ def kkt_error_exact(H, J, s, y, delta, dx, dy, ds, rD, rP, rC):
     return (eD, np.array(bD)), (eP, np.array(bP)), (eM, np.array(bM))
 
 
+def assert_within(r, what):
+    """Every err / bound of r is at most 1."""
+    assert len(r) == 0 or np.max(r) <= 1.0, (what, float(np.max(r)), int(np.argmax(r)))
+
+
+def check_err(res, d, tag, delta):
+    """The N err record res[tag/err] of a case runner against kkt_error_exact of its own dx, dy, ds and rhs at design d and delta:
+    the three maxima within their bounds, rhs_norm, overall and ratio exactly.  Returns kkt_error_exact's blocks."""
+    dx, dy, ds, rD, rP, rC = (res[f"{tag}/{k}"] for k in ("dx", "dy", "ds", "rD", "rP", "rC"))
+    eD, eP, eM = kkt_error_exact(d.H, d.J, d.s, d.y, delta, dx, dy, ds, rD, rP, rC)
+    got = res[f"{tag}/err"]
+    for g, e, what in zip(got[:3], (eD, eP, eM), ("error_D", "error_P", "error_mu")):
+        assert max_ratio(g, e) <= 1.0, (tag, what, g)
+    inf = lambda v: float(np.max(np.abs(v))) if len(v) else 0.0
+    assert got[4] == max(inf(rD), inf(rP), inf(rC))          # rhs_norm: maxima are exact
+    assert got[3] == max(got[:3]) and got[5] == got[3] / got[4]
+    return eD, eP, eM
+
+
 def max_ratio(got, e_b):
     """err / bound of a device maximum against the exact |e_i| with per-component bounds b_i: |max_i |e^_i| - max_i |e_i|| <= max_i b_i."""
     e, b = e_b
     if len(e) == 0:
         return 0.0 if got == 0.0 else math.inf
     return _ratio(got, max(e), float(np.max(b)) / SLACK)
+
+
+# ---- the clever-symmetric kind (clever_symmetric.jl) -----------------------------------------------------------------------------
+# groups: [(members in ls order, their ratios to the leader)] sorted by leader, as kkt_designs.CleverDesign holds them.  u = fl(s / y)
+# is an input (IEEE division: bitwise the device's), 1 / u is a rounding of the path.
+def _sqrt_frac(x):
+    """sqrt of a positive Fraction as a Fraction, from math.isqrt: relative error below 2^-250, far inside SLACK."""
+    k = 300 + x.denominator.bit_length()
+    return Fraction(math.isqrt((x.numerator << (2 * k)) // x.denominator), 1 << k)
+
+
+def clever_u_exact(groups, u):
+    """Per group the exact U_g = 1 / sum_t ratio_t^2 (1 / u_t)."""
+    return [1 / sum((F(r) * F(r) / F(u[j]) for j, r in zip(mem, rat)), Fraction(0)) for mem, rat in groups]
+
+
+def clever_u_g_ratios(groups, u, gU, g):
+    """update_indicies! (k_clever_groups).  U_g: k positive terms, each 1 / u, ratio^2 and their product, k - 1 additions (fused or
+    not), one reciprocal: gamma_{k+3} U.  g_j = U_g ratio_j (1 / u_j) (g indexed by row) with the computed U, 1 / u and two products:
+    gamma_{k+6} |g_j| against the exact U."""
+    ex = clever_u_exact(groups, u)
+    rU, rg = [], []
+    for (mem, rat), U_, got in zip(groups, ex, gU):
+        k = len(mem)
+        rU.append(_ratio(got, U_, gamma(k + 3) * float(U_)))
+        for j, r in zip(mem, rat):
+            e = U_ * F(r) / F(u[j])
+            rg.append(_ratio(g[j], e, gamma(k + 6) * abs(float(e))))
+    return np.array(rU), np.array(rg)
+
+
+def clever_d_ratios(mode, mu, xinf, n, gU, D):
+    """diag_rescale (k_clever_rescale and the host's x scale) from the DEVICE's U_g: 1 (none; the x part of u_only), exactly;
+    1 / sqrt(1 + |x|_inf) and mu / sqrt(U_g) within gamma_4: the addition, the square root and the division taken as at most one
+    ulp each -- the bound does not rely on a correctly rounded device sqrt.  The exact root is a 2^-250 accurate Fraction."""
+    out = []
+    dx = _sqrt_frac(1 / (1 + F(xinf))) if mode == "u_and_x" else Fraction(1)
+    for i in range(n):
+        out.append(_ratio(D[i], dx, gamma(4) * float(dx) if mode == "u_and_x" else 0.0))
+    for g_, U_ in enumerate(gU):
+        e = Fraction(1) if mode == "none" else F(mu) / _sqrt_frac(F(U_))
+        out.append(_ratio(D[n + g_], e, 0.0 if mode == "none" else gamma(4) * float(e)))
+    return np.array(out)
+
+
+def clever_pattern(H, J, firsts):
+    """The lower pattern of M = [[H 0]; [J_new -U]], J_new = J[firsts, :]: per column j < n the row j itself if H has no diagonal
+    there, H's rows, then n + g for every leader row firsts[g] stored in column j of J, ascending; per column n + g its diagonal."""
+    H, J = H.tocsc(), J.tocsc()
+    H.sort_indices(); J.sort_indices()
+    n = J.shape[1]
+    grp = {int(r): g for g, r in enumerate(firsts)}
+    ptr, idx = [0], []
+    for j in range(n):
+        hr = [int(r) for r in H.indices[H.indptr[j]:H.indptr[j + 1]]]
+        idx += ([] if j in hr else [j]) + hr + sorted(n + grp[int(r)] for r in J.indices[J.indptr[j]:J.indptr[j + 1]] if int(r) in grp)
+        ptr.append(len(idx))
+    for g in range(len(firsts)):
+        idx.append(n + g); ptr.append(len(idx))
+    return np.array(ptr, np.int64), np.array(idx, np.int64)
+
+
+def clever_q_ratios(A, H, J, firsts, gU, D, xdiag="scaled"):
+    """Every stored entry of the device's Q = D M D (CSC, the pattern of clever_pattern) from the DEVICE's D and U_g: (D_i v) D_j with
+    v an entry of H, of a leader's J row or -U_g -- two products, no sum: gamma_2 |value|.  The x diagonal: xdiag = "scaled":
+    (D_j h_jj) D_j (after form_system, and after factor! with delta = 0); "true": H's diagonal, unscaled, bit for bit (after factor!
+    with delta != 0).  A diagonal entry that H does not store is exactly 0."""
+    A = A.tocsc()
+    n = J.shape[1]
+    Hd, Jd = sp.dok_matrix(H.tocsc()), sp.dok_matrix(J.tocsc())
+    out = []
+    for j in range(A.shape[1]):
+        for p in range(A.indptr[j], A.indptr[j + 1]):
+            i = int(A.indices[p])
+            if j >= n:
+                v = -float(gU[j - n])
+            elif i >= n:
+                v = float(Jd[int(firsts[i - n]), j])
+            else:
+                v = float(Hd.get((i, j), 0.0))
+            if i == j and j < n and xdiag == "true":
+                out.append(0.0 if A.data[p] == v and not (v == 0.0 and math.copysign(1.0, A.data[p]) < 0) else math.inf)
+                continue
+            e = F(D[i]) * F(v) * F(D[j])
+            out.append(_ratio(A.data[p], e, gamma(2) * abs(float(e))))
+    return np.array(out)
+
+
+def clever_symrhs_ratios(rP, rC, y, symrhs):
+    """symmetric_primal_rhs = rP + rC / y (k_clever_symrhs): a division and an addition, gamma_2 (|rP| + |rC / y|)."""
+    return np.array([_ratio(symrhs[i], F(rP[i]) + F(rC[i]) / F(y[i]), gamma(2) * (abs(rP[i]) + abs(rC[i] / y[i]))) for i in range(len(y))])
+
+
+def clever_crhs_ratios(groups, g, symrhs, crhs):
+    """crhs_g = sum_t g_t symrhs_t (k_clever_crhs) from the device's g and symrhs: k products summed, gamma_k sum |terms|."""
+    out = []
+    for (mem, _), got in zip(groups, crhs):
+        ex = sum((F(g[j]) * F(symrhs[j]) for j in mem), Fraction(0))
+        out.append(_ratio(got, ex, gamma(len(mem)) * sum(abs(g[j] * symrhs[j]) for j in mem)))
+    return np.array(out)
+
+
+def clever_unscale_ratios(sol, D, n, dx, v):
+    """dx, v = sol .* D (k_clever_unscale): one product, gamma_1 |value|."""
+    got = np.concatenate([dx, v])
+    return np.array([_ratio(got[i], F(sol[i]) * F(D[i]), gamma(1) * abs(sol[i] * D[i])) for i in range(len(got))])
+
+
+def clever_dy_terms(groups, u, symrhs, crhs, gU, v):
+    """Per row j the two exact terms of dy_j = (1 / u_j) symrhs_j + ((1 / u_j) ratio_j) (-(crhs_g + U_g v_g)) and the sum of the
+    absolute values the bound takes (|crhs| + |U v| inside the second)."""
+    t = {}
+    for g_, (mem, rat) in enumerate(groups):
+        br = -(F(crhs[g_]) + F(gU[g_]) * F(v[g_]))
+        ab = abs(crhs[g_]) + abs(gU[g_] * v[g_])
+        for j, r in zip(mem, rat):
+            t[j] = (F(symrhs[j]) / F(u[j]), F(r) / F(u[j]) * br, abs(symrhs[j] / u[j]) + abs(r / u[j]) * ab)
+    return t
+
+
+def clever_dy_ratios(groups, u, symrhs, crhs, gU, v, dy):
+    """dir.y (k_clever_y) from the device's own inputs: 1 / u, the product U v, its sum with crhs, three more products and the last
+    sum -- no value passes more than six roundings: gamma_6 times the sum of the absolute values of the two terms."""
+    t = clever_dy_terms(groups, u, symrhs, crhs, gU, v)
+    assert sorted(t) == list(range(len(dy))), "a row that no group lists"
+    return np.array([_ratio(dy[j], t[j][0] + t[j][1], gamma(6) * t[j][2]) for j in range(len(dy))])
+
+
+def ds_ratios(J, dx, rP, ds):
+    """ds = J dx - rP from the device's dx, as dyds_ratios' non-direct branch."""
+    return np.array([_ratio(ds[i], e - F(rP[i]), gamma(k + 1) * (ab + abs(rP[i]))) for i, (e, ab, k) in enumerate(dots(J, dx))])
