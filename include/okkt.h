@@ -280,6 +280,31 @@ int okkt_schur_condense_dev(okkt_handle h, const double* d_rhs, double* d_r2, in
  * condense call.  rhs may alias x. */
 int okkt_schur_expand(okkt_handle h, const double* rhs, const double* x2, double* x, int64_t nrhs);
 int okkt_schur_expand_dev(okkt_handle h, const double* d_rhs, const double* d_x2, double* d_x, int64_t nrhs);
+/* ---- the dense factor of S ----
+ * Factor S on the device with Bunch-Kaufman partial pivoting: P S P' = L D L', L unit lower triangular, D block diagonal with 1 x 1 and
+ * 2 x 2 blocks (the pivot choice of LAPACK's dsytrf, lower variant).  S = NULL factors the S that the last okkt_factor_schur assembled
+ * (which stays intact: okkt_get_schur returns it afterwards); a non-NULL S is the caller's symmetric ns x ns column-major matrix, of
+ * which the lower triangle is read, ld >= ns -- the summed S of a decomposition.  inertia_S: the counts over D (a 2 x 2 block is one
+ * positive and one negative pivot; a column that is exactly zero when its turn comes is a zero pivot and is skipped).  inertia_total:
+ * A11's counts of the last okkt_factor_schur plus S's, by Haynsworth additivity the inertia of the whole matrix (A11's part is zero
+ * before any okkt_factor_schur).  Either may be NULL.  Returns 1 when D has neither a zero nor a non-finite pivot, 0 otherwise, < 0 on
+ * error.  Refused with OKKT_ERR_INVALID: no Schur set, S = NULL before a complete okkt_factor_schur, ld < ns. */
+int okkt_schur_factor(okkt_handle h, const double* S_or_NULL, int64_t ld, okkt_inertia* inertia_S, okkt_inertia* inertia_total);
+/* the same with S in device memory */
+int okkt_schur_factor_dev(okkt_handle h, const double* d_S_or_NULL, int64_t ld, okkt_inertia* inertia_S, okkt_inertia* inertia_total);
+/* The solves below are refused with OKKT_ERR_INVALID until okkt_schur_factor has succeeded, and again after a new okkt_factor_schur
+ * when the factor is of the handle's own S (a factor of a caller's S stays valid).  After a factor with zero or non-finite pivots
+ * they run and return what the divisions give, as okkt_solve does after such a factor of A.
+ * x2 = S^-1 r2 (ns x nrhs each, idx order); r2 may alias x2. */
+int okkt_schur_dense_solve(okkt_handle h, const double* r2, double* x2, int64_t nrhs);
+int okkt_schur_dense_solve_dev(okkt_handle h, const double* d_r2, double* d_x2, int64_t nrhs);
+/* A x = b for the whole matrix (dim x nrhs, original order): one forward sweep over the interior, the dense solve, the backward sweep.
+ * It needs a complete okkt_factor_schur besides the dense factor.  rhs may alias sol. */
+int okkt_schur_solve(okkt_handle h, const double* rhs, double* sol, int64_t nrhs);
+int okkt_schur_solve_dev(okkt_handle h, const double* d_rhs, double* d_sol, int64_t nrhs);
+/* The factor as dsytrf(uplo = 'L') returns it: LD (ns x ns column-major, ld >= ns; the strict upper triangle is set to zero) and
+ * ipiv[ns], 1-based, a 2 x 2 block at columns k, k + 1 marked by ipiv[k] = ipiv[k + 1] = -(row interchanged with k + 1). */
+int okkt_schur_get_factor(okkt_handle h, double* LD, int64_t ld, int32_t* ipiv);
 /* ---- Selected inversion: entries of F^-1 on the pattern of the factor ----------------------------------
  * F is the matrix the handle factored (as for okkt_condest: the values plus the factorisation's diagonal shift).  okkt_selinv computes
  * Z = F^-1 = L^-T D^-1 L^-1 at every entry of the stored supernodal pattern of L (relaxation zeros included) and at the diagonal, on

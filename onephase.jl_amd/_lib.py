@@ -231,6 +231,13 @@ SIGNATURES = {
     "okkt_schur_condense_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64]),
     "okkt_schur_expand": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64]),
     "okkt_schur_expand_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64]),
+    "okkt_schur_factor": (C.c_int, [_vp, _f64p, C.c_int64, C.POINTER(OkktInertia), C.POINTER(OkktInertia)]),
+    "okkt_schur_factor_dev": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(OkktInertia), C.POINTER(OkktInertia)]),
+    "okkt_schur_dense_solve": (C.c_int, [_vp, _f64p, _f64p, C.c_int64]),
+    "okkt_schur_dense_solve_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64]),
+    "okkt_schur_solve": (C.c_int, [_vp, _f64p, _f64p, C.c_int64]),
+    "okkt_schur_solve_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64]),
+    "okkt_schur_get_factor": (C.c_int, [_vp, _f64p, C.c_int64, C.POINTER(C.c_int32)]),
     "okkt_selinv": (C.c_int, [_vp, C.POINTER(OkktSelinvInfo)]),
     "okkt_get_inverse_diag": (C.c_int, [_vp, _f64p]),
     "okkt_get_inverse_diag_dev": (C.c_int, [_vp, _vp]),

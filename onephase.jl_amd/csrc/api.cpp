@@ -83,6 +83,7 @@ int solver_factor_device(okkt_solver_s* h, const double* d_vals, int64_t n, int6
   okkt_inertia in;
   in.pos = (int64_t)cnt[0]; in.neg = (int64_t)cnt[1]; in.zero = (int64_t)cnt[2]; in.nonfinite = (int64_t)cnt[3];
   if (out) *out = in;
+  h->a11_inertia = in;
   h->last_failed = true;
   if (h->N.early_exited || cnt[4] != 0) return 0;   // wrong inertia decided before the end: counts are partial, no factor to solve with
   h->factored = true;
@@ -132,6 +133,7 @@ void solver_refine_release(okkt_solver_s* h) {
   condest_release(h->cd);
   selinv_release(h->sl);
   krylov_release(h->kr);
+  dense_ldlt_release(h->dl);
   h->cd_hist.clear();
   if (h->rf_work) (void)hipFree(h->rf_work);
   if (h->rf_om) (void)hipFree(h->rf_om);
@@ -1026,7 +1028,7 @@ int okkt_analyze(okkt_handle h, int64_t dim, const int64_t* colptr, const int64_
     if (h->opts.ordering == 2 && (int64_t)h->user_perm.size() != dim)
       return solver_set_error(h, OKKT_ERR_INVALID, "ordering=user: okkt_set_perm must supply dim entries first");
     auto t0 = std::chrono::steady_clock::now();
-    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned || h->kr.V)) {   // the refinement map (and Z) belong to the old pattern
+    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned || h->kr.V || h->dl.F)) {   // the refinement map (and Z) belong to the old pattern
       (void)hipSetDevice(h->device);
       (void)hipStreamSynchronize(h->stream);
       solver_refine_release(h);
@@ -1725,6 +1727,157 @@ int okkt_schur_expand(okkt_handle h, const double* rhs, const double* x2, double
     return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_expand");
   }
 }
+
+// ---- the dense factor of the Schur complement (dense_ldlt.hip) -------------------------------------------
+
+// a factor to solve with: made by okkt_schur_factor and, when it is of the handle's own S, not older than the last okkt_factor_schur
+static int schur_dense_ready(okkt_solver_s* h) {
+  if (!h->dl.valid) return solver_set_error(h, OKKT_ERR_INVALID, "no okkt_schur_factor has succeeded on this handle");
+  if (h->dl.own && h->dl.factor_seq != h->factor_seq)
+    return solver_set_error(h, OKKT_ERR_INVALID, "S has been assembled again since okkt_schur_factor: call okkt_schur_factor again");
+  return OKKT_OK;
+}
+
+// S (host or device memory, NULL: the handle's own) into the factor's buffer, the factorisation, the two inertias
+static int schur_factor_impl(okkt_solver_s* h, const double* S, int64_t ld, bool on_device, okkt_inertia* inertia_S, okkt_inertia* inertia_total) {
+  int rc = schur_ready(h, S == nullptr);
+  if (rc != OKKT_OK) return rc;
+  const int64_t ns = h->S.nschur;
+  if (S && ld < ns) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_schur_factor: ld < ns");
+  h->dl.valid = false;
+  std::string e = dense_ldlt_alloc(h->dl, ns);
+  if (!e.empty()) return solver_set_error(h, OKKT_ERR_ALLOC, "dense Schur factor allocation failed: " + e);
+  if (!S) {
+    schur_export_enqueue(h->N, h->dl.F, ns);
+  } else if (hipMemcpy2DAsync(h->dl.F, (size_t)ns * sizeof(double), S, (size_t)ld * sizeof(double), (size_t)ns * sizeof(double), (size_t)ns,
+                              on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+    return solver_set_error(h, OKKT_ERR_HIP, "okkt_schur_factor: the copy of S failed");
+  }
+  if (!(e = dense_ldlt_factor(h->dl, h->stream)).empty()) return solver_set_error(h, OKKT_ERR_HIP, "dense Schur factorisation failed: " + e);
+  h->dl.own = S == nullptr;
+  h->dl.factor_seq = h->factor_seq;
+  okkt_inertia in;
+  in.pos = h->dl.cnt[0]; in.neg = h->dl.cnt[1]; in.zero = h->dl.cnt[2]; in.nonfinite = h->dl.cnt[3];
+  if (in.pos + in.neg + in.zero + in.nonfinite != ns) {
+    h->dl.valid = false;
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "pivot counts of the dense factor do not add up to ns");
+  }
+  if (inertia_S) *inertia_S = in;
+  if (inertia_total) {
+    const okkt_inertia a = h->factored ? h->a11_inertia : okkt_inertia{0, 0, 0, 0};
+    inertia_total->pos = a.pos + in.pos; inertia_total->neg = a.neg + in.neg;
+    inertia_total->zero = a.zero + in.zero; inertia_total->nonfinite = a.nonfinite + in.nonfinite;
+  }
+  return (in.zero == 0 && in.nonfinite == 0) ? 1 : 0;
+}
+
+int okkt_schur_factor(okkt_handle h, const double* S, int64_t ld, okkt_inertia* inertia_S, okkt_inertia* inertia_total) {
+  if (!h) return OKKT_ERR_INVALID;
+  try {
+    return schur_factor_impl(h, S, ld, false, inertia_S, inertia_total);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_factor");
+  }
+}
+
+int okkt_schur_factor_dev(okkt_handle h, const double* d_S, int64_t ld, okkt_inertia* inertia_S, okkt_inertia* inertia_total) {
+  if (!h) return OKKT_ERR_INVALID;
+  try {
+    return schur_factor_impl(h, d_S, ld, true, inertia_S, inertia_total);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_factor_dev");
+  }
+}
+
+int okkt_schur_get_factor(okkt_handle h, double* LD, int64_t ld, int32_t* ipiv) {
+  if (!h || !LD || !ipiv) return OKKT_ERR_INVALID;
+  try {
+    int rc = schur_ready(h, false);
+    if (rc == OKKT_OK) rc = schur_dense_ready(h);
+    if (rc != OKKT_OK) return rc;
+    const int64_t ns = h->S.nschur;
+    if (ld < ns) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_schur_get_factor: ld < ns");
+    std::vector<int> piv((size_t)ns);
+    (void)hipStreamSynchronize(h->stream);
+    if (hipMemcpy2D(LD, (size_t)ld * sizeof(double), h->dl.F, (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), (size_t)ns, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(piv.data(), h->dl.ipiv, (size_t)ns * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "dense Schur factor download failed");
+    for (int64_t j = 0; j < ns; ++j) {
+      ipiv[j] = piv[j];
+      for (int64_t i = 0; i < j; ++i) LD[j * ld + i] = 0.0;
+    }
+    // the device keeps every interchange applied to every column of L; dsytrf applies to a column only the interchanges made before
+    // it was eliminated: undo the later ones, last first (the end of dlasyf does the same for its panel)
+    for (int64_t j = ns - 1; j > 0;) {
+      const int64_t jj = j;                    // row interchanged with jp by the pivot block that ends at column j
+      int64_t jp = piv[j];
+      if (jp < 0) { jp = -jp; --j; }           // a 2 x 2 block: j is its first column now
+      --jp;
+      if (jp != jj) for (int64_t c = 0; c < j; ++c) std::swap(LD[c * ld + jj], LD[c * ld + jp]);
+      --j;
+    }
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_get_factor");
+  }
+}
+
+// batches of up to kMaxRhs right-hand sides; whole: the fused whole-system solve (rhs and sol of order dim), else x2 = S^-1 r2
+static int schur_dense_sweeps(okkt_solver_s* h, const double* d_rhs, double* d_sol, int64_t nrhs, bool whole) {
+  const int64_t n = h->S.n, ns = h->S.nschur;
+  double* t2 = h->dl.X + 8 * ns;      // r2 / x2 of the fused solve
+  for (int64_t r = 0; r < nrhs;) {
+    const int nr = (int)std::min<int64_t>(nrhs - r, kMaxRhs);
+    const int R = nr >= 3 ? 4 : nr;
+    std::string e;
+    if (whole) {
+      solve_permute_in(h->N, d_rhs + r * n, n, nr, R);
+      e = solve_fwd_enqueue(h->N, 0, R);
+      if (e.empty()) e = schur_gather_enqueue(h->N, t2, nr, R);
+      if (e.empty()) e = dense_ldlt_solve_enqueue(h->dl, t2, t2, nr, R, h->stream);
+      if (e.empty()) e = schur_put_enqueue(h->N, t2, nr, R);
+      if (e.empty()) e = solve_bwd_enqueue(h->N, 0, R);
+      if (e.empty()) solve_permute_out(h->N, d_sol + r * n, n, nr, R, false);
+    } else {
+      e = dense_ldlt_solve_enqueue(h->dl, d_rhs + r * ns, d_sol + r * ns, nr, R, h->stream);
+    }
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
+    r += nr;
+  }
+  return schur_sync(h, whole ? "Schur solve" : "dense Schur solve");
+}
+
+static int schur_dense_solve_impl(okkt_solver_s* h, const double* rhs, double* sol, int64_t nrhs, bool whole, bool on_device) {
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  if (nrhs > 0 && (!rhs || !sol)) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+  int rc = schur_ready(h, whole);
+  if (rc == OKKT_OK) rc = schur_dense_ready(h);
+  if (rc != OKKT_OK) return rc;
+  if (on_device) return schur_dense_sweeps(h, rhs, sol, nrhs, whole);
+  const int64_t len = (whole ? h->S.n : h->S.nschur) * nrhs;
+  if (len == 0) return OKKT_OK;
+  if ((rc = rhs_stage(h, len)) != OKKT_OK) return rc;
+  if (hipMemcpyAsync(h->d_rhs_stage, rhs, (size_t)len * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess)
+    return solver_set_error(h, OKKT_ERR_HIP, "rhs upload failed");
+  if ((rc = schur_dense_sweeps(h, h->d_rhs_stage, h->d_rhs_stage, nrhs, whole)) != OKKT_OK) return rc;
+  if (hipMemcpy(sol, h->d_rhs_stage, (size_t)len * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, "solution download failed");
+  return OKKT_OK;
+}
+
+#define OKKT_SCHUR_SOLVE_ENTRY(name, whole, on_device)                                            \
+  int name(okkt_handle h, const double* rhs, double* sol, int64_t nrhs) {                         \
+    if (!h) return OKKT_ERR_INVALID;                                                              \
+    try {                                                                                         \
+      return schur_dense_solve_impl(h, rhs, sol, nrhs, whole, on_device);                         \
+    } catch (...) {                                                                               \
+      return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in " #name);            \
+    }                                                                                             \
+  }
+OKKT_SCHUR_SOLVE_ENTRY(okkt_schur_dense_solve, false, false)
+OKKT_SCHUR_SOLVE_ENTRY(okkt_schur_dense_solve_dev, false, true)
+OKKT_SCHUR_SOLVE_ENTRY(okkt_schur_solve, true, false)
+OKKT_SCHUR_SOLVE_ENTRY(okkt_schur_solve_dev, true, true)
+#undef OKKT_SCHUR_SOLVE_ENTRY
 
 // ---- selected inversion (selinv.hip) --------------------------------------------------------------------
 

@@ -276,6 +276,10 @@ void numeric_sum_counts_device(Numeric& N, long long* d_out4);
 // expand: the forward sweep over the interior, x2 (ns x nr) into the Schur columns of xwork, the backward sweep over the interior
 std::string schur_condense_enqueue(Numeric& N, double* d_r2, int nr, int R);
 std::string schur_expand_enqueue(Numeric& N, const double* d_x2, int nr, int R);
+// their two ends on their own (the fused solve of section 8.7 runs the dense solve between them and each sweep once): the gather
+// behind a forward sweep, the put in front of a backward sweep
+std::string schur_gather_enqueue(Numeric& N, double* d_r2, int nr, int R);
+std::string schur_put_enqueue(Numeric& N, const double* d_x2, int nr, int R);
 // S (lower triangle of the assembled Schur front) -> d_S full and symmetric, leading dimension ld
 void schur_export_enqueue(Numeric& N, double* d_S, int64_t ld);
 // enqueue forward/diagonal/backward solves for the R right-hand sides already stored (permuted) in d.xwork

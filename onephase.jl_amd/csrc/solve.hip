@@ -1706,9 +1706,7 @@ std::string solve_bwd_enqueue(Numeric& N, int which, int R) {
   return sweep_which(N, false, which, R);
 }
 
-std::string schur_condense_enqueue(Numeric& N, double* d_r2, int nr, int R) {
-  std::string e = solve_fwd_enqueue(N, 0, R);
-  if (!e.empty()) return e;
+std::string schur_gather_enqueue(Numeric& N, double* d_r2, int nr, int R) {
   const int ns = N.sn_k[N.schur_sn], col0 = N.d.n - ns;
   const dim3 g((ns + 255) / 256), b(256);
   if (R == 1) hipLaunchKernelGGL(k_schur_gather<1>, g, b, 0, N.stream, N.d, N.schur_gcb, col0, ns, nr, d_r2);
@@ -1718,15 +1716,26 @@ std::string schur_condense_enqueue(Numeric& N, double* d_r2, int nr, int R) {
   return "";
 }
 
-std::string schur_expand_enqueue(Numeric& N, const double* d_x2, int nr, int R) {
-  std::string e = solve_fwd_enqueue(N, 0, R);
-  if (!e.empty()) return e;
+std::string schur_put_enqueue(Numeric& N, const double* d_x2, int nr, int R) {
   const int ns = N.sn_k[N.schur_sn], col0 = N.d.n - ns;
   const dim3 g((ns + 255) / 256), b(256);
   if (R == 1) hipLaunchKernelGGL(k_schur_put<1>, g, b, 0, N.stream, N.d, col0, ns, nr, d_x2);
   else if (R == 2) hipLaunchKernelGGL(k_schur_put<2>, g, b, 0, N.stream, N.d, col0, ns, nr, d_x2);
   else hipLaunchKernelGGL(k_schur_put<4>, g, b, 0, N.stream, N.d, col0, ns, nr, d_x2);
   OKKT_HIP_TRY(hipGetLastError());
+  return "";
+}
+
+std::string schur_condense_enqueue(Numeric& N, double* d_r2, int nr, int R) {
+  std::string e = solve_fwd_enqueue(N, 0, R);
+  if (!e.empty()) return e;
+  return schur_gather_enqueue(N, d_r2, nr, R);
+}
+
+std::string schur_expand_enqueue(Numeric& N, const double* d_x2, int nr, int R) {
+  std::string e = solve_fwd_enqueue(N, 0, R);
+  if (!e.empty()) return e;
+  if (!(e = schur_put_enqueue(N, d_x2, nr, R)).empty()) return e;
   return solve_bwd_enqueue(N, 0, R);
 }
 

@@ -7,6 +7,7 @@
 
 #include "../../include/okkt.h"
 #include "condest.h"
+#include "dense_ldlt.h"
 #include "krylov.h"
 #include "numeric.h"
 #include "refine.h"
@@ -69,6 +70,10 @@ struct okkt_solver_s {
   // GMRES-based refinement (krylov.hip): the basis and the vectors of one group of right-hand sides, allocated on the first
   // okkt_solve_gmres after an analysis (grown for a larger restart) and released with the refinement map
   okkt::KrylovWork kr;
+  // dense factor of the Schur complement (dense_ldlt.hip): allocated by the first okkt_schur_factor after an
+  // analysis and released with the refinement map; the pivot counts of the last okkt_factor_schur (A11's) for the whole-matrix inertia
+  okkt::DenseLdltWork dl;
+  okkt_inertia a11_inertia = {0, 0, 0, 0};
 };
 
 namespace okkt {

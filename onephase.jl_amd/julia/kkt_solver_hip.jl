@@ -252,3 +252,44 @@ function compute_directions!(k::HIP_KKT_solver, etas::Vector{Class_reduction_fac
     end
     return out
 end
+
+# ---- the dense factor of the Schur complement (DESIGN.md section 8.7) on a linear_solver_HIP in Schur mode (okkt_set_schur before the
+# analysis, okkt_factor_schur before these).  UNTESTED like the rest of this file.  Inertias come back as (pos, neg, zero, nonfinite).
+struct OkktInertiaCounts    # okkt_inertia of include/okkt.h
+    pos::Int64
+    neg::Int64
+    zero::Int64
+    nonfinite::Int64
+end
+
+# P S P' = L D L' with Bunch-Kaufman pivoting; S === nothing: the S the handle assembled, else a symmetric ns x ns matrix (lower triangle
+# read).  Returns (flag, inertia of S, inertia of the whole matrix); flag 1: no zero and no non-finite pivot
+function schur_factor(solver::linear_solver_HIP, S::Union{Nothing,Array{Float64,2}}=nothing)
+    si = Ref(OkktInertiaCounts(0, 0, 0, 0)); ti = Ref(OkktInertiaCounts(0, 0, 0, 0))
+    rc = ccall((:okkt_schur_factor, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{OkktInertiaCounts}, Ref{OkktInertiaCounts}),
+               solver.handle, S === nothing ? C_NULL : pointer(S), S === nothing ? 0 : size(S, 1), si, ti)
+    rc < 0 && okkt_error(solver, "okkt_schur_factor", rc)
+    return rc, si[], ti[]
+end
+
+# x2 = S^-1 r2 (set order); r2 may be x2
+function schur_dense_solve(solver::linear_solver_HIP, r2::Array{Float64,1}, x2::Array{Float64,1})
+    rc = ccall((:okkt_schur_dense_solve, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64), solver.handle, r2, x2, 1)
+    rc < 0 && okkt_error(solver, "okkt_schur_dense_solve", rc)
+    return x2
+end
+
+# A sol = rhs for the whole matrix: one forward sweep over the interior, the dense solve, the backward sweep; rhs may be sol
+function schur_solve(solver::linear_solver_HIP, my_rhs::Array{Float64,1}, my_sol::Array{Float64,1})
+    rc = ccall((:okkt_schur_solve, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64), solver.handle, my_rhs, my_sol, 1)
+    rc < 0 && okkt_error(solver, "okkt_schur_solve", rc)
+    return my_sol
+end
+
+# (LD, ipiv) in the layout and convention of LAPACK.sytrf!('L', S)
+function schur_get_factor(solver::linear_solver_HIP, ns::Integer)
+    LD = zeros(ns, ns); ipiv = zeros(Int32, ns)
+    rc = ccall((:okkt_schur_get_factor, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int32}), solver.handle, LD, ns, ipiv)
+    rc < 0 && okkt_error(solver, "okkt_schur_get_factor", rc)
+    return LD, ipiv
+end

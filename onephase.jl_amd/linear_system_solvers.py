@@ -68,6 +68,8 @@ class linear_solver_HIP(abstract_linear_system_solver):
         self.inertia = None  # (pos, neg, zero, nonfinite) of the last factorisation
         self._dim = 0
         self._ns = 0  # Schur set size (set_schur)
+        self.schur_inertia = None  # counts over D of the last schur_factor
+        self.total_inertia = None  # A11's counts + S's: the whole matrix's
         self._borrowed = False  # a view on a handle another object owns (of_kkt): finalize does not destroy it
 
     # -- initialize! / finalize!
@@ -435,6 +437,64 @@ class linear_solver_HIP(abstract_linear_system_solver):
     def schur_expand_dev(self, d_rhs, d_x2, d_x, nrhs=1):
         self._need()
         self._check(self._lib.okkt_schur_expand_dev(self._h, C.c_void_p(d_rhs), C.c_void_p(d_x2), C.c_void_p(d_x), int(nrhs)), "okkt_schur_expand_dev")
+
+    # -- the dense factor of S: Bunch-Kaufman L D L' on the device
+    def _schur_factor(self, fn, what, S, ld):
+        self._need()
+        si, ti = L.OkktInertia(), L.OkktInertia()
+        rc = self._check(fn(self._h, S, int(ld), C.byref(si), C.byref(ti)), what)
+        self.schur_inertia = si.as_tuple()
+        self.total_inertia = ti.as_tuple()
+        return int(rc)
+
+    def schur_factor(self, S=None):
+        """Factor S with pivoting: the assembled S of the last ls_factor_schur, or a symmetric ns x ns array (its lower triangle is
+        read).  1 when no pivot is zero or non-finite, else 0; sets schur_inertia (S's counts) and total_inertia (A11's + S's)."""
+        if S is None:
+            return self._schur_factor(self._lib.okkt_schur_factor, "okkt_schur_factor", None, self._ns)
+        A = L.f64(np.asarray(S, dtype=np.float64).T)      # column-major for the library
+        if A.shape != (self._ns, self._ns):
+            raise OkktError(f"S must be {self._ns} x {self._ns}")
+        return self._schur_factor(self._lib.okkt_schur_factor, "okkt_schur_factor", L.p_f64(A), self._ns)
+
+    def schur_factor_dev(self, d_S=None, ld=None):
+        return self._schur_factor(self._lib.okkt_schur_factor_dev, "okkt_schur_factor_dev", None if d_S is None else C.c_void_p(d_S),
+                                  self._ns if ld is None else ld)
+
+    def schur_dense_solve(self, r2):
+        """x2 = S^-1 r2 with the factor of schur_factor; r2: a vector of ns or one right-hand side per row, set order."""
+        self._need()
+        B, single = self._rhs_block(r2, self._ns)
+        X = np.zeros_like(B)
+        self._check(self._lib.okkt_schur_dense_solve(self._h, L.p_f64(B), L.p_f64(X), B.shape[0]), "okkt_schur_dense_solve")
+        return X[0] if single else X
+
+    def schur_dense_solve_dev(self, d_r2, d_x2, nrhs=1):
+        self._need()
+        self._check(self._lib.okkt_schur_dense_solve_dev(self._h, C.c_void_p(d_r2), C.c_void_p(d_x2), int(nrhs)), "okkt_schur_dense_solve_dev")
+
+    def schur_solve(self, rhs):
+        """x with A x = rhs for the whole matrix: one forward sweep over the interior, the dense solve with the factor of S, the
+        backward sweep; rhs as in schur_condense."""
+        self._need()
+        B, single = self._rhs_block(rhs, self._dim)
+        X = np.zeros_like(B)
+        self._check(self._lib.okkt_schur_solve(self._h, L.p_f64(B), L.p_f64(X), B.shape[0]), "okkt_schur_solve")
+        return X[0] if single else X
+
+    def schur_solve_dev(self, d_rhs, d_sol, nrhs=1):
+        self._need()
+        self._check(self._lib.okkt_schur_solve_dev(self._h, C.c_void_p(d_rhs), C.c_void_p(d_sol), int(nrhs)), "okkt_schur_solve_dev")
+
+    def schur_get_factor(self):
+        """(LD, ipiv) as LAPACK's dsytrf(lower) returns them: LD[i, j] with unit L below the diagonal and D on it, ipiv 1-based with
+        negative pairs for the 2 x 2 blocks."""
+        self._need()
+        ns = self._ns
+        LD = np.zeros((ns, ns))
+        ipiv = np.zeros(ns, dtype=np.int32)
+        self._check(self._lib.okkt_schur_get_factor(self._h, L.p_f64(LD), ns, ipiv.ctypes.data_as(C.POINTER(C.c_int32))), "okkt_schur_get_factor")
+        return np.ascontiguousarray(LD.T), ipiv
 
     # -- selected inversion: entries of F^-1 on the pattern of the factor (not part of the reference interface; DESIGN.md section 8.5)
     @classmethod
