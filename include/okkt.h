@@ -341,9 +341,63 @@ int okkt_get_inverse_csc(okkt_handle h, int64_t* colptr, int64_t* rowval, double
  * complete factorisation (not okkt_selinv); same refusals otherwise. */
 int okkt_logdet(okkt_handle h, double* logabsdet, int32_t* sign);
 
-/* diag(F): the D of LDL^T in pivot (permuted) order, as `diag(solver._factor)` (julia.jl:72) */
+/* ---- Symmetric equilibration before the factorisation ----------------------------------------------------
+ * The factorisation never pivots; with a scaling on, okkt_factor(_dev) factors F~ = S F S for a positive diagonal S = diag(s), so that
+ * the static-pivot LDL^T sees entries of comparable size.  Off by default; with OKKT_SCALE_NONE every call is bit for bit what it is
+ * without this section, with no additional launch and no allocation.
+ * The scaling (OKKT_SCALE_RUIZ).  A is the full symmetric matrix okkt_residual defines (lower triangle read, upper entries ignored,
+ * duplicates summed), with the diagonal shift the factorisation adds at assembly (okkt_kkt_factor's delta) added to the stored diagonal
+ * entries.  s starts at 1.  Each of the `sweeps` sweeps is a Jacobi update: for every row i, r_i = max_j ((|a_ij| * s_i) * s_j), all
+ * rows from the old s, the products rounded in exactly this order; entries that are not finite are skipped in the maximum; then
+ * s_i <- s_i / sqrt(r_i) (IEEE sqrt and division), except that a row whose r_i is 0 (or not finite) keeps its s_i.  After the last sweep
+ * each s_i = m 2^e with m in [1/2, 1) becomes 2^(e-1) when m < fl(sqrt(1/2)) = 0x1.6a09e667f3bcdp-1 and 2^e otherwise, the exponent
+ * clamped to [-510, 510] (an s_i that is not positive and finite becomes 1).  Ten sweeps by default: in the infinity norm the smallest
+ * row maximum roughly square-roots per sweep, so after ten even a spread of 1e-300 is within a few percent of 1 and the rounding then
+ * leaves every non-zero row maximum in (0.45, 2].  Scaling by powers of two is exact: the factor is bitwise the factor of the prescaled
+ * matrix and the inertia is that of F (Sylvester); a factorisation that never pivots is moreover invariant under an exact scaling, so the
+ * solutions of a RUIZ-scaled handle are bitwise those of an unscaled one while nothing leaves the exponent range: what the scaling changes
+ * is which pivots inertia_tol counts as zero (those of F~) and the range.  The sweeps run on the device with no host read between them; a maximum does not
+ * depend on the order it is taken in, so two calls give identical bits.
+ * OKKT_SCALE_USER takes the caller's vector as it is (not rounded): dim entries in the original order, all finite and > 0, read and
+ * copied by okkt_set_scaling, which therefore needs an analysed handle; the factor is then that of S F S up to two roundings per entry.
+ * okkt_factor(_dev) with a scaling on: computes s from the values of this factorisation (RUIZ) or takes the caller's (USER), writes
+ * v'_e = (s_row * v_e) * s_col for every input entry into a workspace of the handle -- the caller's nzval is never modified -- and
+ * factors the workspace by the unchanged numeric path.  Everything is enqueued on the handle's stream inside the timed span of
+ * last_factor_ms; the scaling adds no host synchronisation: its row-maximum extrema are read with the pivot counts at the end.  The
+ * flag, the inertia counts, inertia_tol, early exit and the 1 / 0 contract apply to the pivots of F~.  The first scaled factorisation
+ * after an analysis builds the row map of okkt_residual (if no call has yet) and a workspace of 16 B per input entry.
+ * The solve family: okkt_solve(_dev) returns x = S F~^-1 S b, the two multiplications inside the permutation gather and scatter the
+ * solve has anyway (no extra pass over the vectors).  okkt_solve_refine, okkt_solve_gmres, okkt_condest, okkt_forward_error and the KKT
+ * level's directions and estimates all solve through it: they see F^-1 of the unscaled matrix and keep their residuals and norms against
+ * the caller's unscaled nzval.
+ * Exports: okkt_get_diag and okkt_get_factor_csc return D~ and L~, the factor of S F S.  okkt_logdet returns log |det F| =
+ * log |det F~| - 2 ln 2 * sum_i e_i with s_i = 2^e_i, the e_i summed as integers (USER entries that are no power of two contribute
+ * -2 ln s_i); the sign is that of det F~.
+ * Refused with OKKT_ERR_INVALID and a message, the handle stays usable: a mode other than NONE on a handle in Schur mode or partitioned
+ * with nparts > 1; okkt_set_schur with ns > 0 and okkt_dist_set_partition with nparts > 1 while a scaling is on; okkt_selinv while the
+ * current factor is scaled; okkt_get_scaling(_dev) unless the handle holds a complete factorisation that used a scaling; an unknown
+ * mode, sweeps > 64, USER with a NULL vector, a non-finite or non-positive entry, or before okkt_analyze; a USER vector given for another
+ * dimension than the one analysed since (checked by the next factorisation).  On host_symbolic_only handles the setting is stored (it is
+ * configuration) and the getters return OKKT_ERR_NO_DEVICE.
+ * A re-analysis keeps the mode, the sweeps and a USER vector, and drops the computed scaling with the factor.  okkt_set_scaling itself
+ * does not touch the current factor: the scaling takes effect, or ends, with the next factorisation. */
+#define OKKT_SCALE_NONE 0   /* default */
+#define OKKT_SCALE_RUIZ 1   /* computed from the values of every factorisation */
+#define OKKT_SCALE_USER 2   /* the caller's vector, used as given */
+typedef struct {
+  int32_t mode, sweeps;           /* of the current factor (sweeps: 0 for USER) */
+  double rowmax_min, rowmax_max;  /* over the nonzero rows of |S F S| as factored (0 when every row is zero) */
+  int64_t zero_rows;              /* rows whose maximum is 0: they kept their s_i */
+} okkt_scaling_info;
+int okkt_set_scaling(okkt_handle h, int mode, int32_t sweeps /* RUIZ: 1..64, <= 0: 10 */,
+                     const double* s_user /* USER: [dim], original order, all finite and > 0; else NULL */);
+/* the scaling of the current factor */
+int okkt_get_scaling(okkt_handle h, double* s_out /* [dim], original order */, okkt_scaling_info* info /* or NULL */);
+int okkt_get_scaling_dev(okkt_handle h, double* d_s_out);
+
+/* diag(F): the D of LDL^T in pivot (permuted) order, as `diag(solver._factor)` (julia.jl:72); of a scaled factor (section 8.8): D~ */
 int okkt_get_diag(okkt_handle h, double* d_out /* [dim] */);
-/* L as CSC in permuted numbering (unit diagonal not stored), for parity tests; pass NULLs to size */
+/* L as CSC in permuted numbering (unit diagonal not stored), for parity tests; pass NULLs to size; of a scaled factor: L~ */
 int okkt_get_factor_csc(okkt_handle h, int64_t* colptr_out, int64_t* rowval_out, double* val_out, int64_t* nnz_out);
 
 /* device-memory helpers so that callers without a HIP binding (ctypes, Julia) can keep inputs in HBM */
@@ -532,6 +586,12 @@ int okkt_kkt_condest(okkt_kkt_handle k, int32_t t, okkt_condest_info* info);
  * refuse okkt_kkt_set_ls_refine. */
 int okkt_kkt_direction_error_bound(okkt_kkt_handle k, double* ferr);
 int okkt_kkt_get_dense_rows(okkt_kkt_handle k, int64_t* count_out, int64_t* rows_out /* [count] or NULL */);
+/* Schur, Schur-direct (with and without schur_dense_rows) and symmetric kinds: okkt_set_scaling on the level-1 handle, mode
+ * OKKT_SCALE_RUIZ or OKKT_SCALE_NONE.  Every okkt_kkt_factor, okkt_kkt_factor_trial and attempt of
+ * okkt_kkt_ipopt_strategy then computes the scaling from the shifted values it factors; directions, okkt_kkt_estimate_y_tilde,
+ * okkt_kkt_condest and okkt_kkt_direction_error_bound keep describing the unscaled system.  Refused with OKKT_ERR_INVALID: the
+ * clever-symmetric kind (it has okkt_kkt_set_rescale) and OKKT_SCALE_USER. */
+int okkt_kkt_set_ls_scaling(okkt_kkt_handle k, int mode, int32_t sweeps);
 
 /* ---- Clever_Symmetric only -------------------------------------------------------
  * initialize!(::Clever_Symmetric_KKT_solver, it) = compute_indicies(get_jac(it)) (clever_symmetric.jl:53-61,

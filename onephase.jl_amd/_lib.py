@@ -20,6 +20,10 @@ OKKT_KKT_SYMMETRIC = 1
 OKKT_KKT_CLEVER_SYMMETRIC = 2
 OKKT_KKT_SCHUR_DIRECT = 3
 OKKT_RESCALE = {"none": 0, "u_only": 1, "u_and_x": 2}
+OKKT_SCALE_NONE = 0
+OKKT_SCALE_RUIZ = 1
+OKKT_SCALE_USER = 2
+OKKT_SCALE = {"none": OKKT_SCALE_NONE, "ruiz": OKKT_SCALE_RUIZ, "user": OKKT_SCALE_USER}
 
 OKKT_OK = 0
 OKKT_ERR_INVALID = -1
@@ -190,6 +194,21 @@ class OkktSelinvInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktScalingInfo(C.Structure):
+    """okkt_scaling_info: mode and sweeps of the current factor's scaling, the extrema of the row maxima of |S F S| over its non-zero
+    rows, and the number of zero rows."""
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("sweeps", C.c_int32),
+        ("rowmax_min", C.c_double),
+        ("rowmax_max", C.c_double),
+        ("zero_rows", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/okkt.h declares, with its signature
 _i64p = C.POINTER(C.c_int64)
 _f64p = C.POINTER(C.c_double)
@@ -245,6 +264,9 @@ SIGNATURES = {
     "okkt_get_inverse_on_pattern_dev": (C.c_int, [_vp, _vp]),
     "okkt_get_inverse_csc": (C.c_int, [_vp, _i64p, _i64p, _f64p, _i64p]),
     "okkt_logdet": (C.c_int, [_vp, _f64p, C.POINTER(C.c_int32)]),
+    "okkt_set_scaling": (C.c_int, [_vp, C.c_int, C.c_int32, _f64p]),
+    "okkt_get_scaling": (C.c_int, [_vp, _f64p, C.POINTER(OkktScalingInfo)]),
+    "okkt_get_scaling_dev": (C.c_int, [_vp, _vp]),
     "okkt_get_diag": (C.c_int, [_vp, _f64p]),
     "okkt_get_factor_csc": (C.c_int, [_vp, _i64p, _i64p, _f64p, _i64p]),
     "okkt_dev_alloc": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp)]),
@@ -296,6 +318,7 @@ SIGNATURES = {
     "okkt_kkt_get_schur_diag": (C.c_int, [_vp, _f64p]),
     "okkt_kkt_get_dense_rows": (C.c_int, [_vp, _i64p, _i64p]),
     "okkt_kkt_set_ls_refine": (C.c_int, [_vp, C.c_int32, C.c_double]),
+    "okkt_kkt_set_ls_scaling": (C.c_int, [_vp, C.c_int, C.c_int32]),
     "okkt_kkt_condest": (C.c_int, [_vp, C.c_int32, C.POINTER(OkktCondestInfo)]),
     "okkt_kkt_direction_error_bound": (C.c_int, [_vp, _f64p]),
     "okkt_kkt_compute_indicies": (C.c_int, [_vp, _f64p, C.POINTER(C.c_int64)]),

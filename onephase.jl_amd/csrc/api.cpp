@@ -54,10 +54,35 @@ int solver_ensure_numeric(okkt_solver_s* h) {
   return OKKT_OK;
 }
 
+// A scaling is on: the refusals, the length of a caller's vector, and on the first scaled factorisation after
+// an analysis the row map of the pattern (the one the refinement calls build) and the workspace
+static int scaling_prepare(okkt_solver_s* h) {
+  ScalingWork& W = h->sc;
+  if (schur_mode(h)) return solver_set_error(h, OKKT_ERR_INVALID, "a scaling is set: Schur mode cannot factor a scaled matrix (okkt_set_scaling with OKKT_SCALE_NONE first)");
+  if (h->S.nparts > 1) return solver_set_error(h, OKKT_ERR_INVALID, "a scaling is set: a partitioned handle cannot factor a scaled matrix (okkt_set_scaling with OKKT_SCALE_NONE first)");
+  if (W.mode == OKKT_SCALE_USER && (int64_t)W.user.size() != h->S.n)
+    return solver_set_error(h, OKKT_ERR_INVALID, "the scaling vector of okkt_set_scaling was given for another dimension than the analysed one");
+  if (!h->rf.ready) {
+    std::string e = refine_map_build(h->S.n, h->pat_colptr.data(), h->pat_rowval.data(), h->pat_colptr[0], h->rf);
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, "scaling: row map: " + e);
+  }
+  if (!W.ready) {
+    std::string e = scaling_alloc(W, h->S.n, h->pat_colptr.data(), h->pat_rowval.data(), h->pat_colptr[0]);
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_ALLOC, "scaling workspace: " + e);
+  }
+  if (W.mode == OKKT_SCALE_USER && !W.user_uploaded && W.n > 0) {
+    hipError_t he = hipMemcpyAsync(W.s[0], W.user.data(), (size_t)W.n * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("scaling vector upload: ") + hipGetErrorString(he));
+    W.user_uploaded = true;
+  }
+  return OKKT_OK;
+}
+
 int solver_factor_device(okkt_solver_s* h, const double* d_vals, int64_t n, int64_t m, int sym_kind,
                          okkt_inertia* out, bool zero_tol) {
   int rc = solver_ensure_numeric(h);
   if (rc != OKKT_OK) return rc;
+  const bool scaled = h->sc.mode != OKKT_SCALE_NONE;
   const int64_t order = h->S.n - h->S.nschur;     // the pivots factored: A11's in Schur mode (its front is assembled, not factored)
   if (n < 0 || m < 0 || n + m != order) return solver_set_error(h, OKKT_ERR_INVALID, "n + m does not match the analysed dimension");
   if (sym_kind != OKKT_SYM_DEFINITE && sym_kind != OKKT_SYM_SYMMETRIC) return solver_set_error(h, OKKT_ERR_INVALID, "unknown sym_kind");
@@ -65,14 +90,29 @@ int solver_factor_device(okkt_solver_s* h, const double* d_vals, int64_t n, int6
   const double tol = (sym_kind == OKKT_SYM_DEFINITE || zero_tol) ? 0.0 : h->opts.inertia_tol;
   h->factored = false;
   ++h->factor_seq;     // a selected inverse of the previous factor is stale from here on
+  h->sc.valid = false;
+  if (scaled && (rc = scaling_prepare(h)) != OKKT_OK) return rc;     // (behind the argument checks: it may overwrite the previous factor's s)
   h->N.early_check = h->early_exit && h->S.nschur == 0;
   h->N.early_device = h->early_exit && h->last_failed;   // the previous factorisation failed the inertia: this one is a retry
   h->N.early_n = n;
   h->N.early_m = m;
   (void)hipEventRecord(h->ev0, h->stream);
-  std::string e = numeric_factor_enqueue(h->N, d_vals, tol);
+  std::string e;
+  double sc_out[kScaleOut] = {0.0, 0.0, 0.0, 0.0};
+  if (scaled) {
+    // s, then S F S into the workspace; the assembly adds the scaled shift.  The unscaled shift stays the handle's (okkt_condest reads it)
+    scaling_enqueue(h->sc, h->rf, d_vals, h->N.d.diagadd, h->N.d.perm, h->stream);
+    double* const shift = h->N.d.diagadd;
+    h->N.d.diagadd = h->sc.dadd;
+    e = numeric_factor_enqueue(h->N, h->sc.vals, tol);
+    h->N.d.diagadd = shift;
+  } else {
+    e = numeric_factor_enqueue(h->N, d_vals, tol);
+  }
   if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
   (void)hipEventRecord(h->ev1, h->stream);
+  if (scaled && h->sc.n > 0 && hipMemcpyAsync(sc_out, h->sc.out, sizeof(sc_out), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+    return solver_set_error(h, OKKT_ERR_HIP, "scaling: read of the row-maximum extrema failed");
   unsigned long long cnt[6];
   e = numeric_read_counts(h->N, h->stream, cnt);
   if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, std::string("numeric factorisation failed: ") + e);
@@ -87,6 +127,14 @@ int solver_factor_device(okkt_solver_s* h, const double* d_vals, int64_t n, int6
   h->last_failed = true;
   if (h->N.early_exited || cnt[4] != 0) return 0;   // wrong inertia decided before the end: counts are partial, no factor to solve with
   h->factored = true;
+  if (scaled) {
+    h->sc.valid = true;
+    h->sc.info.mode = h->sc.mode;
+    h->sc.info.sweeps = h->sc.mode == OKKT_SCALE_RUIZ ? h->sc.sweeps : 0;
+    h->sc.info.rowmax_min = sc_out[3] > 0.0 ? sc_out[0] : 0.0;
+    h->sc.info.rowmax_max = sc_out[1];
+    h->sc.info.zero_rows = (int64_t)sc_out[2];
+  }
   if (in.pos + in.neg + in.zero + in.nonfinite != order)
     return solver_set_error(h, OKKT_ERR_INTERNAL, "pivot counts do not add up to the matrix order");
   if (in.nonfinite > 0) return 0;                       // julia.jl:77-89
@@ -101,14 +149,16 @@ int solver_solve_enqueue(okkt_solver_s* h, const double* d_rhs, double* d_sol, i
   if (rc != OKKT_OK) return rc;
   if (!h->factored) return solver_set_error(h, OKKT_ERR_INVALID, "solve called before a factorisation");
   if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  // a scaled factor: x = S F~^-1 S b, the two multiplications inside the permutation gather and scatter
+  const double* sc = h->sc.valid ? h->sc.s_cur : nullptr;
   // batches of up to kMaxRhs right-hand sides: one pass over L per batch (R = 1, 2 or 4 kernels; three are padded to four)
   for (int64_t r = 0; r < nrhs;) {
     const int nr = (int)std::min<int64_t>(nrhs - r, kMaxRhs);
     const int R = nr >= 3 ? 4 : nr;
-    solve_permute_in(h->N, d_rhs + r * h->S.n, h->S.n, nr, R);
+    solve_permute_in(h->N, d_rhs + r * h->S.n, h->S.n, nr, R, sc);
     std::string e = numeric_solve_enqueue(h->N, R);
     if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
-    solve_permute_out(h->N, d_sol + r * h->S.n, h->S.n, nr, R, accumulate);
+    solve_permute_out(h->N, d_sol + r * h->S.n, h->S.n, nr, R, accumulate, sc);
     r += nr;
   }
   return OKKT_OK;
@@ -134,6 +184,7 @@ void solver_refine_release(okkt_solver_s* h) {
   selinv_release(h->sl);
   krylov_release(h->kr);
   dense_ldlt_release(h->dl);
+  scaling_release(h->sc);
   h->cd_hist.clear();
   if (h->rf_work) (void)hipFree(h->rf_work);
   if (h->rf_om) (void)hipFree(h->rf_om);
@@ -775,6 +826,34 @@ int solver_forward_error_device(okkt_solver_s* h, const double* d_nzval, const d
   return OKKT_OK;
 }
 
+int solver_set_scaling(okkt_solver_s* h, int mode, int32_t sweeps, const double* s_user) {
+  if (mode != OKKT_SCALE_NONE && mode != OKKT_SCALE_RUIZ && mode != OKKT_SCALE_USER)
+    return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_scaling: unknown mode");
+  if (mode == OKKT_SCALE_NONE) {      // the current factor, if scaled, stays what it is until the next factorisation
+    h->sc.mode = OKKT_SCALE_NONE;
+    return OKKT_OK;
+  }
+  if (schur_mode(h))
+    return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_scaling: the handle is in Schur mode, which does not factor a scaled matrix (clear the set with okkt_set_schur, ns = 0)");
+  if (h->analyzed && h->S.nparts > 1)
+    return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_scaling: the handle is partitioned (okkt_dist_set_partition with nparts > 1), a partitioned factorisation is not scaled");
+  if (mode == OKKT_SCALE_RUIZ) {
+    if (sweeps > kScaleMaxSweeps) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_scaling: sweeps > 64");
+    h->sc.mode = OKKT_SCALE_RUIZ;
+    h->sc.sweeps = sweeps <= 0 ? kScaleDefaultSweeps : sweeps;
+    return OKKT_OK;
+  }
+  if (!s_user) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_scaling: OKKT_SCALE_USER needs the vector s_user (it is NULL)");
+  if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_scaling: OKKT_SCALE_USER reads dim entries: okkt_analyze has not been called");
+  for (int64_t i = 0; i < h->S.n; ++i)
+    if (!(s_user[i] > 0.0) || !std::isfinite(s_user[i]))
+      return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_scaling: s_user[" + std::to_string(i) + "] is not finite and positive");
+  h->sc.user.assign(s_user, s_user + h->S.n);
+  h->sc.user_uploaded = false;
+  h->sc.mode = OKKT_SCALE_USER;
+  return OKKT_OK;
+}
+
 }  // namespace okkt
 
 extern "C" {
@@ -1028,7 +1107,7 @@ int okkt_analyze(okkt_handle h, int64_t dim, const int64_t* colptr, const int64_
     if (h->opts.ordering == 2 && (int64_t)h->user_perm.size() != dim)
       return solver_set_error(h, OKKT_ERR_INVALID, "ordering=user: okkt_set_perm must supply dim entries first");
     auto t0 = std::chrono::steady_clock::now();
-    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned || h->kr.V || h->dl.F)) {   // the refinement map (and Z) belong to the old pattern
+    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned || h->kr.V || h->dl.F || h->sc.ready)) {   // the refinement map (and Z) belong to the old pattern
       (void)hipSetDevice(h->device);
       (void)hipStreamSynchronize(h->stream);
       solver_refine_release(h);
@@ -1513,6 +1592,54 @@ int okkt_forward_error(okkt_handle h, const double* nzval, const double* rhs, co
   }
 }
 
+// ---- symmetric equilibration (scaling.hip) ------------------------------------------------------------------
+
+int okkt_set_scaling(okkt_handle h, int mode, int32_t sweeps, const double* s_user) {
+  if (!h) return OKKT_ERR_INVALID;
+  try {
+    return solver_set_scaling(h, mode, sweeps, s_user);
+  } catch (const std::bad_alloc&) {
+    return solver_set_error(h, OKKT_ERR_ALLOC, "out of host memory in okkt_set_scaling");
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_set_scaling");
+  }
+}
+
+// the scaling of the current factor: device, a complete factorisation that used one
+static int scaling_current(okkt_solver_s* h) {
+  int rc = ensure_device(h);
+  if (rc != OKKT_OK) return rc;
+  if (!h->analyzed || !h->factored || !h->sc.valid || !h->sc.ready)
+    return solver_set_error(h, OKKT_ERR_INVALID, "okkt_get_scaling: the handle holds no complete factorisation that used a scaling (okkt_set_scaling, then okkt_factor)");
+  return OKKT_OK;
+}
+
+int okkt_get_scaling_dev(okkt_handle h, double* d_s_out) {
+  if (!h) return OKKT_ERR_INVALID;
+  int rc = scaling_current(h);
+  if (rc != OKKT_OK) return rc;
+  if (h->S.n == 0) return OKKT_OK;
+  if (!d_s_out) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_get_scaling_dev: null pointer");
+  hipError_t he = hipMemcpyAsync(d_s_out, h->sc.s_cur, (size_t)h->S.n * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(h->stream);
+  if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("okkt_get_scaling_dev: ") + hipGetErrorString(he));
+  return OKKT_OK;
+}
+
+int okkt_get_scaling(okkt_handle h, double* s_out, okkt_scaling_info* info) {
+  if (!h) return OKKT_ERR_INVALID;
+  int rc = scaling_current(h);
+  if (rc != OKKT_OK) return rc;
+  if (h->S.n > 0 && !s_out) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_get_scaling: null pointer");
+  if (h->S.n > 0) {
+    hipError_t he = hipStreamSynchronize(h->stream);
+    if (he == hipSuccess) he = hipMemcpy(s_out, h->sc.s_cur, (size_t)h->S.n * sizeof(double), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("okkt_get_scaling: ") + hipGetErrorString(he));
+  }
+  if (info) *info = h->sc.info;
+  return OKKT_OK;
+}
+
 int64_t okkt_debug_dataflow_queue(int32_t nfronts, const int32_t* f, const int32_t* k, int32_t workers, int32_t group,
                                   int32_t* tasks, int64_t cap, double* model_us) {
   if (nfronts < 0 || !f || !k || (cap > 0 && !tasks)) return OKKT_ERR_INVALID;
@@ -1549,6 +1676,8 @@ int okkt_set_schur(okkt_handle h, int64_t ns, const int64_t* idx) {
     if (h->analyzed && ns > 0 && (ns >= h->S.n || sorted.back() >= h->S.n))
       return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_schur: index out of range or ns >= dim of the analysed pattern");
     if (v == h->schur_idx) return OKKT_OK;
+    if (ns > 0 && h->sc.mode != OKKT_SCALE_NONE)
+      return solver_set_error(h, OKKT_ERR_INVALID, "okkt_set_schur: a scaling is set on this handle and Schur mode does not factor a scaled matrix (okkt_set_scaling with OKKT_SCALE_NONE first)");
     h->schur_idx.swap(v);
     h->analyzed = false;      // the plan changes: okkt_analyze builds it again
     h->factored = false;
@@ -1909,6 +2038,8 @@ int okkt_selinv(okkt_handle h, okkt_selinv_info* info) {
   try {
     int rc = selinv_ready(h, false);
     if (rc != OKKT_OK) return rc;
+    if (h->sc.valid)
+      return solver_set_error(h, OKKT_ERR_INVALID, "selected inversion of a scaled factor is not available: the current factor is that of S F S (okkt_set_scaling with OKKT_SCALE_NONE, then factor again)");
     SelinvWork& W = h->sl;
     if (!W.planned || W.analysis != h->n_analyze_calls || W.arena != h->N.d.arena) {
       (void)hipStreamSynchronize(h->stream);
@@ -2061,6 +2192,27 @@ int okkt_logdet(okkt_handle h, double* logabsdet, int32_t* sign) {
       if (v < 0) sg = -sg;
       else if (!(v > 0)) sg = 0;   // zero or NaN
       acc += std::log(std::fabs(v));
+    }
+    if (h->sc.valid && n > 0) {
+      // log |det F| = log |det F~| - 2 sum_i log s_i: for powers of two 2 ln 2 times the integer sum of the exponents
+      int64_t esum = 0;
+      double lsum = 0.0;
+      if (h->sc.info.mode == OKKT_SCALE_RUIZ) {
+        std::vector<int> ex((size_t)n);
+        if (hipMemcpy(ex.data(), h->sc.expo, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+          return solver_set_error(h, OKKT_ERR_HIP, "download of the scaling exponents failed");
+        for (int64_t i = 0; i < n; ++i) esum += ex[(size_t)i];
+      } else {
+        std::vector<double> sv((size_t)n);
+        if (hipMemcpy(sv.data(), h->sc.s_cur, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+          return solver_set_error(h, OKKT_ERR_HIP, "download of the scaling failed");
+        for (int64_t i = 0; i < n; ++i) {
+          int ex = 0;
+          if (std::frexp(sv[(size_t)i], &ex) == 0.5) esum += ex - 1;
+          else lsum += std::log(sv[(size_t)i]);
+        }
+      }
+      acc -= 2.0 * 0.69314718055994530942 * (double)esum + 2.0 * lsum;
     }
     *logabsdet = acc;
     *sign = sg;

@@ -40,6 +40,8 @@ extern "C" {
 int okkt_dist_set_partition(okkt_handle h, int nparts, int part_id) {
   if (!h || nparts < 1 || part_id < 0 || part_id >= nparts) return OKKT_ERR_INVALID;
   if (nparts > 1 && schur_mode(h)) return schur_refuse(h, "okkt_dist_set_partition with nparts > 1");
+  if (nparts > 1 && h->sc.mode != OKKT_SCALE_NONE)
+    return solver_set_error(h, OKKT_ERR_INVALID, "okkt_dist_set_partition with nparts > 1: a scaling is set on this handle and a partitioned factorisation is not scaled (okkt_set_scaling with OKKT_SCALE_NONE first)");
   if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_analyze has not been called");
   if (h->numeric_ready) {
     (void)hipSetDevice(h->device);

@@ -1311,6 +1311,18 @@ int okkt_kkt_set_ls_refine(okkt_kkt_handle k, int32_t max_steps, double tol) {
   return OKKT_OK;
 }
 
+// symmetric equilibration of the system every factor! factors: the level-1 handle scales the shifted values
+// and every solve of this level goes through its solve, so nothing else changes here
+int okkt_kkt_set_ls_scaling(okkt_kkt_handle k, int mode, int32_t sweeps) {
+  if (!k) return OKKT_ERR_INVALID;
+  if (k->kind == OKKT_KKT_CLEVER_SYMMETRIC)
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_set_ls_scaling: the clever-symmetric kind has a rescale of its own (okkt_kkt_set_rescale)");
+  if (mode == OKKT_SCALE_USER)
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_set_ls_scaling: a caller's vector (OKKT_SCALE_USER) is not available at the KKT level: OKKT_SCALE_RUIZ or OKKT_SCALE_NONE");
+  const int rc = solver_set_scaling(k->ls, mode, sweeps, nullptr);
+  return rc < 0 ? kk_check_ls(k, rc, "okkt_kkt_set_ls_scaling") : rc;
+}
+
 int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const double* primal_r, const double* comp_r,
                                int32_t ItRefine_Num, double* dx, double* dy, double* ds, okkt_kkt_error* err_out) {
   if (!k) return OKKT_ERR_INVALID;

@@ -261,9 +261,11 @@ std::string solve_fwd_enqueue(Numeric& N, int which, int R);
 std::string solve_bwd_enqueue(Numeric& N, int which, int R);
 std::string solve_setup(const Symbolic& S, Numeric& N);
 std::string solve_invert_enqueue(Numeric& N, hipStream_t st, const SolveLevel& L, int b_lo, int b_hi);
-// xwork[q][k] = rhs[q * stride + perm[k]] for q < nr (zero for nr <= q < R)  /  sol[q * stride + perm[k]] (+)= xwork[q][k]
-void solve_permute_in(const Numeric& N, const double* d_rhs, int64_t stride, int nr, int R);
-void solve_permute_out(const Numeric& N, double* d_sol, int64_t stride, int nr, int R, bool accumulate);
+// xwork[q][k] = rhs[q * stride + perm[k]] for q < nr (zero for nr <= q < R)  /  sol[q * stride + perm[k]] (+)= xwork[q][k].
+// d_scale (original order; NULL: none): the gathered / scattered value is multiplied by d_scale[perm[k]] in the same launch -- the
+// two ends of x = S F~^-1 S b of a scaled factor
+void solve_permute_in(const Numeric& N, const double* d_rhs, int64_t stride, int nr, int R, const double* d_scale = nullptr);
+void solve_permute_out(const Numeric& N, double* d_sol, int64_t stride, int nr, int R, bool accumulate, const double* d_scale = nullptr);
 // what = 0 contribution blocks, 1 contribution vectors; unpack = 0: mine -> buffer, 1: buffer -> the others' slots
 std::string numeric_dist_pack(Numeric& N, int what, int unpack, double* d_buf);
 // mode 0: the top's columns of xwork -> buf, packed (n_top_cols doubles); 1: buf -> xwork on the top's columns; 2: owned part of the solution,

@@ -1387,17 +1387,23 @@ __global__ __launch_bounds__(256) void k_schur_export(const double* __restrict__
   }
 }
 
-template <int R>
-__global__ void k_permute_in_r(int n, int nr, int64_t stride_in, const int* __restrict__ perm, const double* __restrict__ rhs, double* __restrict__ x, int64_t xs) {
+// SC: the scaled twins (a scaled factor): the value is multiplied by sc[g] on its way in and on its way out
+template <int R, bool SC>
+__global__ void k_permute_in_r(int n, int nr, int64_t stride_in, const int* __restrict__ perm, const double* __restrict__ rhs, double* __restrict__ x, int64_t xs,
+                               const double* __restrict__ sc) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int g = perm[i];
+  const double sg = SC ? sc[g] : 1.0;
 #pragma unroll
-  for (int q = 0; q < R; ++q) x[(size_t)q * xs + i] = q < nr ? rhs[(size_t)q * stride_in + g] : 0.0;
+  for (int q = 0; q < R; ++q) {
+    const double v = q < nr ? rhs[(size_t)q * stride_in + g] : 0.0;
+    x[(size_t)q * xs + i] = SC ? v * sg : v;
+  }
 }
-template <int R>
+template <int R, bool SC>
 __global__ void k_permute_out_r(int n, int nr, int64_t stride_out, const int* __restrict__ perm, const double* __restrict__ x, int64_t xs, double* __restrict__ sol, int accumulate,
-                                const unsigned long long* __restrict__ tmo) {
+                                const unsigned long long* __restrict__ tmo, const double* __restrict__ sc) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int g = perm[i];
@@ -1407,7 +1413,8 @@ __global__ void k_permute_out_r(int n, int nr, int64_t stride_out, const int* __
   for (int q = 0; q < R; ++q)
     if (q < nr) {
       double* d = sol + (size_t)q * stride_out + g;
-      const double v = lost ? __builtin_nan("") : x[(size_t)q * xs + i];
+      double v = lost ? __builtin_nan("") : x[(size_t)q * xs + i];
+      if (SC) v = v * sc[g];
       *d = accumulate ? *d + v : v;
     }
 }
@@ -1745,22 +1752,39 @@ void schur_export_enqueue(Numeric& N, double* d_S, int64_t ld) {
   hipLaunchKernelGGL(k_schur_export, dim3((unsigned)(T * (T + 1) / 2)), dim3(256), 0, N.stream, N.d.arena + N.front_pos_host[N.schur_sn], ns, d_S, ld);
 }
 
-void solve_permute_in(const Numeric& N, const double* d_rhs, int64_t stride, int nr, int R) {
+void solve_permute_in(const Numeric& N, const double* d_rhs, int64_t stride, int nr, int R, const double* d_scale) {
   const int n = N.d.n;
   if (!n) return;
   const dim3 g((n + 255) / 256), b(256);
-  if (R == 1) hipLaunchKernelGGL(k_permute_in_r<1>, g, b, 0, N.stream, n, nr, stride, N.d.perm, d_rhs, N.d.xwork, N.d.xw_stride);
-  else if (R == 2) hipLaunchKernelGGL(k_permute_in_r<2>, g, b, 0, N.stream, n, nr, stride, N.d.perm, d_rhs, N.d.xwork, N.d.xw_stride);
-  else hipLaunchKernelGGL(k_permute_in_r<4>, g, b, 0, N.stream, n, nr, stride, N.d.perm, d_rhs, N.d.xwork, N.d.xw_stride);
+#define OKKT_PERMUTE_IN(RR, SCL) hipLaunchKernelGGL((k_permute_in_r<RR, SCL>), g, b, 0, N.stream, n, nr, stride, N.d.perm, d_rhs, N.d.xwork, N.d.xw_stride, d_scale)
+  if (d_scale) {
+    if (R == 1) OKKT_PERMUTE_IN(1, true);
+    else if (R == 2) OKKT_PERMUTE_IN(2, true);
+    else OKKT_PERMUTE_IN(4, true);
+  } else {
+    if (R == 1) OKKT_PERMUTE_IN(1, false);
+    else if (R == 2) OKKT_PERMUTE_IN(2, false);
+    else OKKT_PERMUTE_IN(4, false);
+  }
+#undef OKKT_PERMUTE_IN
 }
-void solve_permute_out(const Numeric& N, double* d_sol, int64_t stride, int nr, int R, bool accumulate) {
+void solve_permute_out(const Numeric& N, double* d_sol, int64_t stride, int nr, int R, bool accumulate, const double* d_scale) {
   const int n = N.d.n;
   if (!n) return;
   const dim3 g((n + 255) / 256), b(256);
   const int acc = accumulate ? 1 : 0;
-  if (R == 1) hipLaunchKernelGGL(k_permute_out_r<1>, g, b, 0, N.stream, n, nr, stride, N.d.perm, N.d.xwork, N.d.xw_stride, d_sol, acc, N.d.counters + 5);
-  else if (R == 2) hipLaunchKernelGGL(k_permute_out_r<2>, g, b, 0, N.stream, n, nr, stride, N.d.perm, N.d.xwork, N.d.xw_stride, d_sol, acc, N.d.counters + 5);
-  else hipLaunchKernelGGL(k_permute_out_r<4>, g, b, 0, N.stream, n, nr, stride, N.d.perm, N.d.xwork, N.d.xw_stride, d_sol, acc, N.d.counters + 5);
+#define OKKT_PERMUTE_OUT(RR, SCL) \
+  hipLaunchKernelGGL((k_permute_out_r<RR, SCL>), g, b, 0, N.stream, n, nr, stride, N.d.perm, N.d.xwork, N.d.xw_stride, d_sol, acc, N.d.counters + 5, d_scale)
+  if (d_scale) {
+    if (R == 1) OKKT_PERMUTE_OUT(1, true);
+    else if (R == 2) OKKT_PERMUTE_OUT(2, true);
+    else OKKT_PERMUTE_OUT(4, true);
+  } else {
+    if (R == 1) OKKT_PERMUTE_OUT(1, false);
+    else if (R == 2) OKKT_PERMUTE_OUT(2, false);
+    else OKKT_PERMUTE_OUT(4, false);
+  }
+#undef OKKT_PERMUTE_OUT
 }
 
 }  // namespace okkt

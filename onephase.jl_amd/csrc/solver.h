@@ -11,6 +11,7 @@
 #include "krylov.h"
 #include "numeric.h"
 #include "refine.h"
+#include "scaling.h"
 #include "selinv.h"
 #include "symbolic.h"
 
@@ -74,6 +75,9 @@ struct okkt_solver_s {
   // analysis and released with the refinement map; the pivot counts of the last okkt_factor_schur (A11's) for the whole-matrix inertia
   okkt::DenseLdltWork dl;
   okkt_inertia a11_inertia = {0, 0, 0, 0};
+  // symmetric equilibration (scaling.hip): the configuration of okkt_set_scaling (kept across analyses) and the
+  // device state of the current analysis, allocated by the first scaled factorisation and released with the refinement map
+  okkt::ScalingWork sc;
 };
 
 namespace okkt {
@@ -94,6 +98,8 @@ inline int schur_refuse(okkt_solver_s* h, const char* what) {
                                                    "use okkt_factor_schur / okkt_schur_condense / okkt_schur_expand, or clear the set with ns = 0)");
 }
 int solver_ensure_numeric(okkt_solver_s* h);
+// okkt_set_scaling behind its argument checks (api.cpp): also what okkt_kkt_set_ls_scaling forwards to
+int solver_set_scaling(okkt_solver_s* h, int mode, int32_t sweeps, const double* s_user);
 // refinement driver (api.cpp): x = F \ b, then corrections from the double-double residual against d_nzval until omega <= tol,
 // stagnation, a non-finite value or max_steps.  d_rhs, d_sol: nrhs x n on the device (they may alias).  lap(tag), if given, is called at
 // the phase boundaries (tag 0: a solve ended, 1: residual / vector work ended); n_solves_out: right-hand sides solved

@@ -68,6 +68,19 @@ function set_ls_refine!(k::HIP_KKT_solver, pars::Class_parameters)
     (steps != 0 || tol != 0.0) && set_ls_refine!(k, steps, tol)
 end
 
+# okkt_kkt_set_ls_scaling (Schur, Schur-direct and symmetric kinds): pars.kkt.hip_ls_scaling (0 / 1) and hip_ls_scaling_sweeps (0 = 10)
+# ("kkt!hip_ls_scaling", "kkt!hip_ls_scaling_sweeps"; not okkt_opts fields).  Call once after construction: every factor! then
+# equilibrates the shifted system it factors (DESIGN.md section 8.8); directions and estimates keep describing the unscaled system.
+function set_ls_scaling!(k::HIP_KKT_solver, on::Integer, sweeps::Integer=0)
+    kkt_hip_check(k, "okkt_kkt_set_ls_scaling", ccall((:okkt_kkt_set_ls_scaling, OKKT_LIB), Cint, (Ptr{Cvoid}, Cint, Int32),
+                                                      k.handle, on != 0 ? 1 : 0, Int32(sweeps)))
+end
+function set_ls_scaling!(k::HIP_KKT_solver, pars::Class_parameters)
+    on = hasproperty(pars.kkt, :hip_ls_scaling) ? pars.kkt.hip_ls_scaling : 0
+    sweeps = hasproperty(pars.kkt, :hip_ls_scaling_sweeps) ? pars.kkt.hip_ls_scaling_sweeps : 0
+    on != 0 && set_ls_scaling!(k, on, sweeps)
+end
+
 # okkt_kkt_condest: kappa_1 of the system the last factor! factored (K + delta, M, Q + delta I or the bordered A with dense rows)
 function kkt_condest(k::HIP_KKT_solver; t::Integer=2)
     info = Ref(OkktCondestInfo(0.0, 0.0, 0.0, 0, 0, 0))

@@ -211,6 +211,34 @@ function ls_forward_error(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,
     return ferr[1], berr[1]
 end
 
+struct OkktScalingInfo    # okkt_scaling_info of include/okkt.h
+    mode::Int32          # 0 none, 1 Ruiz sweeps rounded to powers of two, 2 the caller's vector
+    sweeps::Int32
+    rowmax_min::Float64  # over the non-zero rows of |S F S| as factored
+    rowmax_max::Float64
+    zero_rows::Int64
+end
+
+# Symmetric equilibration before the factorisation (DESIGN.md section 8.8): mode 0 off, 1 every ls_factor! computes s by `sweeps`
+# Jacobi sweeps (0 = 10) rounded to powers of two and factors S F S, 2 the vector s (the analysed dimension, finite and > 0) as given.
+# Solves, refinement and the estimates keep describing the unscaled matrix.  Not part of the reference interface.
+function set_scaling!(solver::linear_solver_HIP, mode::Integer, sweeps::Integer=0, s::Union{Nothing,Array{Float64,1}}=nothing)
+    rc = s === nothing ?
+         ccall((:okkt_set_scaling, OKKT_LIB), Cint, (Ptr{Cvoid}, Cint, Int32, Ptr{Float64}), solver.handle, mode, Int32(sweeps), C_NULL) :
+         ccall((:okkt_set_scaling, OKKT_LIB), Cint, (Ptr{Cvoid}, Cint, Int32, Ptr{Float64}), solver.handle, mode, Int32(sweeps), s)
+    rc < 0 && okkt_error(solver, "okkt_set_scaling", rc)
+end
+
+# (s, info) of the current factor: s in the original order (dim = the analysed dimension)
+function scaling(solver::linear_solver_HIP, dim::Integer)
+    s = zeros(dim)
+    info = Ref(OkktScalingInfo(0, 0, 0.0, 0.0, 0))
+    rc = ccall((:okkt_get_scaling, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ref{OkktScalingInfo}), solver.handle, s, info)
+    rc < 0 && okkt_error(solver, "okkt_get_scaling", rc)
+    return s, info[]
+end
+scaling_info(solver::linear_solver_HIP, dim::Integer) = scaling(solver, dim)[2]
+
 function ls_solve(solver::linear_solver_HIP, my_rhs::AbstractArray, timer::class_advanced_timer)
     rhs = Vector{Float64}(my_rhs)      # SparseVector rhs is densified, as in julia.jl:105-113
     sol = zeros(length(rhs))

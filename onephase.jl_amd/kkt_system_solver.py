@@ -113,6 +113,11 @@ class Class_kkt_solver_options:   # parameters.jl:4-46 (the entries the path rea
     # <= hip_ls_refine_tol (0.0 = 2^-52) ("kkt!hip_ls_refine_steps", "kkt!hip_ls_refine_tol")
     hip_ls_refine_steps: int = 0
     hip_ls_refine_tol: float = 0.0
+    # Schur, Schur-direct and symmetric kinds, not okkt_opts fields (okkt_kkt_set_ls_scaling): 1 = every factor! equilibrates the shifted
+    # system it factors, S F S with s from hip_ls_scaling_sweeps Jacobi sweeps (0 = 10) rounded to powers of two; 0 = off
+    # ("kkt!hip_ls_scaling", "kkt!hip_ls_scaling_sweeps")
+    hip_ls_scaling: int = 0
+    hip_ls_scaling_sweeps: int = 0
 
 
 def okkt_opts_from_pars(kkt):
@@ -193,6 +198,8 @@ class HIP_KKT_solver:
         # the refinement of the symmetric kind is a setter of the handle, not an okkt_opts field: keywords override pars.kkt
         self.ls_refine_steps = int(opts.pop("hip_ls_refine_steps", self.pars.kkt.hip_ls_refine_steps))
         self.ls_refine_tol = float(opts.pop("hip_ls_refine_tol", self.pars.kkt.hip_ls_refine_tol))
+        self.ls_scaling = int(opts.pop("hip_ls_scaling", self.pars.kkt.hip_ls_scaling))
+        self.ls_scaling_sweeps = int(opts.pop("hip_ls_scaling_sweeps", self.pars.kkt.hip_ls_scaling_sweeps))
         self._opts = opts
         self._lib = None
         self._k = None
@@ -224,6 +231,8 @@ class HIP_KKT_solver:
             self._k = k
             if self.ls_refine_steps != 0 or self.ls_refine_tol != 0.0:
                 self._check(self._lib.okkt_kkt_set_ls_refine(self._k, self.ls_refine_steps, self.ls_refine_tol), "okkt_kkt_set_ls_refine")
+            if self.ls_scaling != 0:
+                self._check(self._lib.okkt_kkt_set_ls_scaling(self._k, L.OKKT_SCALE_RUIZ, self.ls_scaling_sweeps), "okkt_kkt_set_ls_scaling")
         self.dir = Class_point(np.zeros(intial_it.dim()), np.zeros(intial_it.ncon()), np.zeros(intial_it.ncon()))
         if self.kind == "clever_symmetric" and self._pattern is None:
             # initialize!(::Clever_Symmetric_KKT_solver, it): compute_indicies(get_jac(it)), clever_symmetric.jl:53-61

@@ -372,6 +372,37 @@ class linear_solver_HIP(abstract_linear_system_solver):
                     "okkt_forward_error")
         return (ferr[0], berr[0]) if single else (ferr, berr)
 
+    # -- symmetric equilibration before the factorisation (not part of the reference interface)
+    def set_scaling(self, mode, sweeps=0, s=None):
+        """okkt_set_scaling: mode "none" | "ruiz" | "user" (or OKKT_SCALE_*).  "ruiz": every factorisation computes s by `sweeps`
+        Jacobi sweeps (0 = 10) rounded to powers of two and factors S F S; "user": the vector s (analysed dimension, original order,
+        finite and > 0) as given.  Solves, refinement and the estimates keep describing the unscaled matrix."""
+        self._need()
+        mode = L.OKKT_SCALE[mode] if isinstance(mode, str) else int(mode)
+        v = None if s is None else L.f64(s)
+        if v is not None and self._dim and v.shape != (self._dim,):
+            raise OkktError("s must have the analysed dimension")
+        self._check(self._lib.okkt_set_scaling(self._h, mode, int(sweeps), None if v is None else L.p_f64(v)), "okkt_set_scaling")
+
+    def scaling(self):
+        """s of the current factor (original order)."""
+        self._need()
+        out = np.zeros(self._dim)
+        self._check(self._lib.okkt_get_scaling(self._h, L.p_f64(out), None), "okkt_get_scaling")
+        return out
+
+    def scaling_info(self):
+        """okkt_scaling_info of the current factor as a dict (mode, sweeps, rowmax_min, rowmax_max, zero_rows)."""
+        self._need()
+        out = np.zeros(max(self._dim, 1))
+        info = L.OkktScalingInfo()
+        self._check(self._lib.okkt_get_scaling(self._h, L.p_f64(out), C.byref(info)), "okkt_get_scaling")
+        return info.as_dict()
+
+    def scaling_dev(self, d_s_out):
+        self._need()
+        self._check(self._lib.okkt_get_scaling_dev(self._h, C.c_void_p(d_s_out)), "okkt_get_scaling_dev")
+
     # -- Schur mode: partial factorisation with a dense Schur complement (not part of the reference interface; DESIGN.md section 8.4)
     def set_schur(self, idx):
         """Hold the variables idx (0-based, distinct) back: the next analyze() orders the rest and puts them last as one front that
