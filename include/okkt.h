@@ -430,6 +430,15 @@ int okkt_get_profile(okkt_handle h, int64_t* n_launches, double* total_ms, doubl
  * the queue on a dense matrix with numpy and checks the dependency order. */
 int64_t okkt_debug_dataflow_queue(int32_t nfronts, const int32_t* f, const int32_t* k, int32_t workers, int32_t group,
                                   int32_t* tasks, int64_t cap, double* model_us);
+/* Test hook, host only: the register and LDS maps of the update tasks of the dataflow launch (csrc/df_fragments.h), evaluated by the
+ * functions the kernel itself uses.  map: 0 = the earlier map (column fragments 4 doubles apart, both operand images with leading
+ * dimension 144), 1 = the contiguous map with the ring's own images, < 0 = the one this library's kernel was compiled with.  what:
+ * 0 = column (inside the wave's 32) of accumulator group idx of a lane, 1 = column of its column-operand fragment idx, 2 = offset
+ * (doubles, from the ring slot's first) of column-operand fragment idx of k-step kk, 3 = the same for row-operand fragment idx (0 .. 3),
+ * 4 = rows by which the LDS-DMA rotates the panel column that the lane reads in k-step kk, 5 = geometry: idx 0 / 1 leading dimension of
+ * the row / column operand image, 2 doubles per ring slot, 3 panel columns per slot, 4 slots, 5 the compiled-in map, 6 the kernel's LDS
+ * bytes, 7 the per-step kernels' leading dimension.  Returns the value, or a negative error code.  tests/test_dataflow_fragments.py. */
+int64_t okkt_debug_dataflow_fragment(int32_t map, int32_t what, int32_t wave, int32_t lane, int32_t kk, int32_t idx);
 
 
 /* ---- multi-GPU: subtree-to-GPU sharding of ONE factorisation (one process per GPU) -------------------

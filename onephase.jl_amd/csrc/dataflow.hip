@@ -18,6 +18,8 @@
 // The arithmetic per entry is the sequence of the per-step kernels (same bodies, same order of the panels per tile): the factor
 // is bitwise the same, which is how the GPU tests pin this path (tests/test_gpu_dataflow.py).
 #include "front_device.h"
+#include "df_fragments.h"
+#include "../../include/okkt.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -86,6 +88,15 @@ constexpr bool kDfLog = OKKT_DF_LOG_BUILD != 0;
 constexpr bool kDfMulti = OKKT_DF_MULTI != 0;
 constexpr bool kDfPipe = OKKT_DF_PIPE != 0;      // update tasks: operand fragments requested one step ahead of their MFMAs, reads and waits by hand (df_syrk_tiles); bitwise equal, no gain in the kernel: off
 constexpr bool kDfRot = OKKT_DF_ROT != 0;   // update tasks: the column fragments of a k-step from ONE LDS read + lane rotations (df_syrk_tiles); bitwise equal, 12 % SLOWER (see there)
+#ifndef OKKT_DF_CONTIG
+#define OKKT_DF_CONTIG 1
+#endif
+// update tasks: a lane's eight column fragments are eight NEIGHBOURING columns (4 x ds_read_b128 instead of 4 x ds_read2_b64 per k-step) and the operand
+// ring has a conflict-free image of its own (df_fragments.h); bitwise equal.  -DOKKT_DF_CONTIG=0: the earlier map and the kSyrkLd ring, for A/B runs
+constexpr int kDfContig = OKKT_DF_CONTIG != 0 ? 1 : 0;
+static_assert(!(kDfContig && (OKKT_DF_ROT != 0 || OKKT_DF_PIPE != 0)), "the rotation and hand-pipelined experiments are written for the earlier fragment map");
+static_assert(kDfFragLdOld == kSyrkLd, "df_fragments.h describes the earlier ring with kSyrkLd");
+static_assert(df_ring_rot(kDfContig, 1) == 0, "the LDS-DMA of df_syrk_tiles fetches a panel column lane-linearly");
 constexpr bool kDfMacro = OKKT_DF_MACRO != 0;   // update tasks on pairs of row tiles as one macro tile (df_syrk_macro)
 constexpr int kDfDiagMfmaWaves = 6;   // MFMA waves of the diagonal-block factorisation in a worker (four or six: the same time)
 constexpr int kDfKC = OKKT_DF_KC;           // panel columns per ring slot of the update tasks
@@ -1008,6 +1019,11 @@ __device__ __forceinline__ double df_row_ror(double v) {
 // 19.0 cycles per MFMA and SIMD, S-metric 19.2 instead of 17.1 ms: the 12 v_mov_b32_dpp of a k-step do not hide behind the MFMAs, each costs
 // the wave ~ 7.5 issue cycles, more than the LDS read it replaces.  The loop is bound by what a pair of waves can ISSUE per MFMA slot (LDS
 // reads and VALU alike), which is why the wider register tile (df_syrk_macro: fewer operand instructions per MFMA) helps and this does not.  Off.
+// kDfContig (default): the LDS ARRAY's side of the same bound.  With the earlier map the eight column fragments of a lane lie 4 doubles apart and come
+// as 4 x ds_read2_b64 (8 array cycles each, against 4 for a ds_read_b128 of the same bytes), and at kSyrkLd = 144 every row read is 2-way bank-conflicted.
+// Here the wave's columns are renamed so that a lane's fragments are 64 contiguous bytes, and the ring has its own two images (df_fragments.h): per
+// k-step 6 conflict-free ds_read_b128, 24 instead of 40 + 8 array cycles, no VALU added.  Measured (profiles/contiguous_fragments_ab.txt): LDS-array cycles
+// of the launch - 41 %, conflict share 0.143 -> 0.011, the chunk 10 268 -> 9 771 cycles, S-metric 18.09 -> 17.85 ms -- the array was part of the wait, not all.
 // KC / STAGES: panel columns per ring slot and slots (32 x 2 for the one-workgroup-per-CU worker; 16 x 2 = 72 KB was the 128-VGPR
 // bulk kernel's of the two-kernel form, scripts/experiments/r05_two_kernel_form.patch); MULTI: a task may carry several row tiles
 // (the next C tile in a second register set); STAGGER: see below.
@@ -1019,6 +1035,8 @@ __device__ __forceinline__ void df_syrk_tiles(const DevPlan& P, int s, int j0, i
   constexpr int DMA = 2 * (kDfKC / NW);   // LDS-DMA instructions per wave and chunk
   constexpr int WCW = 128 / (NW / 2);   // columns per wave
   constexpr int NCG = WCW / 4;          // 4-column groups per wave
+  constexpr int LDW = df_ring_ld_w(kDfContig), LDL = df_ring_ld_l(kDfContig), SLOT = df_ring_slot_doubles(kDfContig, kDfKC);      // the ring's images: df_fragments.h
+  static_assert(WCW == 32 && NCG == 8, "df_fragments.h: 2 x 4 waves of 64 rows x 32 columns");
   int tid_ = threadIdx.x;
   asm volatile("" : "+v"(tid_));      // opaque: nothing derived from the lane id is hoisted out of the worker's loop and kept live across the other roles
   const int tid = tid_, lane = tid & 63, wv = tid >> 6;
@@ -1039,7 +1057,7 @@ __device__ __forceinline__ void df_syrk_tiles(const DevPlan& P, int s, int j0, i
     grp3 = __builtin_amdgcn_update_dpp(0, quad, 0x12C, 0xf, 0xf, false);
   }
   auto col_of = [&](int cg) {      // the column of accumulator group cg in this lane
-    if constexpr (!kDfRot) return cbase + cg * 4 + l4;
+    if constexpr (!kDfRot) return cbase + df_frag_acc_col(kDfContig, lane, cg);
     const int m = cg & 3;
     return cbase + (cg >> 2) * 16 + (m == 0 ? quad : m == 1 ? grp1 : m == 2 ? grp2 : grp3) * 4 + l4;
   };
@@ -1049,15 +1067,15 @@ __device__ __forceinline__ void df_syrk_tiles(const DevPlan& P, int s, int j0, i
   auto issue = [&](int g) {
     const int r = g / nchunk, ch = g - r * nchunk;
     const double* Wg = Wcol + df_block_lo(i + r, KB, k, f);
-    double* slot = sm + (size_t)(g % STAGES) * 2 * kDfKC * kSyrkLd;
+    double* slot = sm + (size_t)(g % STAGES) * SLOT;
 #pragma unroll
     for (int qq = 0; qq < kDfKC / NW; ++qq) {
       const int prow = qq * NW + wv;
       const int p = ch * kDfKC + prow;
       const double* wsrc = p < nb ? Wg + (size_t)p * f : P.zero_page + lane * 2;
       const double* lsrc = p < nb ? Lg + (size_t)p * f : P.zero_page + lane * 2;
-      __builtin_amdgcn_global_load_lds(wsrc, (lds_void_t*)(slot + prow * kSyrkLd), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(lsrc, (lds_void_t*)(slot + (kDfKC + prow) * kSyrkLd), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(wsrc, (lds_void_t*)(slot + prow * LDW), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(lsrc, (lds_void_t*)(slot + kDfKC * LDW + prow * LDL), 16, 0, 0);
     }
   };
   // raw C pairs of a row tile (clamped addresses, no branches) and the masks that turn them into accumulators
@@ -1134,10 +1152,30 @@ __device__ __forceinline__ void df_syrk_tiles(const DevPlan& P, int s, int j0, i
     // around the loop unchanged: does the launch get faster when the bulk work gets cheaper?)
     const bool active = !(rbase + 63 < cbase) && rbase < rlim && cbase < clim && !(kDfChain && P.df_dbg_half && nb >= 256 && (g & 1));
     if (active) {
-      const double* slot = sm + (size_t)(g % STAGES) * 2 * kDfKC * kSyrkLd;
+      const double* slot = sm + (size_t)(g % STAGES) * SLOT;
       const double* bw = slot + (wv & 1) * 64 + 2 * l15;
-      const double* bl = slot + kDfKC * kSyrkLd + (wv >> 1) * WCW + (kDfRot ? l15 : (lane & 3));
-      if constexpr (kDfRot || !kDfPipe) {
+      const double* bl = slot + kDfKC * kSyrkLd + (wv >> 1) * WCW + (kDfRot ? l15 : (lane & 3));      // (the experiments: the earlier ring)
+      if constexpr (kDfContig) {
+        // a k-step: the four row fragments and the eight column fragments as 2 + 4 sixteen-byte reads (df_fragments.h)
+  #pragma unroll
+        for (int kk = 0; kk < kDfKC / 4; ++kk) {
+          if (kk == (KC / 8) && more && late) issue(g + STAGES - 1);
+          d2_t bq[2];
+  #pragma unroll
+          for (int h = 0; h < 2; ++h) bq[h] = *(const d2_t*)(slot + df_frag_b_off(kDfContig, wv, lane, kk, 2 * h));
+  #pragma unroll
+          for (int half = 0; half < NCG / 4; ++half) {
+            d2_t aq[2];
+  #pragma unroll
+            for (int h = 0; h < 2; ++h) aq[h] = *(const d2_t*)(slot + df_frag_a_off(kDfContig, kDfKC, wv, lane, kk, half * 4 + 2 * h));
+  #pragma unroll
+            for (int qq = 0; qq < 4; ++qq)
+  #pragma unroll
+              for (int rb = 0; rb < 4; ++rb)
+                acc[half * 4 + qq][rb] = __builtin_amdgcn_mfma_f64_4x4x4f64(aq[qq >> 1][qq & 1], bq[rb >> 1][rb & 1], acc[half * 4 + qq][rb], 0, 0, 1 /* neg A */);
+          }
+        }
+      } else if constexpr (kDfRot || !kDfPipe) {
   #pragma unroll
         for (int kk = 0; kk < kDfKC / 4; ++kk) {
           if (kk == (KC / 8) && more && late) issue(g + STAGES - 1);
@@ -1214,9 +1252,13 @@ __device__ __forceinline__ void df_syrk_tiles(const DevPlan& P, int s, int j0, i
       if (marks && g == total - 1 && tid == 0) { marks[1] = wall_clock64(); marks[3] += (long long)clock64(); }      // main loop done: marks[3] = shader cycles of the main loop
       // the row tile is done: store it (write-through, not waited for here) and switch to the next one's accumulators
       if (active) {
+        // (contiguous map: the eight column addresses are formed here, from a lane id read afresh -- hoisted out of the chunk loop they do
+        // not fit beside the accumulators, and a reload from scratch in front of every store waits for the store before it)
+        int lane_s = lane;
+        if constexpr (kDfContig) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_s));
 #pragma unroll
         for (int cg = 0; cg < NCG; ++cg) {
-          const int c = col_of(cg);
+          const int c = kDfContig ? cbase + df_frag_acc_col(kDfContig, lane_s, cg) : col_of(cg);
           if (c >= clim) continue;
           double* colp = Fc + (size_t)c * f;
 #pragma unroll
@@ -1612,7 +1654,7 @@ __device__ __forceinline__ void df_syrk_chain(const DevPlan& P, const DfTask* __
 }
 
 constexpr int kDfThreads = kDfThreadsC;
-constexpr size_t kDfLds = std::max(std::max(std::max(std::max(OKKT_DIAG2_LDS_DOUBLES(kMW) * sizeof(double), kDfTuLds), (size_t)kDfStages * 2 * kDfKC * kSyrkLd * sizeof(double)), kDfTlLds), std::max(std::max(kDfTuLockLds, kDfMacroLds), (size_t)128 * kDfTileLd * sizeof(double)));   // diag2_body's and df_tu_tile's; the other roles need less
+constexpr size_t kDfLds = std::max(std::max(std::max(std::max(OKKT_DIAG2_LDS_DOUBLES(kMW) * sizeof(double), kDfTuLds), (size_t)kDfStages * df_ring_slot_doubles(kDfContig, kDfKC) * sizeof(double)), kDfTlLds), std::max(std::max(kDfTuLockLds, kDfMacroLds), (size_t)128 * kDfTileLd * sizeof(double)));   // diag2_body's and df_tu_tile's; the other roles need less
 
 // counters[5] = a wait ran into its bound, three seconds of wall clock (or another worker's did): every worker leaves, the factorisation
 // fails with "a hand-off timed out" and the solves return NaN -- never numbers computed from tiles that had not arrived
@@ -1900,3 +1942,22 @@ std::string df_launch(Numeric& N, const DevPlan& P, const Segment& g, hipStream_
 }
 
 }  // namespace okkt
+
+// the maps of df_fragments.h as this library's kernel was compiled with them (host only; tests/test_dataflow_fragments.py)
+extern "C" int64_t okkt_debug_dataflow_fragment(int32_t map, int32_t what, int32_t wave, int32_t lane, int32_t kk, int32_t idx) {
+  using namespace okkt;
+  if (map < 0) map = kDfContig;
+  if (map > 1 || wave < 0 || wave >= 8 || lane < 0 || lane >= 64 || kk < 0 || kk >= kDfKC / 4 || idx < 0 || idx >= 8) return OKKT_ERR_INVALID;
+  switch (what) {
+    case 0: return df_frag_acc_col(map, lane, idx);
+    case 1: return df_frag_a_col(map, lane, idx);
+    case 2: return df_frag_a_off(map, kDfKC, wave, lane, kk, idx);
+    case 3: return idx < 4 ? df_frag_b_off(map, wave, lane, kk, idx) : OKKT_ERR_INVALID;
+    case 4: return df_ring_rot(map, 4 * kk + (lane >> 4));
+    case 5: {
+      const int64_t geo[8] = {df_ring_ld_w(map), df_ring_ld_l(map), df_ring_slot_doubles(map, kDfKC), kDfKC, kDfStages, kDfContig, (int64_t)kDfLds, kSyrkLd};
+      return geo[idx];
+    }
+  }
+  return OKKT_ERR_INVALID;
+}
