@@ -340,6 +340,49 @@ int okkt_get_inverse_csc(okkt_handle h, int64_t* colptr, int64_t* rowval, double
 /* log |det F| and its sign from D, summed in pivot order on the host (deterministic); sign 0 and -Inf when a pivot is 0.  Needs a
  * complete factorisation (not okkt_selinv); same refusals otherwise. */
 int okkt_logdet(okkt_handle h, double* logabsdet, int32_t* sign);
+/* ---- Threshold pivot report: the multipliers of the static-pivot factor ----------------------------------
+ * The factorisation never pivots.  okkt_pivot_report reads the stored L once, on the device, and reports for every pivot column j (of
+ * the permuted matrix) g_j = max_i |L_ij| over the stored rows below the diagonal (relaxation zeros included) and the row p_j that
+ * attains it (the lowest front row on a tie), both kept on the device in the ORIGINAL numbering: g_out[c] and partner_out[c] describe
+ * the column that eliminates original variable c, and partner_out[c] is an original index.  A 1 x 1 pivot passes MA97's threshold test
+ * |a_jj| >= u max_{i>j} |a_ij| on the reduced matrix exactly when g_j <= 1/u, so `rejected` counts the pivots a threshold-pivoting
+ * code run with ma97_u = u would not have taken where they stand.  A column with no row below the diagonal has g = 0 and p = -1; a
+ * column that holds a NaN or an Inf has g = +Inf and p = its first such row.  In Schur mode the Schur front (it holds S, not L) is not
+ * scanned: the set's variables get g = 0, p = -1, and the interior columns keep their rows towards the set.  A scaled factor (section
+ * 8.8) is reported as stored (L~).  Deterministic: no atomics, (value, row) pairs reduced in a fixed order; two calls give identical bits.
+ * The report belongs to the factorisation it scanned: the next okkt_factor* / okkt_factor_schur* makes it stale, and the getters then
+ * return OKKT_ERR_INVALID until okkt_pivot_report runs again.  A call with another u on an unchanged factor recounts without
+ * scanning again.  The device memory (2 x dim words and the work-item lists) is allocated by the first call after an analysis and
+ * released with the analysis.
+ * Refused with OKKT_ERR_INVALID (the handle stays usable): before a complete factorisation, after an early-exit factorisation that
+ * stopped short, on partitioned handles, for u > 1 or a non-finite u; host_symbolic_only handles get OKKT_ERR_NO_DEVICE.  Accepted: a
+ * factorisation whose flag was 0, Schur mode after a complete okkt_factor_schur, scaled factors, both sym_kinds.
+ * No existing call changes: okkt_solve after okkt_pivot_report is bitwise what it was before. */
+typedef struct {
+  double u;                 /* threshold the counts refer to */
+  int64_t rejected;         /* columns with g_j > 1/u (non-finite columns included) */
+  int64_t nonfinite_cols;   /* columns that hold a NaN or an Inf */
+  double max_multiplier;    /* max_j g_j */
+  int64_t max_col;          /* original index of that column (lowest on a tie), -1 when dim = 0 */
+  double seconds_device;    /* the device time of the scan (HIP events around it; that of the last scan when only recounting) */
+} okkt_pivot_info;
+int okkt_pivot_report(okkt_handle h, double u /* (0, 1]; <= 0: 1e-8, the reference's ma97_u */, okkt_pivot_info* info /* or NULL */);
+/* g and the partners of the last report (dim entries each, original order; host / device memory).  partner_out may be NULL. */
+int okkt_get_multipliers(okkt_handle h, double* g_out, int64_t* partner_out);
+int okkt_get_multipliers_dev(okkt_handle h, double* d_g_out, int64_t* d_partner_out);
+/* the rejected columns of the last report (original indices) and their partners, descending g, ties by ascending original index;
+ * returns their number (at most cap are written; either array may be NULL), < 0 on error */
+int64_t okkt_get_rejected_pivots(okkt_handle h, int64_t* idx_out, int64_t* partner_out, int64_t cap);
+/* Refinement through the Schur route: okkt_solve_refine's loop -- the same omega, stagnation rule, best
+ * iterate, masked correction and one device-to-host read per step -- with every solve the fused whole-system solve of okkt_schur_solve.
+ * nzval: the values of the whole A on the analysed pattern (residuals are against the whole matrix).  It needs a complete
+ * okkt_factor_schur and an okkt_schur_factor of the handle's OWN S (S = NULL): after a factor of a caller's S, A is not this handle's
+ * matrix and the call is refused with OKKT_ERR_INVALID, as it is outside Schur mode and on partitioned handles.  rhs may alias sol;
+ * max_steps = 0 returns okkt_schur_solve's x. */
+int okkt_schur_solve_refine(okkt_handle h, const double* nzval, const double* rhs, double* sol, int64_t nrhs, int32_t max_steps,
+                            double tol, okkt_refine_info* info /* or NULL */, double* omega_out /* [nrhs] or NULL */);
+int okkt_schur_solve_refine_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
+                                double tol, okkt_refine_info* info, double* omega_out /* host memory */);
 
 /* ---- Symmetric equilibration before the factorisation ----------------------------------------------------
  * The factorisation never pivots; with a scaling on, okkt_factor(_dev) factors F~ = S F S for a positive diagonal S = diag(s), so that

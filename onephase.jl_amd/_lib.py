@@ -194,6 +194,21 @@ class OkktSelinvInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktPivotInfo(C.Structure):
+    """okkt_pivot_info: the threshold u, the columns with g > 1/u, the non-finite columns, max g and its column (original index)."""
+    _fields_ = [
+        ("u", C.c_double),
+        ("rejected", C.c_int64),
+        ("nonfinite_cols", C.c_int64),
+        ("max_multiplier", C.c_double),
+        ("max_col", C.c_int64),
+        ("seconds_device", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class OkktScalingInfo(C.Structure):
     """okkt_scaling_info: mode and sweeps of the current factor's scaling, the extrema of the row maxima of |S F S| over its non-zero
     rows, and the number of zero rows."""
@@ -264,6 +279,12 @@ SIGNATURES = {
     "okkt_get_inverse_on_pattern_dev": (C.c_int, [_vp, _vp]),
     "okkt_get_inverse_csc": (C.c_int, [_vp, _i64p, _i64p, _f64p, _i64p]),
     "okkt_logdet": (C.c_int, [_vp, _f64p, C.POINTER(C.c_int32)]),
+    "okkt_pivot_report": (C.c_int, [_vp, C.c_double, C.POINTER(OkktPivotInfo)]),
+    "okkt_get_multipliers": (C.c_int, [_vp, _f64p, _i64p]),
+    "okkt_get_multipliers_dev": (C.c_int, [_vp, _vp, _vp]),
+    "okkt_get_rejected_pivots": (C.c_int64, [_vp, _i64p, _i64p, C.c_int64]),
+    "okkt_schur_solve_refine": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
+    "okkt_schur_solve_refine_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
     "okkt_set_scaling": (C.c_int, [_vp, C.c_int, C.c_int32, _f64p]),
     "okkt_get_scaling": (C.c_int, [_vp, _f64p, C.POINTER(OkktScalingInfo)]),
     "okkt_get_scaling_dev": (C.c_int, [_vp, _vp]),

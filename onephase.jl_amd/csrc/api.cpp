@@ -13,6 +13,12 @@
 
 using namespace okkt;
 
+// the Schur route of the refinement loop (defined with the Schur-mode entry points below)
+extern "C" {
+static int schur_refine_ready(okkt_solver_s* h);
+static int schur_dense_sweeps(okkt_solver_s* h, const double* d_rhs, double* d_sol, int64_t nrhs, bool whole, bool sync = true);
+}
+
 namespace okkt {
 
 int solver_set_error(okkt_solver_s* h, int code, const std::string& msg) {
@@ -182,6 +188,7 @@ void solver_refine_release(okkt_solver_s* h) {
   refine_map_release(h->rf);
   condest_release(h->cd);
   selinv_release(h->sl);
+  pivots_release(h->pv);
   krylov_release(h->kr);
   dense_ldlt_release(h->dl);
   scaling_release(h->sc);
@@ -255,13 +262,18 @@ static int residual_device(okkt_solver_s* h, const double* d_nzval, const double
   return OKKT_OK;
 }
 
-int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
-                         double tol, okkt_refine_info* info, double* omega_out, void (*lap)(void*, int), void* lap_ctx, int* n_solves_out) {
+// the refinement loop over one of two solves: the factor of the whole matrix (solver_solve_enqueue), or, schur_route, the fused
+// whole-system sweeps of okkt_schur_solve
+static int refine_loop(okkt_solver_s* h, bool schur_route, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
+                       double tol, okkt_refine_info* info, double* omega_out, void (*lap)(void*, int), void* lap_ctx, int* n_solves_out) {
   if (n_solves_out) *n_solves_out = 0;
   if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
   if (max_steps < 0) return solver_set_error(h, OKKT_ERR_INVALID, "max_steps < 0");
-  int rc = refine_ready(h, true);
+  int rc = schur_route ? ::schur_refine_ready(h) : refine_ready(h, true);
   if (rc != OKKT_OK) return rc;
+  auto solve = [&](const double* src, double* dst, int64_t cnt) {
+    return schur_route ? ::schur_dense_sweeps(h, src, dst, cnt, true, false) : solver_solve_enqueue(h, src, dst, cnt, false);
+  };
   if (!(tol > 0.0)) tol = std::ldexp(1.0, -52);
   const int64_t n = h->S.n;
   okkt_refine_info I;
@@ -283,7 +295,7 @@ int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* 
   if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("refinement rhs copy: ") + hipGetErrorString(he));
   refine_gather_enqueue(h->rf, d_nzval, st);
   mark(1);
-  if ((rc = solver_solve_enqueue(h, B, d_sol, nrhs, false)) != OKKT_OK) return rc;   // x = F \ b: the batches of okkt_solve
+  if ((rc = solve(B, d_sol, nrhs)) != OKKT_OK) return rc;   // x = F \ b: the batches of okkt_solve / okkt_schur_solve
   nsolves += (int)nrhs;
   mark(0);
   const size_t Q = (size_t)nrhs;
@@ -345,7 +357,7 @@ int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* 
         if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("refinement compaction: ") + hipGetErrorString(he));
       }
     mark(1);
-    if ((rc = solver_solve_enqueue(h, R, D, (int64_t)next.size(), false)) != OKKT_OK) return rc;   // d = F \ r
+    if ((rc = solve(R, D, (int64_t)next.size())) != OKKT_OK) return rc;   // d = F \ r
     nsolves += (int)next.size();
     mark(0);
     // masked correction: only the right-hand sides that go on are touched (no solve of a zero rhs: 0 * NaN is not 0)
@@ -374,6 +386,11 @@ int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* 
   he = hipStreamSynchronize(st);
   if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("refinement: ") + hipGetErrorString(he));
   return OKKT_OK;
+}
+
+int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
+                         double tol, okkt_refine_info* info, double* omega_out, void (*lap)(void*, int), void* lap_ctx, int* n_solves_out) {
+  return refine_loop(h, false, d_nzval, d_rhs, d_sol, nrhs, max_steps, tol, info, omega_out, lap, lap_ctx, n_solves_out);
 }
 
 // ---- GMRES-based iterative refinement (krylov.hip) ---------------------------------------------
@@ -1107,7 +1124,7 @@ int okkt_analyze(okkt_handle h, int64_t dim, const int64_t* colptr, const int64_
     if (h->opts.ordering == 2 && (int64_t)h->user_perm.size() != dim)
       return solver_set_error(h, OKKT_ERR_INVALID, "ordering=user: okkt_set_perm must supply dim entries first");
     auto t0 = std::chrono::steady_clock::now();
-    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned || h->kr.V || h->dl.F || h->sc.ready)) {   // the refinement map (and Z) belong to the old pattern
+    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned || h->kr.V || h->dl.F || h->sc.ready || h->pv.planned)) {   // the refinement map (and Z) belong to the old pattern
       (void)hipSetDevice(h->device);
       (void)hipStreamSynchronize(h->stream);
       solver_refine_release(h);
@@ -1952,7 +1969,7 @@ int okkt_schur_get_factor(okkt_handle h, double* LD, int64_t ld, int32_t* ipiv) 
 }
 
 // batches of up to kMaxRhs right-hand sides; whole: the fused whole-system solve (rhs and sol of order dim), else x2 = S^-1 r2
-static int schur_dense_sweeps(okkt_solver_s* h, const double* d_rhs, double* d_sol, int64_t nrhs, bool whole) {
+static int schur_dense_sweeps(okkt_solver_s* h, const double* d_rhs, double* d_sol, int64_t nrhs, bool whole, bool sync) {
   const int64_t n = h->S.n, ns = h->S.nschur;
   double* t2 = h->dl.X + 8 * ns;      // r2 / x2 of the fused solve
   for (int64_t r = 0; r < nrhs;) {
@@ -1973,6 +1990,7 @@ static int schur_dense_sweeps(okkt_solver_s* h, const double* d_rhs, double* d_s
     if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
     r += nr;
   }
+  if (!sync) return OKKT_OK;      // the refinement loop of okkt_schur_solve_refine: its own read of omega synchronises
   return schur_sync(h, whole ? "Schur solve" : "dense Schur solve");
 }
 
@@ -2007,6 +2025,66 @@ OKKT_SCHUR_SOLVE_ENTRY(okkt_schur_dense_solve_dev, false, true)
 OKKT_SCHUR_SOLVE_ENTRY(okkt_schur_solve, true, false)
 OKKT_SCHUR_SOLVE_ENTRY(okkt_schur_solve_dev, true, true)
 #undef OKKT_SCHUR_SOLVE_ENTRY
+
+// ---- refinement through the Schur route ------------------------------------------------------------------
+
+// Schur mode, a complete okkt_factor_schur, a current dense factor of the handle's own S; the row map of the pattern (it does not
+// depend on the mode: pat_colptr / pat_rowval hold the whole pattern as okkt_analyze was given it)
+static int schur_refine_ready(okkt_solver_s* h) {
+  int rc = schur_ready(h, true);
+  if (rc == OKKT_OK) rc = schur_dense_ready(h);
+  if (rc != OKKT_OK) return rc;
+  if (!h->dl.own)
+    return solver_set_error(h, OKKT_ERR_INVALID, "okkt_schur_solve_refine: the dense factor is of a caller's S, so the factored matrix is not this handle's A (okkt_schur_factor with S = NULL first)");
+  if (h->S.nparts > 1)
+    return solver_set_error(h, OKKT_ERR_INVALID, "residuals and refinement are not available on a partitioned handle (okkt_dist_set_partition with nparts > 1)");
+  if (!h->rf.ready) {
+    std::string e = refine_map_build(h->S.n, h->pat_colptr.data(), h->pat_rowval.data(), h->pat_colptr[0], h->rf);
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, "refinement map: " + e);
+  }
+  return OKKT_OK;
+}
+
+int okkt_schur_solve_refine_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
+                                double tol, okkt_refine_info* info, double* omega_out) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs > 0 && (!d_rhs || !d_sol || (!d_nzval && h->S.nnz_in > 0))) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+  try {
+    return refine_loop(h, true, d_nzval, d_rhs, d_sol, nrhs, max_steps, tol, info, omega_out, nullptr, nullptr, nullptr);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_solve_refine_dev");
+  }
+}
+
+int okkt_schur_solve_refine(okkt_handle h, const double* nzval, const double* rhs, double* sol, int64_t nrhs, int32_t max_steps, double tol,
+                            okkt_refine_info* info, double* omega_out) {
+  if (!h) return OKKT_ERR_INVALID;
+  if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
+  if (max_steps < 0) return solver_set_error(h, OKKT_ERR_INVALID, "max_steps < 0");
+  if (nrhs > 0 && (!rhs || !sol || (!nzval && h->S.nnz_in > 0))) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+  try {
+    int rc = schur_refine_ready(h);
+    if (rc != OKKT_OK) return rc;
+    const int64_t len = h->S.n * nrhs;
+    if (len == 0) return refine_loop(h, true, nullptr, nullptr, nullptr, nrhs, max_steps, tol, info, omega_out, nullptr, nullptr, nullptr);
+    std::string e = refine_stage_alloc(h->rf);
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_ALLOC, "nzval staging: " + e);
+    if (h->rhs_stage_len < len) (void)hipStreamSynchronize(h->stream);
+    if ((rc = rhs_stage(h, len)) != OKKT_OK) return rc;
+    hipStream_t st = h->stream;
+    hipError_t he = hipSuccess;
+    if (h->S.nnz_in > 0) he = hipMemcpyAsync(h->rf.nz_stage, nzval, (size_t)h->S.nnz_in * sizeof(double), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(h->d_rhs_stage, rhs, (size_t)len * sizeof(double), hipMemcpyHostToDevice, st);
+    if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("refinement upload: ") + hipGetErrorString(he));
+    rc = refine_loop(h, true, h->rf.nz_stage, h->d_rhs_stage, h->d_rhs_stage, nrhs, max_steps, tol, info, omega_out, nullptr, nullptr, nullptr);
+    if (rc != OKKT_OK) return rc;
+    if (hipMemcpy(sol, h->d_rhs_stage, (size_t)len * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "sol download failed");
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_solve_refine");
+  }
+}
 
 // ---- selected inversion (selinv.hip) --------------------------------------------------------------------
 
@@ -2219,6 +2297,147 @@ int okkt_logdet(okkt_handle h, double* logabsdet, int32_t* sign) {
     return OKKT_OK;
   } catch (...) {
     return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_logdet");
+  }
+}
+
+// ---- threshold pivot report (pivots.hip) ------------------------------------------------------------------
+
+// device, analysis, no partition, a complete factorisation (Schur mode: a complete okkt_factor_schur); need_report: a report of it
+static int pivots_ready(okkt_solver_s* h, bool need_report) {
+  int rc = ensure_device(h);
+  if (rc != OKKT_OK) return rc;
+  if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_analyze has not been called");
+  if (h->S.nparts > 1)
+    return solver_set_error(h, OKKT_ERR_INVALID, "the pivot report is not available on a partitioned handle (okkt_dist_set_partition with nparts > 1)");
+  if ((rc = solver_ensure_numeric(h)) != OKKT_OK) return rc;
+  if (!h->factored)
+    return solver_set_error(h, OKKT_ERR_INVALID, "the pivot report needs a complete factorisation (none yet, or an early exit stopped it)");
+  if (need_report && (!h->pv.planned || h->pv.factor_seq != h->factor_seq))
+    return solver_set_error(h, OKKT_ERR_INVALID, "no pivot report of the current factorisation: call okkt_pivot_report after okkt_factor");
+  return OKKT_OK;
+}
+
+int okkt_pivot_report(okkt_handle h, double u, okkt_pivot_info* info) {
+  if (!h) return OKKT_ERR_INVALID;
+  try {
+    int rc = pivots_ready(h, false);
+    if (rc != OKKT_OK) return rc;
+    if (!std::isfinite(u) || u > 1.0) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_pivot_report: u must be finite and at most 1");
+    if (u <= 0.0) u = 1e-8;      // parameters.jl:25 (ma97_u)
+    PivotWork& W = h->pv;
+    hipStream_t st = h->stream;
+    if (!W.planned || W.analysis != h->n_analyze_calls || W.arena != h->N.d.arena) {
+      (void)hipStreamSynchronize(st);
+      std::string e = pivots_setup(h->S, h->N, W);
+      if (!e.empty()) { pivots_release(W); return solver_set_error(h, OKKT_ERR_ALLOC, "pivot report set-up: " + e); }
+      W.analysis = h->n_analyze_calls;
+      W.arena = h->N.d.arena;
+    }
+    const bool scan = W.factor_seq != h->factor_seq;
+    if (scan) {
+      W.factor_seq = -1;
+      (void)hipEventRecord(h->ev0, st);
+      std::string e = pivots_scan_enqueue(h->N, W, st);
+      if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
+      (void)hipEventRecord(h->ev1, st);
+    }
+    pivots_count_enqueue(W, 1.0 / u, st);
+    PvCount part[kPvCountBlocks];
+    hipError_t he = hipGetLastError();
+    if (he == hipSuccess) he = hipMemcpyAsync(part, W.count, sizeof(part), hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("pivot report failed: ") + hipGetErrorString(he));
+    if (scan) {
+      float ms = 0;
+      W.seconds_device = hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess ? ms * 1e-3 : 0.0;
+      W.factor_seq = h->factor_seq;
+    }
+    W.u = u;
+    W.rejected = 0; W.nonfinite_cols = 0; W.max_col = -1; W.max_multiplier = 0.0;
+    for (int b = 0; b < kPvCountBlocks; ++b) {
+      W.rejected += part[b].rejected;
+      W.nonfinite_cols += part[b].nonfinite;
+      if (part[b].max_idx < 0) continue;
+      if (W.max_col < 0 || part[b].max_g > W.max_multiplier || (part[b].max_g == W.max_multiplier && part[b].max_idx < W.max_col)) {
+        W.max_multiplier = part[b].max_g;
+        W.max_col = part[b].max_idx;
+      }
+    }
+    if (info) {
+      info->u = W.u; info->rejected = W.rejected; info->nonfinite_cols = W.nonfinite_cols;
+      info->max_multiplier = W.max_multiplier; info->max_col = W.max_col; info->seconds_device = W.seconds_device;
+    }
+    return OKKT_OK;
+  } catch (const std::bad_alloc&) {
+    return solver_set_error(h, OKKT_ERR_ALLOC, "out of host memory in okkt_pivot_report");
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_pivot_report");
+  }
+}
+
+static int pivots_copy_out(okkt_solver_s* h, double* g_out, int64_t* partner_out, hipMemcpyKind kind) {
+  const size_t n = (size_t)h->S.n;
+  hipError_t he = hipSuccess;
+  if (n > 0) he = hipMemcpyAsync(g_out, h->pv.g, n * sizeof(double), kind, h->stream);
+  if (he == hipSuccess && n > 0 && partner_out) he = hipMemcpyAsync(partner_out, h->pv.partner, n * sizeof(int64_t), kind, h->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(h->stream);
+  if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("multiplier export failed: ") + hipGetErrorString(he));
+  return OKKT_OK;
+}
+
+int okkt_get_multipliers(okkt_handle h, double* g_out, int64_t* partner_out) {
+  if (!h || !g_out) return OKKT_ERR_INVALID;
+  try {
+    int rc = pivots_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    return pivots_copy_out(h, g_out, partner_out, hipMemcpyDeviceToHost);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_get_multipliers");
+  }
+}
+
+int okkt_get_multipliers_dev(okkt_handle h, double* d_g_out, int64_t* d_partner_out) {
+  if (!h || !d_g_out) return OKKT_ERR_INVALID;
+  try {
+    int rc = pivots_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    return pivots_copy_out(h, d_g_out, d_partner_out, hipMemcpyDeviceToDevice);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_get_multipliers_dev");
+  }
+}
+
+int64_t okkt_get_rejected_pivots(okkt_handle h, int64_t* idx_out, int64_t* partner_out, int64_t cap) {
+  if (!h) return OKKT_ERR_INVALID;
+  try {
+    int rc = pivots_ready(h, true);
+    if (rc != OKKT_OK) return rc;
+    PivotWork& W = h->pv;
+    const int64_t n = h->S.n;
+    if (W.host_seq != W.factor_seq || (int64_t)W.g_host.size() != n) {
+      W.host_seq = -1;
+      W.g_host.resize((size_t)n);
+      W.partner_host.resize((size_t)n);
+      if ((rc = pivots_copy_out(h, W.g_host.data(), W.partner_host.data(), hipMemcpyDeviceToHost)) != OKKT_OK) return rc;
+      W.host_seq = W.factor_seq;
+    }
+    const double inv_u = 1.0 / W.u;
+    std::vector<int64_t> rej;
+    for (int64_t c = 0; c < n; ++c)
+      if (W.g_host[(size_t)c] > inv_u) rej.push_back(c);
+    std::sort(rej.begin(), rej.end(), [&](int64_t a, int64_t b) {
+      const double ga = W.g_host[(size_t)a], gb = W.g_host[(size_t)b];
+      return ga > gb || (ga == gb && a < b);
+    });
+    for (int64_t t = 0; t < (int64_t)rej.size() && t < cap; ++t) {
+      if (idx_out) idx_out[t] = rej[(size_t)t];
+      if (partner_out) partner_out[t] = W.partner_host[(size_t)rej[(size_t)t]];
+    }
+    return (int64_t)rej.size();
+  } catch (const std::bad_alloc&) {
+    return solver_set_error(h, OKKT_ERR_ALLOC, "out of host memory in okkt_get_rejected_pivots");
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_get_rejected_pivots");
   }
 }
 

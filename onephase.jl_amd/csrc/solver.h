@@ -10,6 +10,7 @@
 #include "dense_ldlt.h"
 #include "krylov.h"
 #include "numeric.h"
+#include "pivots.h"
 #include "refine.h"
 #include "scaling.h"
 #include "selinv.h"
@@ -78,6 +79,9 @@ struct okkt_solver_s {
   // symmetric equilibration (scaling.hip): the configuration of okkt_set_scaling (kept across analyses) and the
   // device state of the current analysis, allocated by the first scaled factorisation and released with the refinement map
   okkt::ScalingWork sc;
+  // threshold pivot report (pivots.hip): the work-item lists, g and the partners, allocated by the first
+  // okkt_pivot_report after an analysis and released with the refinement map; stale after the next factorisation (factor_seq)
+  okkt::PivotWork pv;
 };
 
 namespace okkt {

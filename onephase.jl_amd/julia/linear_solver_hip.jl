@@ -239,6 +239,55 @@ function scaling(solver::linear_solver_HIP, dim::Integer)
 end
 scaling_info(solver::linear_solver_HIP, dim::Integer) = scaling(solver, dim)[2]
 
+struct OkktPivotInfo      # okkt_pivot_info of include/okkt.h
+    u::Float64
+    rejected::Int64          # columns with g_j > 1/u: the pivots MA97 with ma97_u = u would not have taken where they stand
+    nonfinite_cols::Int64
+    max_multiplier::Float64
+    max_col::Int64           # 0-based original index, -1 when dim = 0
+    seconds_device::Float64
+end
+
+# Threshold pivot report of the current factor (DESIGN.md section 8.9): g_j = max_i |L_ij| per pivot column, counted against 1/u
+# (u <= 0: 1e-8, pars.kkt.ma97_u).  Not part of the reference interface.
+function pivot_report(solver::linear_solver_HIP, u::Float64=1e-8)
+    info = Ref(OkktPivotInfo(0.0, 0, 0, 0.0, -1, 0.0))
+    rc = ccall((:okkt_pivot_report, OKKT_LIB), Cint, (Ptr{Cvoid}, Float64, Ref{OkktPivotInfo}), solver.handle, u, info)
+    rc < 0 && okkt_error(solver, "okkt_pivot_report", rc)
+    return info[]
+end
+
+# (g, partner) of the last report in the original order; partner is 0-based, -1 for a column without a row below the diagonal
+function multipliers(solver::linear_solver_HIP, dim::Integer)
+    g = zeros(dim)
+    partner = zeros(Int64, dim)
+    rc = ccall((:okkt_get_multipliers, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}), solver.handle, g, partner)
+    rc < 0 && okkt_error(solver, "okkt_get_multipliers", rc)
+    return g, partner
+end
+
+# the rejected columns of the last report (0-based original indices) by descending g, and their partners
+function rejected_pivots(solver::linear_solver_HIP)
+    cnt = ccall((:okkt_get_rejected_pivots, OKKT_LIB), Int64, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Int64), solver.handle, C_NULL, C_NULL, 0)
+    cnt < 0 && okkt_error(solver, "okkt_get_rejected_pivots", cnt)
+    idx = zeros(Int64, cnt)
+    partner = zeros(Int64, cnt)
+    ccall((:okkt_get_rejected_pivots, OKKT_LIB), Int64, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Int64), solver.handle, idx, partner, cnt)
+    return idx, partner
+end
+
+# ls_solve_refine! through the Schur route: every solve is okkt_schur_solve's, the residuals are against the whole A.  Needs
+# okkt_factor_schur and okkt_schur_factor of the handle's own S.
+function schur_solve_refine!(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}, my_rhs::Array{Float64,1}, my_sol::Array{Float64,1};
+                             max_steps::Integer=3, tol::Float64=0.0)
+    info = Ref(OkktRefineInfo(0, 0, 0.0, 0.0, 0.0))
+    rc = ccall((:okkt_schur_solve_refine, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Float64,
+                                                           Ref{OkktRefineInfo}, Ptr{Float64}),
+               solver.handle, A.nzval, my_rhs, my_sol, 1, Int32(max_steps), tol, info, C_NULL)
+    rc < 0 && okkt_error(solver, "okkt_schur_solve_refine", rc)
+    return info[]
+end
+
 function ls_solve(solver::linear_solver_HIP, my_rhs::AbstractArray, timer::class_advanced_timer)
     rhs = Vector{Float64}(my_rhs)      # SparseVector rhs is densified, as in julia.jl:105-113
     sol = zeros(length(rhs))

@@ -71,6 +71,8 @@ class linear_solver_HIP(abstract_linear_system_solver):
         self.schur_inertia = None  # counts over D of the last schur_factor
         self.total_inertia = None  # A11's counts + S's: the whole matrix's
         self._borrowed = False  # a view on a handle another object owns (of_kkt): finalize does not destroy it
+        self._scale_mode = L.OKKT_SCALE_NONE  # the mode of the last set_scaling (ls_factor_robust refuses scaled handles)
+        self._robust_mode = None  # "plain" | "schur": the mode the last ls_factor_robust ended in
 
     # -- initialize! / finalize!
     def _initialize(self):
@@ -383,6 +385,7 @@ class linear_solver_HIP(abstract_linear_system_solver):
         if v is not None and self._dim and v.shape != (self._dim,):
             raise OkktError("s must have the analysed dimension")
         self._check(self._lib.okkt_set_scaling(self._h, mode, int(sweeps), None if v is None else L.p_f64(v)), "okkt_set_scaling")
+        self._scale_mode = mode
 
     def scaling(self):
         """s of the current factor (original order)."""
@@ -591,3 +594,129 @@ class linear_solver_HIP(abstract_linear_system_solver):
         s = C.c_int32()
         self._check(self._lib.okkt_logdet(self._h, C.byref(v), C.byref(s)), "okkt_logdet")
         return v.value, int(s.value)
+
+    # -- threshold pivot report and the robust route through the Schur set (not part of the reference interface)
+    def pivot_report(self, u=1e-8):
+        """okkt_pivot_report: scan the stored L for g_j = max_i |L_ij| and count the pivots MA97's threshold test with ma97_u = u would
+        have rejected (g_j > 1/u).  Returns okkt_pivot_info as a dict.  On `linear_solver_HIP.of_kkt(kkt)` it describes the matrix
+        okkt_kkt_factor last factored."""
+        self._need()
+        info = L.OkktPivotInfo()
+        self._check(self._lib.okkt_pivot_report(self._h, float(u), C.byref(info)), "okkt_pivot_report")
+        return info.as_dict()
+
+    def multipliers(self):
+        """(g, partner) of the last report, original order: g[c] of the column that eliminates variable c and the original index of the
+        row that attains it (-1: no row below the diagonal)."""
+        self._need()
+        g = np.zeros(self._dim)
+        p = np.zeros(self._dim, dtype=np.int64)
+        self._check(self._lib.okkt_get_multipliers(self._h, L.p_f64(g) if self._dim else L.p_f64(np.zeros(1)), L.p_i64(p) if self._dim else None),
+                    "okkt_get_multipliers")
+        return g, p
+
+    def multipliers_dev(self, d_g_out, d_partner_out=None):
+        self._need()
+        self._check(self._lib.okkt_get_multipliers_dev(self._h, C.c_void_p(d_g_out), None if d_partner_out is None else C.c_void_p(d_partner_out)),
+                    "okkt_get_multipliers_dev")
+
+    def rejected_pivots(self):
+        """(idx, partner): the rejected columns of the last report (original indices) by descending g, ties by ascending index, and
+        their partners."""
+        self._need()
+        cnt = int(self._check(self._lib.okkt_get_rejected_pivots(self._h, None, None, 0), "okkt_get_rejected_pivots"))
+        idx = np.zeros(max(cnt, 1), dtype=np.int64)
+        par = np.zeros(max(cnt, 1), dtype=np.int64)
+        self._check(self._lib.okkt_get_rejected_pivots(self._h, L.p_i64(idx), L.p_i64(par), cnt), "okkt_get_rejected_pivots")
+        return idx[:cnt], par[:cnt]
+
+    def schur_solve_refine(self, nzval_or_matrix, rhs, max_steps=3, tol=0.0):
+        """ls_solve_refine through the Schur route (okkt_schur_solve_refine): every solve is schur_solve's, the residuals are against
+        the whole A.  Needs ls_factor_schur and schur_factor() of the handle's own S.  Returns (x, info) as ls_solve_refine."""
+        self._need()
+        vals = self._values(nzval_or_matrix)
+        B, single = self._rhs_block(rhs, self._dim)
+        X = np.zeros_like(B)
+        om = np.zeros(B.shape[0])
+        info = L.OkktRefineInfo()
+        self._check(self._lib.okkt_schur_solve_refine(self._h, L.p_f64(vals), L.p_f64(B), L.p_f64(X), B.shape[0], int(max_steps), float(tol),
+                                                       C.byref(info), L.p_f64(om)), "okkt_schur_solve_refine")
+        d = info.as_dict()
+        d["omega_per_rhs"] = om
+        return (X[0] if single else X), d
+
+    def schur_solve_refine_dev(self, d_nzval, d_rhs, d_sol, nrhs=1, max_steps=3, tol=0.0):
+        self._need()
+        info = L.OkktRefineInfo()
+        om = np.zeros(max(int(nrhs), 1))
+        self._check(self._lib.okkt_schur_solve_refine_dev(self._h, C.c_void_p(d_nzval), C.c_void_p(d_rhs), C.c_void_p(d_sol), int(nrhs),
+                                                           int(max_steps), float(tol), C.byref(info), L.p_f64(om)), "okkt_schur_solve_refine_dev")
+        return info.as_dict(), om[: int(nrhs)]
+
+    def ls_factor_robust(self, A, n, m, u=1e-8, max_rounds=3, max_set=None):
+        """Factor A (inertia (n, m, 0) wanted) so that no pivot of the static-pivot part fails the threshold test with ma97_u = u.
+        Round 1 is ls_factor_b and a pivot report; while columns are rejected, they and their partners (the row a rejected 1 x 1
+        pivot lost to: Bunch-Kaufman pairs the two into a 2 x 2 block) join the Schur set, the pattern is analysed again,
+        ls_factor_schur factors the interior and the report runs on it.  At most max_rounds rounds, at most max_set set variables
+        (default max(64, ceil(sqrt(dim)))): past either an OkktError carries the last report and the handle is left without a set.
+        When a set was needed, schur_factor() factors S with pivoting and the flag is inertia_status of total_inertia against (n, m)
+        and of the dense factor's own flag; otherwise the handle stays in its ordinary mode and the flag is ls_factor_b's.
+        Returns (flag, info): info["rounds"], info["set"] (sorted original indices), info["rejected"] and info["max_multiplier"] per
+        round, info["mode"] ("plain" | "schur").  Symmetric kind only; refused while a scaling is set (Schur mode refuses scalings)."""
+        self._need()
+        if self.sym != "symmetric":
+            raise OkktError("ls_factor_robust: symmetric kind only")
+        if self._scale_mode != L.OKKT_SCALE_NONE:
+            raise OkktError("ls_factor_robust: a scaling is set on this handle and Schur mode does not factor a scaled matrix")
+        if max_rounds < 1:
+            raise OkktError("ls_factor_robust: max_rounds < 1")
+        dim = csc_arrays(A)[0]
+        if max_set is None:
+            max_set = max(64, int(np.ceil(np.sqrt(dim))))
+        if self._ns:
+            self.set_schur([])
+        self._robust_mode = None
+        cur = np.zeros(0, dtype=np.int64)
+        rejected, biggest = [], []
+        flag = 0
+        for rnd in range(1, max_rounds + 1):
+            if len(cur) == 0:
+                flag = self.ls_factor_b(A, n, m)
+            else:
+                self.set_schur(cur)
+                self.analyze(A)
+                n_in = int(np.count_nonzero(cur < n))
+                self.ls_factor_schur(A, n - n_in, m - (len(cur) - n_in))
+            rep = self.pivot_report(u)
+            rejected.append(int(rep["rejected"]))
+            biggest.append(float(rep["max_multiplier"]))
+            if rep["rejected"] == 0:
+                break
+            idx, par = self.rejected_pivots()
+            grown = np.union1d(cur, np.union1d(idx, par[par >= 0])).astype(np.int64)
+            why = None
+            if rnd == max_rounds:
+                why = f"columns are still rejected after {max_rounds} rounds"
+            elif len(grown) > max_set or len(grown) >= dim:
+                why = f"the Schur set would grow to {len(grown)} variables (max_set = {max_set})"
+            if why is not None:
+                self.set_schur([])
+                raise OkktError(f"ls_factor_robust: {why}; last report: {rep}, rejected per round {rejected}")
+            cur = grown
+        info = {"rounds": len(rejected), "set": cur, "rejected": rejected, "max_multiplier": biggest, "mode": "schur" if len(cur) else "plain"}
+        if len(cur):
+            dense_flag = self.schur_factor()
+            pos, neg, zero, nonfinite = self.total_inertia
+            flag = int(dense_flag == 1 and nonfinite == 0 and inertia_status(pos, neg, zero, n, m))
+        self._robust_mode = info["mode"]
+        return flag, info
+
+    def ls_solve_robust(self, A_or_nzval, rhs, max_steps=5):
+        """Solve with the factorisation of ls_factor_robust and refine against A: ls_solve_refine when it ended in the ordinary mode,
+        schur_solve_refine when it ended in Schur mode.  Returns (x, info) as ls_solve_refine."""
+        mode = self._robust_mode
+        if mode is None:
+            raise OkktError("ls_solve_robust: ls_factor_robust has not succeeded on this solver")
+        if mode == "schur":
+            return self.schur_solve_refine(A_or_nzval, rhs, max_steps=max_steps)
+        return self.ls_solve_refine(A_or_nzval, rhs, max_steps=max_steps)
