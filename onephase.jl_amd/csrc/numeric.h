@@ -95,9 +95,6 @@ struct DevPlan {
   // dataflow factorisation of the big fronts (dataflow.hip): per tile (i, j) of a big front's 128-block grid the number of tasks that
   // have been applied to it (updates, then the factorisation of the tile itself), TB x TB ints per front
   int df_early_pub = 1;              // multi-tile update tasks: a row tile is published as soon as its stores have drained (dataflow.hip, df_syrk_tiles)
-  int df_dbg_half = 0;               // timing experiment: bulk update tasks skip the products of every other operand chunk (wrong numbers)
-  int df_chain = 0;                  // chained update tasks: least distance (block columns) of a chained tile from its group's last panel; 0 = off (dataflow.hip, df_syrk_chain; OKKT_DF_CHAIN)
-  int df_macro = 1;                  // update tasks on pairs of row tiles run as one macro tile (dataflow.hip, df_syrk_macro; OKKT_DF_MACRO=0: tile after tile)
   int* df_state = nullptr;
   int64_t* df_state_pos = nullptr;   // [nsuper] offset of the front's states, -1 for small fronts
 };
@@ -109,7 +106,7 @@ struct DfFront { int s, f, k; };
 // queue of the fronts of one level in the start order of a simulated list schedule on `workers` workers; `group` panels per
 // update task where the tile allows it; model_us = the simulated makespan
 void df_build_queue(const std::vector<DfFront>& fronts, int workers, int group, int rows_per_task, bool fuse_d, bool split_tu, std::vector<DfTask>& out, double* model_us,
-                    bool fuse_tl = false, bool lockstep = false, bool multi_rows = true);
+                    bool fuse_tl = false, bool multi_rows = true);
 
 // largest front order a partitioned plan (okkt_dist_*, dist.cpp) accepts: its f x f buffers keep 32-bit local offsets (f * f < 2^31);
 // single-GPU plans have no such limit
@@ -218,7 +215,6 @@ struct Numeric {
   int64_t arena_doubles = 0;               // doubles of the front arena as allocated (panels + the shared contribution-block region)
   int64_t cb_region_doubles = 0;           // ... of which the contribution-block region
   int release_cb = 1;                      // OKKT_RELEASE_CB (0: every front keeps its f x f buffer for the plan's lifetime)
-  int df_lockstep = 0;                 // TU(q) in lockstep with the 32-column blocks of D(q) (df_tu_lock; OKKT_DF_LOCKSTEP=0: the split TA / TU of rounds 4 - 5 behind the whole of D(q))
   int df_fuse_tl = 1;                  // T(i, q) with the last update of its tile inside the task (TL), q >= 1 (OKKT_DF_FUSE_TL=0: separate tasks)
   int df_rows = 1;                     // row tiles per bulk update task (OKKT_DF_ROWS; 2 and 4 measured slower: the coarser tasks cost the schedule more than the shared prologue saves)
   int df_workers = 256;                // workers of the simulated schedule (and the grid of the launch): one workgroup per CU
@@ -290,7 +286,7 @@ std::string numeric_solve_enqueue(Numeric& N, int R);
 void launch_set_shift(const Numeric& N, double delta, int64_t nshift);
 // dataflow.hip: the big fronts of one level (class-3 segment g, already assembled) as one persistent launch on `st`
 std::string df_setup(Numeric& N);
-const char* df_build_flags();      // which optional roles the dataflow kernel of this library carries (dataflow.hip)
+const char* df_build_flags();      // "log=1": the dataflow kernel of this library carries the task-log instrumentation (dataflow.hip)
 std::string df_launch(Numeric& N, const DevPlan& P, const Segment& g, hipStream_t st, double tol);
 
 }  // namespace okkt
