@@ -383,6 +383,42 @@ int okkt_schur_solve_refine(okkt_handle h, const double* nzval, const double* rh
                             double tol, okkt_refine_info* info /* or NULL */, double* omega_out /* [nrhs] or NULL */);
 int okkt_schur_solve_refine_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
                                 double tol, okkt_refine_info* info, double* omega_out /* host memory */);
+/* ---- The Schur route made whole ---------------------------------------------------------------------------
+ * What judges and rescues a doubtful factor, for a handle in Schur mode: every call below takes A^-1 to be the fused whole-system
+ * solve of okkt_schur_solve (the interior's static factor and the Bunch-Kaufman factor of S).  The plain calls (okkt_selinv,
+ * okkt_logdet, okkt_condest, okkt_forward_error, okkt_solve_gmres) keep refusing a handle in Schur mode.  Except okkt_schur_get_inverse
+ * every call needs what okkt_schur_solve_refine needs: a complete okkt_factor_schur and a current okkt_schur_factor of the handle's OWN
+ * S; outside Schur mode, before or after a stale okkt_schur_factor, after a factor of a caller's S and on partitioned handles they
+ * return OKKT_ERR_INVALID, on a host_symbolic_only handle OKKT_ERR_NO_DEVICE.  Two calls on one factor give the same bits.
+ *
+ * okkt_schur_get_inverse: Z (ns x ns, column-major, ld >= ns, set order) = S^-1 from the current dense factor, of the handle's own S
+ * or of a caller's; both triangles are written and are bitwise mirror images.  Zero or non-finite pivots divide as they divide: the call
+ * succeeds and okkt_schur_inverse_nonfinite returns the number of non-finite entries of the Z handed out last.  The device time of
+ * the call is left in okkt_stats.last_solve_ms. */
+int okkt_schur_get_inverse(okkt_handle h, double* Z, int64_t ld);
+int okkt_schur_get_inverse_dev(okkt_handle h, double* d_Z, int64_t ld);
+int64_t okkt_schur_inverse_nonfinite(okkt_handle h);
+/* Selected inversion through the route: Z = A^-1 on the pattern of the whole factor -- the interior supernodes' panels and the full
+ * lower triangle on the set (S^-1 above seeds the Schur front's panel, the top-down schedule of okkt_selinv runs below it).
+ * Afterwards okkt_get_inverse_diag / _on_pattern / _csc (and _dev) serve this Z on the Schur-mode handle, until the next
+ * okkt_factor_schur or okkt_schur_factor; before it they answer that there is no selected inverse. */
+int okkt_schur_selinv(okkt_handle h, okkt_selinv_info* info /* or NULL */);
+/* log |det A| and its sign (0 on a zero or NaN pivot) from the interior's D and the 1 x 1 and 2 x 2 blocks of the dense D */
+int okkt_schur_logdet(okkt_handle h, double* logabsdet, int32_t* sign);
+/* okkt_condest / okkt_forward_error (section 8.3) with Y = A^-1 X through the route; nzval: the values of the whole A on the analysed
+ * pattern, which the 1-norm and the residuals are taken of.  okkt_condest_indices reports the unit vectors as after okkt_condest. */
+int okkt_schur_condest(okkt_handle h, const double* nzval, int32_t t /* 1..4, <=0: 2 */, okkt_condest_info* info);
+int okkt_schur_condest_dev(okkt_handle h, const double* d_nzval, int32_t t, okkt_condest_info* info);
+int okkt_schur_forward_error(okkt_handle h, const double* nzval, const double* rhs, const double* x, int64_t nrhs,
+                             double* ferr_out /* [nrhs] */, double* berr_out /* [nrhs] or NULL */);
+int okkt_schur_forward_error_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, const double* d_x, int64_t nrhs,
+                                 double* ferr_out /* host memory */, double* berr_out /* host memory or NULL */);
+/* okkt_solve_gmres (section 8.6) with the initial solve and the preconditioner applications through the route; max_iters = 0 returns
+ * okkt_schur_solve's x bit for bit.  rhs may alias sol. */
+int okkt_schur_solve_gmres(okkt_handle h, const double* nzval, const double* rhs, double* sol, int64_t nrhs, int32_t restart,
+                           int32_t max_iters, double tol, okkt_gmres_info* info /* or NULL */, double* omega_out /* [nrhs] or NULL */);
+int okkt_schur_solve_gmres_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
+                               int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out /* host memory */);
 
 /* ---- Symmetric equilibration before the factorisation ----------------------------------------------------
  * The factorisation never pivots; with a scaling on, okkt_factor(_dev) factors F~ = S F S for a positive diagonal S = diag(s), so that

@@ -285,6 +285,19 @@ SIGNATURES = {
     "okkt_get_rejected_pivots": (C.c_int64, [_vp, _i64p, _i64p, C.c_int64]),
     "okkt_schur_solve_refine": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
     "okkt_schur_solve_refine_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
+    "okkt_schur_get_inverse": (C.c_int, [_vp, _f64p, C.c_int64]),
+    "okkt_schur_get_inverse_dev": (C.c_int, [_vp, _vp, C.c_int64]),
+    "okkt_schur_inverse_nonfinite": (C.c_int64, [_vp]),
+    "okkt_schur_selinv": (C.c_int, [_vp, C.POINTER(OkktSelinvInfo)]),
+    "okkt_schur_logdet": (C.c_int, [_vp, _f64p, C.POINTER(C.c_int32)]),
+    "okkt_schur_condest": (C.c_int, [_vp, _f64p, C.c_int32, C.POINTER(OkktCondestInfo)]),
+    "okkt_schur_condest_dev": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OkktCondestInfo)]),
+    "okkt_schur_forward_error": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, _f64p, _f64p]),
+    "okkt_schur_forward_error_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _f64p, _f64p]),
+    "okkt_schur_solve_gmres": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(OkktGmresInfo),
+                                         _f64p]),
+    "okkt_schur_solve_gmres_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(OkktGmresInfo),
+                                             _f64p]),
     "okkt_set_scaling": (C.c_int, [_vp, C.c_int, C.c_int32, _f64p]),
     "okkt_get_scaling": (C.c_int, [_vp, _f64p, C.POINTER(OkktScalingInfo)]),
     "okkt_get_scaling_dev": (C.c_int, [_vp, _vp]),

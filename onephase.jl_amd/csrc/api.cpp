@@ -182,6 +182,18 @@ int solver_solve_device(okkt_solver_s* h, const double* d_rhs, double* d_sol, in
   return OKKT_OK;
 }
 
+// A^-1 for the drivers that run on either route: the factor of the whole matrix, or, schur_route, the fused
+// whole-system sweeps of okkt_schur_solve.  No synchronisation
+static int route_solve_enqueue(okkt_solver_s* h, bool schur_route, const double* d_rhs, double* d_sol, int64_t nrhs) {
+  return schur_route ? ::schur_dense_sweeps(h, d_rhs, d_sol, nrhs, true, false) : solver_solve_enqueue(h, d_rhs, d_sol, nrhs, false);
+}
+
+// the Schur route's gate: a device, then the rules of okkt_schur_solve_refine
+static int schur_route_ready(okkt_solver_s* h) {
+  int rc = ensure_device(h);
+  return rc != OKKT_OK ? rc : ::schur_refine_ready(h);
+}
+
 // ---- refinement with extra-precise residuals (refine.hip) ------------------------------------
 
 void solver_refine_release(okkt_solver_s* h) {
@@ -271,9 +283,7 @@ static int refine_loop(okkt_solver_s* h, bool schur_route, const double* d_nzval
   if (max_steps < 0) return solver_set_error(h, OKKT_ERR_INVALID, "max_steps < 0");
   int rc = schur_route ? ::schur_refine_ready(h) : refine_ready(h, true);
   if (rc != OKKT_OK) return rc;
-  auto solve = [&](const double* src, double* dst, int64_t cnt) {
-    return schur_route ? ::schur_dense_sweeps(h, src, dst, cnt, true, false) : solver_solve_enqueue(h, src, dst, cnt, false);
-  };
+  auto solve = [&](const double* src, double* dst, int64_t cnt) { return route_solve_enqueue(h, schur_route, src, dst, cnt); };
   if (!(tol > 0.0)) tol = std::ldexp(1.0, -52);
   const int64_t n = h->S.n;
   okkt_refine_info I;
@@ -443,12 +453,12 @@ void gmres_solve_y(const GmresCycle& c, double* y) {
 }  // namespace
 
 int solver_gmres_device(okkt_solver_s* h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
-                        int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out) {
+                        int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out, bool schur_route) {
   if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
   if (max_iters < 0) return solver_set_error(h, OKKT_ERR_INVALID, "max_iters < 0");
   if (restart > kKryMaxRestart) return solver_set_error(h, OKKT_ERR_INVALID, "restart > 64");
   if (restart <= 0) restart = 30;
-  int rc = refine_ready(h, true);
+  int rc = schur_route ? schur_route_ready(h) : refine_ready(h, true);
   if (rc != OKKT_OK) return rc;
   if (!(tol > 0.0)) tol = std::ldexp(1.0, -52);
   const int64_t n = h->S.n;
@@ -477,7 +487,7 @@ int solver_gmres_device(okkt_solver_s* h, const double* d_nzval, const double* d
     double* X = d_sol + q0 * n;                  // system g of the group: column q0 + g
     hipError_t he = hipMemcpyAsync(K.B, d_rhs + q0 * n, (size_t)(G * n) * sizeof(double), hipMemcpyDeviceToDevice, st);
     if (he != hipSuccess) return hip_fail(he, "GMRES rhs copy");
-    if ((rc = solver_solve_enqueue(h, K.B, X, G, false)) != OKKT_OK) return rc;   // x = F \ b: okkt_solve's batch
+    if ((rc = route_solve_enqueue(h, schur_route, K.B, X, G)) != OKKT_OK) return rc;   // x = F \ b: okkt_solve's / okkt_schur_solve's batch
     ++nsolves;
     double wprev[4] = {0, 0, 0, 0}, rprev[4] = {0, 0, 0, 0};
     std::vector<int> act;                        // systems of the group that go on; outer slot k belongs to act[k]
@@ -564,7 +574,7 @@ int solver_gmres_device(okkt_solver_s* h, const double* d_nzval, const double* d
           }
           zin = K.P;
         }
-        if ((rc = solver_solve_enqueue(h, zin, K.Z, nl, false)) != OKKT_OK) return rc;   // z = F^-1 v_j
+        if ((rc = route_solve_enqueue(h, schur_route, zin, K.Z, nl)) != OKKT_OK) return rc;   // z = F^-1 v_j
         ++nsolves;
         ResidSet OS;
         KrySet AS;
@@ -610,7 +620,7 @@ int solver_gmres_device(okkt_solver_s* h, const double* d_nzval, const double* d
       if (ne > 0) {
         for (int s = ne; s < 4; ++s) { CB.v[s] = CB.v[0]; CB.u[s] = CB.u[0]; CB.m[s] = 0; }
         krylov_combine_enqueue(n, CB, ne, st);
-        if ((rc = solver_solve_enqueue(h, K.U, K.Z, ne, false)) != OKKT_OK) return rc;   // d = F^-1 (V y)
+        if ((rc = route_solve_enqueue(h, schur_route, K.U, K.Z, ne)) != OKKT_OK) return rc;   // d = F^-1 (V y)
         ++nsolves;
         UpdateSet U;
         for (int s = 0; s < 4; ++s) {
@@ -641,12 +651,17 @@ int solver_gmres_device(okkt_solver_s* h, const double* d_nzval, const double* d
 // ---- condition estimation and forward error bounds (condest.hip) -----------------------------
 
 // device, analysis, no partition, a complete factorisation; the refinement map and the estimator's blocks
-static int condest_ready(okkt_solver_s* h) {
-  if (schur_mode(h)) return schur_refuse(h, "the condition estimate / forward error bound");
-  int rc = refine_ready(h, false);
-  if (rc != OKKT_OK) return rc;
-  if (!h->numeric_ready || !h->factored)
-    return solver_set_error(h, OKKT_ERR_INVALID, "condition estimate called before a complete factorisation (none yet, or an early exit stopped it)");
+static int condest_ready(okkt_solver_s* h, bool schur_route = false) {
+  if (schur_route) {
+    int rc = schur_route_ready(h);
+    if (rc != OKKT_OK) return rc;
+  } else {
+    if (schur_mode(h)) return schur_refuse(h, "the condition estimate / forward error bound");
+    int rc = refine_ready(h, false);
+    if (rc != OKKT_OK) return rc;
+    if (!h->numeric_ready || !h->factored)
+      return solver_set_error(h, OKKT_ERR_INVALID, "condition estimate called before a complete factorisation (none yet, or an early exit stopped it)");
+  }
   std::string e = condest_alloc(h->S.n, h->cd);
   if (!e.empty()) return solver_set_error(h, OKKT_ERR_ALLOC, "condition estimator blocks: " + e);
   return OKKT_OK;
@@ -655,8 +670,8 @@ static int condest_ready(okkt_solver_s* h) {
 // Higham-Tisseur Algorithm 2.4 for op = diag(f) F^-1 (f NULL: F^-1), op' = F^-1 diag(f), t columns (1 <= t <= min(n, 4)).  Y = op X and
 // Z = op' S are one solve pass each, every pass followed by one read of the small buffer W.out (first: its copy at the first read,
 // which carries what was enqueued before the estimate: ||F||_1, ||x||_inf).  est: the estimate (Inf for status 3).
-static int condest_run(okkt_solver_s* h, int t, const double* f, double* est_out, int* iters_out, int* solves_out, int* status_out,
-                       double* first) {
+static int condest_run(okkt_solver_s* h, bool schur_route, int t, const double* f, double* est_out, int* iters_out, int* solves_out,
+                       int* status_out, double* first) {
   CondestWork& W = h->cd;
   const int64_t n = h->S.n;
   const int64_t H = std::min<int64_t>(n, 4);
@@ -692,7 +707,7 @@ static int condest_run(okkt_solver_s* h, int t, const double* f, double* est_out
   uint64_t next_draw = (uint64_t)t;
   const double dn = (double)n;
   for (int k = 1;; ++k) {
-    if ((rc = solver_solve_enqueue(h, W.X, W.Y, t, false)) != OKKT_OK) return rc;    // Y = F^-1 X
+    if ((rc = route_solve_enqueue(h, schur_route, W.X, W.Y, t)) != OKKT_OK) return rc;    // Y = F^-1 X
     ++solves;
     condest_ystats_enqueue(W, t, cur, has_old, f, st);
     if ((rc = read()) != OKKT_OK) return rc;
@@ -735,7 +750,7 @@ static int condest_run(okkt_solver_s* h, int t, const double* f, double* est_out
         }
       }
     for (int a = 0; a < t; ++a) cls_old[a] = cls[a];
-    if ((rc = solver_solve_enqueue(h, f ? W.SF : W.S[cur], W.Y, t, false)) != OKKT_OK) return rc;   // Z = F^-1 diag(f) S
+    if ((rc = route_solve_enqueue(h, schur_route, f ? W.SF : W.S[cur], W.Y, t)) != OKKT_OK) return rc;   // Z = F^-1 diag(f) S
     ++solves;
     ++iters;
     condest_zstats_enqueue(W, t, k >= 2 ? ind_best : -1, st);
@@ -775,8 +790,8 @@ static int condest_run(okkt_solver_s* h, int t, const double* f, double* est_out
   return OKKT_OK;
 }
 
-int solver_condest_device(okkt_solver_s* h, const double* d_nzval, int32_t t, okkt_condest_info* info) {
-  int rc = condest_ready(h);
+int solver_condest_device(okkt_solver_s* h, const double* d_nzval, int32_t t, okkt_condest_info* info, bool schur_route) {
+  int rc = condest_ready(h, schur_route);
   if (rc != OKKT_OK) return rc;
   okkt_condest_info I;
   std::memset(&I, 0, sizeof(I));
@@ -789,7 +804,7 @@ int solver_condest_device(okkt_solver_s* h, const double* d_nzval, int32_t t, ok
   refine_gather_enqueue(h->rf, d_nzval, st);
   condest_norm1_enqueue(h->rf, h->cd, h->N.d.diagadd, h->N.d.perm, st);
   double first[kCdOut], est = 0.0;
-  if ((rc = condest_run(h, t, nullptr, &est, &I.iterations, &I.solves, &I.status, first)) != OKKT_OK) return rc;
+  if ((rc = condest_run(h, schur_route, t, nullptr, &est, &I.iterations, &I.solves, &I.status, first)) != OKKT_OK) return rc;
   I.norm1 = first[kCdN];
   I.inv_norm1 = est;
   I.cond1 = I.status == 3 ? INFINITY : I.norm1 * est;
@@ -798,9 +813,9 @@ int solver_condest_device(okkt_solver_s* h, const double* d_nzval, int32_t t, ok
 }
 
 int solver_forward_error_device(okkt_solver_s* h, const double* d_nzval, const double* d_b, const double* d_x, int64_t nrhs, double* ferr_out,
-                                double* berr_out) {
+                                double* berr_out, bool schur_route) {
   if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
-  int rc = condest_ready(h);
+  int rc = condest_ready(h, schur_route);
   if (rc != OKKT_OK) return rc;
   const int64_t n = h->S.n;
   h->cd_hist.clear();
@@ -830,7 +845,7 @@ int solver_forward_error_device(okkt_solver_s* h, const double* d_nzval, const d
       condest_fweights_enqueue(h->rf, W, W.R + (int64_t)k * n, W.DEN + (int64_t)k * n, d_x + q * n, st);
       double first[kCdOut], est = 0.0;
       int iters = 0, solves = 0, status = 0;
-      if ((rc = condest_run(h, t, W.f, &est, &iters, &solves, &status, first)) != OKKT_OK) return rc;
+      if ((rc = condest_run(h, schur_route, t, W.f, &est, &iters, &solves, &status, first)) != OKKT_OK) return rc;
       const double xn = first[kCdN + 2];
       ferr_out[q] = status == 3 ? INFINITY : (xn > 0.0 ? est / xn : (xn == 0.0 ? est : NAN));
     }
@@ -1488,29 +1503,40 @@ int okkt_solve_refine(okkt_handle h, const double* nzval, const double* rhs, dou
   }
 }
 
-int okkt_solve_gmres_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
-                         int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out) {
+// okkt_solve_gmres_dev / okkt_solve_gmres and their twins through the Schur route
+static int gmres_dev_entry(okkt_handle h, bool schur_route, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
+                           int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out) {
   if (!h) return OKKT_ERR_INVALID;
   if (nrhs > 0 && (!d_rhs || !d_sol || (!d_nzval && h->S.nnz_in > 0))) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
   try {
-    return solver_gmres_device(h, d_nzval, d_rhs, d_sol, nrhs, restart, max_iters, tol, info, omega_out);
+    return solver_gmres_device(h, d_nzval, d_rhs, d_sol, nrhs, restart, max_iters, tol, info, omega_out, schur_route);
   } catch (...) {
-    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_solve_gmres_dev");
+    return solver_set_error(h, OKKT_ERR_INTERNAL, schur_route ? "unexpected exception in okkt_schur_solve_gmres_dev" : "unexpected exception in okkt_solve_gmres_dev");
   }
 }
 
-int okkt_solve_gmres(okkt_handle h, const double* nzval, const double* rhs, double* sol, int64_t nrhs, int32_t restart, int32_t max_iters,
-                     double tol, okkt_gmres_info* info, double* omega_out) {
+int okkt_solve_gmres_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
+                         int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out) {
+  return gmres_dev_entry(h, false, d_nzval, d_rhs, d_sol, nrhs, restart, max_iters, tol, info, omega_out);
+}
+
+int okkt_schur_solve_gmres_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
+                               int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out) {
+  return gmres_dev_entry(h, true, d_nzval, d_rhs, d_sol, nrhs, restart, max_iters, tol, info, omega_out);
+}
+
+static int gmres_host_entry(okkt_handle h, bool schur_route, const double* nzval, const double* rhs, double* sol, int64_t nrhs, int32_t restart,
+                            int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out) {
   if (!h) return OKKT_ERR_INVALID;
   if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
   if (max_iters < 0) return solver_set_error(h, OKKT_ERR_INVALID, "max_iters < 0");
   if (restart > kKryMaxRestart) return solver_set_error(h, OKKT_ERR_INVALID, "restart > 64");
   if (nrhs > 0 && (!rhs || !sol || (!nzval && h->S.nnz_in > 0))) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
   try {
-    int rc = refine_ready(h, true);
+    int rc = schur_route ? schur_route_ready(h) : refine_ready(h, true);
     if (rc != OKKT_OK) return rc;
     const int64_t len = h->S.n * nrhs;
-    if (len == 0) return solver_gmres_device(h, nullptr, nullptr, nullptr, nrhs, restart, max_iters, tol, info, omega_out);
+    if (len == 0) return solver_gmres_device(h, nullptr, nullptr, nullptr, nrhs, restart, max_iters, tol, info, omega_out, schur_route);
     std::string e = refine_stage_alloc(h->rf);
     if (!e.empty()) return solver_set_error(h, OKKT_ERR_ALLOC, "nzval staging: " + e);
     if (h->rhs_stage_len < len) {
@@ -1527,31 +1553,45 @@ int okkt_solve_gmres(okkt_handle h, const double* nzval, const double* rhs, doub
     if (h->S.nnz_in > 0) he = hipMemcpyAsync(h->rf.nz_stage, nzval, (size_t)h->S.nnz_in * sizeof(double), hipMemcpyHostToDevice, st);
     if (he == hipSuccess) he = hipMemcpyAsync(h->d_rhs_stage, rhs, (size_t)len * sizeof(double), hipMemcpyHostToDevice, st);
     if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("GMRES upload: ") + hipGetErrorString(he));
-    rc = solver_gmres_device(h, h->rf.nz_stage, h->d_rhs_stage, h->d_rhs_stage, nrhs, restart, max_iters, tol, info, omega_out);
+    rc = solver_gmres_device(h, h->rf.nz_stage, h->d_rhs_stage, h->d_rhs_stage, nrhs, restart, max_iters, tol, info, omega_out, schur_route);
     if (rc != OKKT_OK) return rc;
     if (hipMemcpy(sol, h->d_rhs_stage, (size_t)len * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
       return solver_set_error(h, OKKT_ERR_HIP, "sol download failed");
     return OKKT_OK;
   } catch (...) {
-    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_solve_gmres");
+    return solver_set_error(h, OKKT_ERR_INTERNAL, schur_route ? "unexpected exception in okkt_schur_solve_gmres" : "unexpected exception in okkt_solve_gmres");
   }
 }
 
-int okkt_condest_dev(okkt_handle h, const double* d_nzval, int32_t t, okkt_condest_info* info) {
+int okkt_solve_gmres(okkt_handle h, const double* nzval, const double* rhs, double* sol, int64_t nrhs, int32_t restart, int32_t max_iters,
+                     double tol, okkt_gmres_info* info, double* omega_out) {
+  return gmres_host_entry(h, false, nzval, rhs, sol, nrhs, restart, max_iters, tol, info, omega_out);
+}
+
+int okkt_schur_solve_gmres(okkt_handle h, const double* nzval, const double* rhs, double* sol, int64_t nrhs, int32_t restart, int32_t max_iters,
+                           double tol, okkt_gmres_info* info, double* omega_out) {
+  return gmres_host_entry(h, true, nzval, rhs, sol, nrhs, restart, max_iters, tol, info, omega_out);
+}
+
+// okkt_condest_dev / okkt_condest and their twins through the Schur route
+static int condest_dev_entry(okkt_handle h, bool schur_route, const double* d_nzval, int32_t t, okkt_condest_info* info) {
   if (!h) return OKKT_ERR_INVALID;
   if (!d_nzval && h->S.nnz_in > 0) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
   try {
-    return solver_condest_device(h, d_nzval, t, info);
+    return solver_condest_device(h, d_nzval, t, info, schur_route);
   } catch (...) {
-    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_condest_dev");
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in the condition estimate");
   }
 }
 
-int okkt_condest(okkt_handle h, const double* nzval, int32_t t, okkt_condest_info* info) {
+int okkt_condest_dev(okkt_handle h, const double* d_nzval, int32_t t, okkt_condest_info* info) { return condest_dev_entry(h, false, d_nzval, t, info); }
+int okkt_schur_condest_dev(okkt_handle h, const double* d_nzval, int32_t t, okkt_condest_info* info) { return condest_dev_entry(h, true, d_nzval, t, info); }
+
+static int condest_host_entry(okkt_handle h, bool schur_route, const double* nzval, int32_t t, okkt_condest_info* info) {
   if (!h) return OKKT_ERR_INVALID;
   if (!nzval && h->S.nnz_in > 0) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
   try {
-    int rc = condest_ready(h);
+    int rc = condest_ready(h, schur_route);
     if (rc != OKKT_OK) return rc;
     std::string e = refine_stage_alloc(h->rf);
     if (!e.empty()) return solver_set_error(h, OKKT_ERR_ALLOC, "nzval staging: " + e);
@@ -1559,11 +1599,14 @@ int okkt_condest(okkt_handle h, const double* nzval, int32_t t, okkt_condest_inf
       hipError_t he = hipMemcpyAsync(h->rf.nz_stage, nzval, (size_t)h->S.nnz_in * sizeof(double), hipMemcpyHostToDevice, h->stream);
       if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("nzval upload: ") + hipGetErrorString(he));
     }
-    return solver_condest_device(h, h->rf.nz_stage, t, info);
+    return solver_condest_device(h, h->rf.nz_stage, t, info, schur_route);
   } catch (...) {
-    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_condest");
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in the condition estimate");
   }
 }
+
+int okkt_condest(okkt_handle h, const double* nzval, int32_t t, okkt_condest_info* info) { return condest_host_entry(h, false, nzval, t, info); }
+int okkt_schur_condest(okkt_handle h, const double* nzval, int32_t t, okkt_condest_info* info) { return condest_host_entry(h, true, nzval, t, info); }
 
 int64_t okkt_condest_indices(okkt_handle h, int64_t* ind_out, int64_t cap) {
   if (!h || (cap > 0 && !ind_out)) return OKKT_ERR_INVALID;
@@ -1572,24 +1615,35 @@ int64_t okkt_condest_indices(okkt_handle h, int64_t* ind_out, int64_t cap) {
   return cnt;
 }
 
-int okkt_forward_error_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, const double* d_x, int64_t nrhs, double* ferr_out,
-                           double* berr_out) {
+// okkt_forward_error_dev / okkt_forward_error and their twins through the Schur route
+static int ferr_dev_entry(okkt_handle h, bool schur_route, const double* d_nzval, const double* d_rhs, const double* d_x, int64_t nrhs, double* ferr_out,
+                          double* berr_out) {
   if (!h) return OKKT_ERR_INVALID;
   if (nrhs > 0 && (!d_rhs || !d_x || !ferr_out || (!d_nzval && h->S.nnz_in > 0))) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
   try {
-    return solver_forward_error_device(h, d_nzval, d_rhs, d_x, nrhs, ferr_out, berr_out);
+    return solver_forward_error_device(h, d_nzval, d_rhs, d_x, nrhs, ferr_out, berr_out, schur_route);
   } catch (...) {
-    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_forward_error_dev");
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in the forward error bound");
   }
 }
 
-int okkt_forward_error(okkt_handle h, const double* nzval, const double* rhs, const double* x, int64_t nrhs, double* ferr_out,
-                       double* berr_out) {
+int okkt_forward_error_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, const double* d_x, int64_t nrhs, double* ferr_out,
+                           double* berr_out) {
+  return ferr_dev_entry(h, false, d_nzval, d_rhs, d_x, nrhs, ferr_out, berr_out);
+}
+
+int okkt_schur_forward_error_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, const double* d_x, int64_t nrhs, double* ferr_out,
+                                 double* berr_out) {
+  return ferr_dev_entry(h, true, d_nzval, d_rhs, d_x, nrhs, ferr_out, berr_out);
+}
+
+static int ferr_host_entry(okkt_handle h, bool schur_route, const double* nzval, const double* rhs, const double* x, int64_t nrhs, double* ferr_out,
+                           double* berr_out) {
   if (!h) return OKKT_ERR_INVALID;
   if (nrhs < 0) return solver_set_error(h, OKKT_ERR_INVALID, "nrhs < 0");
   if (nrhs > 0 && (!rhs || !x || !ferr_out || (!nzval && h->S.nnz_in > 0))) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
   try {
-    int rc = condest_ready(h);
+    int rc = condest_ready(h, schur_route);
     if (rc != OKKT_OK) return rc;
     const int64_t len = nrhs * h->S.n;
     std::string e = refine_stage_alloc(h->rf);
@@ -1603,10 +1657,20 @@ int okkt_forward_error(okkt_handle h, const double* nzval, const double* rhs, co
     if (he == hipSuccess && len > 0) he = hipMemcpyAsync(db, rhs, (size_t)len * sizeof(double), hipMemcpyHostToDevice, st);
     if (he == hipSuccess && len > 0) he = hipMemcpyAsync(dxv, x, (size_t)len * sizeof(double), hipMemcpyHostToDevice, st);
     if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("forward error upload: ") + hipGetErrorString(he));
-    return solver_forward_error_device(h, h->rf.nz_stage, db, dxv, nrhs, ferr_out, berr_out);
+    return solver_forward_error_device(h, h->rf.nz_stage, db, dxv, nrhs, ferr_out, berr_out, schur_route);
   } catch (...) {
-    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_forward_error");
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in the forward error bound");
   }
+}
+
+int okkt_forward_error(okkt_handle h, const double* nzval, const double* rhs, const double* x, int64_t nrhs, double* ferr_out,
+                       double* berr_out) {
+  return ferr_host_entry(h, false, nzval, rhs, x, nrhs, ferr_out, berr_out);
+}
+
+int okkt_schur_forward_error(okkt_handle h, const double* nzval, const double* rhs, const double* x, int64_t nrhs, double* ferr_out,
+                             double* berr_out) {
+  return ferr_host_entry(h, true, nzval, rhs, x, nrhs, ferr_out, berr_out);
 }
 
 // ---- symmetric equilibration (scaling.hip) ------------------------------------------------------------------
@@ -1893,6 +1957,7 @@ static int schur_factor_impl(okkt_solver_s* h, const double* S, int64_t ld, bool
   h->dl.valid = false;
   std::string e = dense_ldlt_alloc(h->dl, ns);
   if (!e.empty()) return solver_set_error(h, OKKT_ERR_ALLOC, "dense Schur factor allocation failed: " + e);
+  h->dl.seq = ++h->dense_seq;      // a selected inverse seeded from the previous dense factor is stale from here on
   if (!S) {
     schur_export_enqueue(h->N, h->dl.F, ns);
   } else if (hipMemcpy2DAsync(h->dl.F, (size_t)ns * sizeof(double), S, (size_t)ld * sizeof(double), (size_t)ns * sizeof(double), (size_t)ns,
@@ -2092,6 +2157,15 @@ int okkt_schur_solve_refine(okkt_handle h, const double* nzval, const double* rh
 static int selinv_ready(okkt_solver_s* h, bool need_z) {
   int rc = ensure_device(h);
   if (rc != OKKT_OK) return rc;
+  if (schur_mode(h) && need_z) {
+    // the exports serve the Z of okkt_schur_selinv: current against both factors it was made from
+    if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_analyze has not been called");
+    const SelinvWork& W = h->sl;
+    if (!h->numeric_ready || !h->factored || !h->dl.valid || !W.planned || W.skip_sn < 0 || W.skip_sn != h->N.schur_sn || W.factor_seq != h->factor_seq ||
+        W.dense_seq != h->dl.seq)
+      return solver_set_error(h, OKKT_ERR_INVALID, "no selected inverse of the current factorisation: call okkt_schur_selinv after okkt_factor_schur and okkt_schur_factor");
+    return OKKT_OK;
+  }
   if (schur_mode(h)) return schur_refuse(h, "selected inversion");
   if (!h->analyzed) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_analyze has not been called");
   if (h->S.nparts > 1)
@@ -2297,6 +2371,141 @@ int okkt_logdet(okkt_handle h, double* logabsdet, int32_t* sign) {
     return OKKT_OK;
   } catch (...) {
     return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_logdet");
+  }
+}
+
+// ---- the Schur route made whole: S^-1, selected inversion and the log-determinant through it ------------------
+
+static int schur_inverse_impl(okkt_solver_s* h, double* Z, int64_t ld, bool on_device) {
+  int rc = ensure_device(h);
+  if (rc == OKKT_OK) rc = schur_ready(h, false);
+  if (rc == OKKT_OK) rc = schur_dense_ready(h);
+  if (rc != OKKT_OK) return rc;
+  const int64_t ns = h->S.nschur;
+  if (ld < ns) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_schur_get_inverse: ld < ns");
+  DevTemp t;
+  if (!on_device && !t.alloc(ns * ns)) return solver_set_error(h, OKKT_ERR_ALLOC, "inverse staging allocation failed");
+  (void)hipEventRecord(h->ev0, h->stream);
+  std::string e = dense_ldlt_inverse_enqueue(h->dl, on_device ? Z : t.p, on_device ? ld : ns, h->stream);
+  if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, "dense Schur inverse: " + e);
+  (void)hipEventRecord(h->ev1, h->stream);
+  unsigned long long nf = 0;
+  hipError_t he = hipMemcpyAsync(&nf, h->dl.nonfinite, sizeof(nf), hipMemcpyDeviceToHost, h->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(h->stream);
+  if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("dense Schur inverse failed: ") + hipGetErrorString(he));
+  h->dl.inv_nonfinite = (long long)nf;
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->last_solve_ms = ms;
+  if (!on_device && hipMemcpy2D(Z, (size_t)ld * sizeof(double), t.p, (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), (size_t)ns, hipMemcpyDeviceToHost) != hipSuccess)
+    return solver_set_error(h, OKKT_ERR_HIP, "inverse download failed");
+  return OKKT_OK;
+}
+
+int okkt_schur_get_inverse(okkt_handle h, double* Z, int64_t ld) {
+  if (!h || !Z) return OKKT_ERR_INVALID;
+  try {
+    return schur_inverse_impl(h, Z, ld, false);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_get_inverse");
+  }
+}
+
+int okkt_schur_get_inverse_dev(okkt_handle h, double* d_Z, int64_t ld) {
+  if (!h || !d_Z) return OKKT_ERR_INVALID;
+  try {
+    return schur_inverse_impl(h, d_Z, ld, true);
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_get_inverse_dev");
+  }
+}
+
+int64_t okkt_schur_inverse_nonfinite(okkt_handle h) {
+  if (!h) return OKKT_ERR_INVALID;
+  return (int64_t)h->dl.inv_nonfinite;
+}
+
+int okkt_schur_selinv(okkt_handle h, okkt_selinv_info* info) {
+  if (!h) return OKKT_ERR_INVALID;
+  try {
+    int rc = schur_route_ready(h);
+    if (rc != OKKT_OK) return rc;
+    SelinvWork& W = h->sl;
+    const int ssn = h->N.schur_sn;
+    const int64_t ns = h->S.nschur;
+    if (!W.planned || W.analysis != h->n_analyze_calls || W.arena != h->N.d.arena || W.skip_sn != ssn) {
+      (void)hipStreamSynchronize(h->stream);
+      std::string e = selinv_setup(h->S, h->N, h->pat_colptr.data(), h->pat_rowval.data(), W, ssn);
+      if (!e.empty()) { selinv_release(W); return solver_set_error(h, OKKT_ERR_ALLOC, "selected inversion set-up: " + e); }
+      W.analysis = h->n_analyze_calls;
+      W.arena = h->N.d.arena;
+    }
+    W.factor_seq = -1;
+    (void)hipEventRecord(h->ev0, h->stream);
+    // the Schur front's panel is S^-1 in the set's order, which is the front's column order (k_schur_gather / k_schur_put); the
+    // schedule of the plain route then runs on everything below it
+    std::string e = dense_ldlt_inverse_enqueue(h->dl, W.Z + W.zpos_host[(size_t)ssn], ns, h->stream);
+    if (e.empty()) e = selinv_enqueue(h->N, W);
+    if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
+    (void)hipEventRecord(h->ev1, h->stream);
+    unsigned long long nf = 0;
+    hipError_t he = hipMemcpyAsync(&nf, W.count, sizeof(nf), hipMemcpyDeviceToHost, h->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(h->stream);
+    if (he != hipSuccess) return solver_set_error(h, OKKT_ERR_HIP, std::string("selected inversion failed: ") + hipGetErrorString(he));
+    W.factor_seq = h->factor_seq;
+    W.dense_seq = h->dl.seq;
+    if (info) {
+      float ms = 0;
+      info->seconds_device = hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess ? ms * 1e-3 : 0.0;
+      info->arena_bytes = W.bytes;
+      info->nonfinite = (int64_t)nf;
+      info->status = nf ? 1 : 0;
+      info->flops = W.flops + (double)ns * (double)ns * (double)ns;
+    }
+    return OKKT_OK;
+  } catch (const std::bad_alloc&) {
+    return solver_set_error(h, OKKT_ERR_ALLOC, "out of host memory in okkt_schur_selinv");
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_selinv");
+  }
+}
+
+int okkt_schur_logdet(okkt_handle h, double* logabsdet, int32_t* sign) {
+  if (!h || !logabsdet || !sign) return OKKT_ERR_INVALID;
+  try {
+    int rc = schur_route_ready(h);
+    if (rc != OKKT_OK) return rc;
+    const int64_t ns = h->S.nschur, n1 = h->S.n - ns;
+    std::vector<double> d((size_t)n1), dg((size_t)ns), sub((size_t)ns, 0.0);
+    std::vector<int> ptype((size_t)ns);
+    if ((rc = schur_sync(h, "logdet")) != OKKT_OK) return rc;
+    const size_t pitch = (size_t)(ns + 1) * sizeof(double);      // down the diagonal of the dense factor, and the entries below it
+    if ((n1 > 0 && hipMemcpy(d.data(), h->N.d.dvals, (size_t)n1 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+        hipMemcpy2D(dg.data(), sizeof(double), h->dl.F, pitch, sizeof(double), (size_t)ns, hipMemcpyDeviceToHost) != hipSuccess ||
+        (ns > 1 && hipMemcpy2D(sub.data(), sizeof(double), h->dl.F + 1, pitch, sizeof(double), (size_t)(ns - 1), hipMemcpyDeviceToHost) != hipSuccess) ||
+        hipMemcpy(ptype.data(), h->dl.ptype, (size_t)ns * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+      return solver_set_error(h, OKKT_ERR_HIP, "download of D failed");
+    double acc = 0.0;
+    int32_t sg = 1;
+    auto take = [&](double v) {
+      if (v < 0) sg = -sg;
+      else if (!(v > 0)) sg = 0;   // zero or NaN
+      acc += std::log(std::fabs(v));
+    };
+    for (int64_t i = 0; i < n1; ++i) take(d[(size_t)i]);
+    for (int64_t k = 0; k < ns; ++k) {
+      if (ptype[(size_t)k] == 0) { take(dg[(size_t)k]); continue; }
+      // a 2 x 2 block [a b; b c]: det = b^2 ((a / |b|)(c / |b|) - 1), the scaled form of the solves
+      const double b = sub[(size_t)k], t = std::fabs(b);
+      take(t);
+      take(t);
+      take((dg[(size_t)k] / t) * (dg[(size_t)k + 1] / t) - 1.0);
+      ++k;
+    }
+    *logabsdet = acc;
+    *sign = sg;
+    return OKKT_OK;
+  } catch (...) {
+    return solver_set_error(h, OKKT_ERR_INTERNAL, "unexpected exception in okkt_schur_logdet");
   }
 }
 

@@ -444,9 +444,213 @@ std::string solve_r(DenseLdltWork& D, const double* d_r2, double* d_x2, int nr, 
   return "";
 }
 
+// ---- the inverse ------------------------------------------------------------------------------------------
+// Zt = (P S P')^-1 = L^-T D^-1 L^-1 by the recurrence of selected inversion (selinv.hip) on the dense factor as one front: the blocks
+// of kDlIB columns from the last to the first, for block j (columns c0 .. j1, the rows below it B = j1 .. n)
+//   W_j = L_Bj L_jj^-1,   Z_Bj = - Z_BB W_j,   Z_jj = L_jj^-T D_j^-1 L_jj^-1 - W_j' Z_Bj.
+// Every entry is computed once, in the lower triangle, and stored at both places, so the two triangles are the same bits.  Three
+// launches per block step (k_dli_block, k_dli_cols, k_dli_diag); where the blocks begin depends on the 2 x 2 pivots, so a launch reads
+// its block from the list k_dli_plan made and the host enqueues the largest number of steps there can be.  Fixed summation orders,
+// no floating-point atomics: the same factor gives the same bits.
+
+__global__ void k_dli_plan(int n, const int* __restrict__ ptype, int* __restrict__ blk, unsigned long long* __restrict__ nonfinite) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  int nb = 0, c = 0;
+  while (c < n) {
+    blk[1 + nb++] = c;
+    int e = min(n, c + kDlIB);
+    if (e < n && ptype[e - 1] == 1) --e;      // the 2 x 2 pivot (e - 1, e) opens the next block
+    c = e;
+  }
+  blk[1 + nb] = n;
+  blk[0] = nb;
+  *nonfinite = 0ull;
+}
+
+// Every workgroup inverts L_jj in LDS.  Workgroup 0 stores L_jj^-T D_j^-1 L_jj^-1 (lower triangle) into Zt; workgroup g >= 1 the 256
+// rows j1 + 256 (g - 1) .. of W_j, one row per thread, into Wt (row-major, kDlIB entries per row, zeros beyond the block's width).
+__global__ __launch_bounds__(256) void k_dli_block(const double* __restrict__ F, int n, const int* __restrict__ ptype, const int* __restrict__ blk, int j,
+                                                   double* __restrict__ Zt, double* __restrict__ Wt) {
+  __shared__ double Lb[kDlIB][kDlIB + 1];
+  __shared__ double Li[kDlIB][kDlIB + 1];
+  __shared__ double Ms[kDlIB][kDlIB + 1];
+  __shared__ double dd[kDlIB], od[kDlIB];
+  __shared__ int pt[kDlIB];
+  if (j >= blk[0]) return;
+  const int c0 = blk[1 + j], j1 = blk[2 + j], w = j1 - c0;
+  const size_t ld = (size_t)n;
+  const int tid = threadIdx.x;
+  if (blockIdx.x > 0 && (int64_t)j1 + (int64_t)(blockIdx.x - 1) * 256 >= n) return;
+  for (int e = tid; e < kDlIB * kDlIB; e += 256) {
+    const int x = e % kDlIB, y = e / kDlIB;
+    Lb[x][y] = (x < w && y < x) ? l_entry(F, ptype, ld, c0 + x, c0 + y) : 0.0;
+    Li[x][y] = (x == y && x < w) ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  // unit lower inverse, row by row: Li[x][y] = - sum_{y <= t < x} Lb[x][t] Li[t][y]
+  for (int x = 1; x < w; ++x) {
+    if (tid < x) {
+      double s = 0.0;
+      for (int t = tid; t < x; ++t) s += Lb[x][t] * Li[t][tid];
+      Li[x][tid] = -s;
+    }
+    __syncthreads();
+  }
+  if (blockIdx.x == 0) {
+    // D_j^-1, row t: dd[t] on the diagonal, od[t] at the partner pt[t] of a 2 x 2 pivot (dsytri's scaled formulas)
+    if (tid < w) {
+      const int k = c0 + tid, ty = ptype[k];
+      if (ty == 0) {
+        dd[tid] = 1.0 / F[(size_t)k * ld + k];
+        od[tid] = 0.0;
+        pt[tid] = tid;
+      } else {
+        const int k0 = ty == 1 ? k : k - 1;
+        const double b = F[(size_t)k0 * ld + k0 + 1];
+        const double t = fabs(b);
+        const double ak = F[(size_t)k0 * ld + k0] / t, akp1 = F[(size_t)(k0 + 1) * ld + k0 + 1] / t, akkp1 = b / t;
+        const double d = t * (ak * akp1 - 1.0);
+        dd[tid] = (ty == 1 ? akp1 : ak) / d;
+        od[tid] = -akkp1 / d;
+        pt[tid] = ty == 1 ? tid + 1 : tid - 1;
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < kDlIB * kDlIB; e += 256) {
+      const int t = e % kDlIB, y = e / kDlIB;
+      Ms[t][y] = t < w ? dd[t] * Li[t][y] + od[t] * Li[pt[t]][y] : 0.0;
+    }
+    __syncthreads();
+    for (int e = tid; e < kDlIB * kDlIB; e += 256) {
+      const int x = e % kDlIB, y = e / kDlIB;
+      if (x >= w || y > x) continue;
+      double s = 0.0;
+      for (int t = x; t < w; ++t) s += Li[t][x] * Ms[t][y];
+      Zt[(size_t)(c0 + y) * ld + c0 + x] = s;
+    }
+    return;
+  }
+  const int64_t x = (int64_t)j1 + (int64_t)(blockIdx.x - 1) * 256 + tid;
+  if (x >= n) return;
+  double acc[kDlIB];
+#pragma unroll
+  for (int c = 0; c < kDlIB; ++c) acc[c] = 0.0;
+  for (int t = 0; t < w; ++t) {
+    const double l = F[(size_t)(c0 + t) * ld + x];
+#pragma unroll
+    for (int c = 0; c < kDlIB; ++c) acc[c] += l * Li[t][c];
+  }
+  double* wr = Wt + (size_t)(x - j1) * kDlIB;
+#pragma unroll
+  for (int c = 0; c < kDlIB; ++c) wr[c] = acc[c];
+}
+
+// Z_Bj = - Z_BB W_j, one workgroup per 16 rows of B.  The kDliWaves waves share the sum over B's rows y (wave v takes the groups of
+// four rows 4 q .., q = v mod kDliWaves) on v_mfma_f64_16x16x4 (operand and result layout: k_dl_trail); their partial sums are added in
+// wave order.  The workgroup then leaves its rows' part of W_j' Z_Bj (kDlIB x kDlIB) in Pt for k_dli_diag.
+constexpr int kDliWaves = 8;
+__global__ __launch_bounds__(64 * kDliWaves) void k_dli_cols(int n, const int* __restrict__ blk, int j, double* Zt, const double* __restrict__ Wt,
+                                                             double* __restrict__ Pt) {
+  typedef double v4d __attribute__((ext_vector_type(4)));
+  __shared__ double part[kDliWaves][2][4][64];
+  __shared__ double Zs[16][kDlIB + 1];
+  __shared__ double Ws[16][kDlIB + 1];
+  if (j >= blk[0]) return;
+  const int c0 = blk[1 + j], j1 = blk[2 + j], w = j1 - c0;
+  const int64_t x0 = (int64_t)j1 + (int64_t)blockIdx.x * 16;
+  if (x0 >= n) return;
+  const size_t ld = (size_t)n;
+  const int m = n - j1;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const int64_t arow = x0 + l15;
+  v4d acc[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[s][r] = 0.0;
+  for (int q = wave; 4 * q < m; q += kDliWaves) {
+    const int yl = 4 * q + l4;
+    const bool yin = yl < m;
+    const double a = (yin && arow < n) ? Zt[(size_t)(j1 + yl) * ld + arow] : 0.0;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const double bv = yin ? Wt[(size_t)yl * kDlIB + 16 * s + l15] : 0.0;
+      acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, acc[s], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) part[wave][s][r][lane] = acc[s][r];
+  {
+    const int xl = tid >> 5, c = tid & 31;      // 16 x kDlIB entries of W_j, one per thread
+    Ws[xl][c] = x0 + xl < n ? Wt[(size_t)(x0 + xl - j1) * kDlIB + c] : 0.0;
+  }
+  __syncthreads();
+  {
+    const int ln = tid & 63, r = (tid >> 6) & 3, s = tid >> 8;
+    double v = part[0][s][r][ln];
+#pragma unroll
+    for (int v2 = 1; v2 < kDliWaves; ++v2) v += part[v2][s][r][ln];
+    const int xl = (ln >> 4) + 4 * r;
+    const int64_t x = x0 + xl;
+    const int cc = 16 * s + (ln & 15);
+    const bool in = x < n && cc < w;
+    Zs[xl][cc] = in ? -v : 0.0;
+    if (in) {
+      Zt[(size_t)(c0 + cc) * ld + x] = -v;
+      Zt[(size_t)x * ld + c0 + cc] = -v;
+    }
+  }
+  __syncthreads();
+  double* P = Pt + (size_t)blockIdx.x * (kDlIB * kDlIB);
+  for (int e = tid; e < kDlIB * kDlIB; e += 64 * kDliWaves) {
+    const int a = e % kDlIB, c = e / kDlIB;
+    double sum = 0.0;
+#pragma unroll
+    for (int xl = 0; xl < 16; ++xl) sum = fma(Ws[xl][a], Zs[xl][c], sum);
+    P[e] = sum;
+  }
+}
+static_assert(64 * kDliWaves == 16 * kDlIB, "k_dli_cols stages one entry of the W tile and one of the Z tile per thread");
+
+// Z_jj -= W_j' Z_Bj: the row tiles' parts added in tile order (lower triangle), the result stored at both places
+__global__ __launch_bounds__(kDlIB * kDlIB) void k_dli_diag(int n, const int* __restrict__ blk, int j, double* Zt, const double* __restrict__ Pt) {
+  if (j >= blk[0]) return;
+  const int c0 = blk[1 + j], j1 = blk[2 + j], w = j1 - c0;
+  const size_t ld = (size_t)n;
+  const int ntile = (n - j1 + 15) / 16;
+  const int a = threadIdx.x % kDlIB, c = threadIdx.x / kDlIB;
+  if (a >= w || c > a) return;
+  double s = 0.0;
+  for (int t = 0; t < ntile; ++t) s += Pt[(size_t)t * (kDlIB * kDlIB) + threadIdx.x];
+  const double v = Zt[(size_t)(c0 + c) * ld + c0 + a] - s;
+  Zt[(size_t)(c0 + c) * ld + c0 + a] = v;
+  Zt[(size_t)(c0 + a) * ld + c0 + c] = v;
+}
+
+// Z[perm[i], perm[j]] = Zt[i, j], and the count of the non-finite entries (integer atomics: exact in any order)
+__global__ __launch_bounds__(256) void k_dli_out(int n, const int* __restrict__ perm, const double* __restrict__ Zt, double* __restrict__ Z, int64_t ldz,
+                                                 unsigned long long* __restrict__ nonfinite) {
+  const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+  bool bad = false;
+  if (i < n) {
+    const double v = Zt[(size_t)j * n + i];
+    Z[(size_t)perm[j] * (size_t)ldz + perm[i]] = v;
+    bad = !isfinite(v);
+  }
+  const unsigned long long b = __ballot(bad);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(nonfinite, (unsigned long long)__popcll(b));
+}
+
 }  // namespace
 
 void dense_ldlt_release(DenseLdltWork& D) {
+  if (D.Zt) (void)hipFree(D.Zt);
+  if (D.Pt) (void)hipFree(D.Pt);
+  if (D.blk) (void)hipFree(D.blk);
+  if (D.nonfinite) (void)hipFree(D.nonfinite);
   if (D.F) (void)hipFree(D.F);
   if (D.W) (void)hipFree(D.W);
   if (D.X) (void)hipFree(D.X);
@@ -502,6 +706,29 @@ std::string dense_ldlt_solve_enqueue(DenseLdltWork& D, const double* d_r2, doubl
   if (R == 1) return solve_r<1>(D, d_r2, d_x2, nr, st);
   if (R == 2) return solve_r<2>(D, d_r2, d_x2, nr, st);
   return solve_r<4>(D, d_r2, d_x2, nr, st);
+}
+
+std::string dense_ldlt_inverse_enqueue(DenseLdltWork& D, double* d_Z, int64_t ld, hipStream_t st) {
+  const int n = (int)D.ns;
+  if (n <= 0) return "";
+  const int maxb = (n + kDlIB - 2) / (kDlIB - 1);      // a block has kDlIB - 1 columns at the least (the last one apart)
+  if (!D.Zt) {
+    OKKT_HIP_TRY(hipMalloc((void**)&D.Zt, (size_t)n * n * sizeof(double)));
+    OKKT_HIP_TRY(hipMalloc((void**)&D.Pt, (size_t)((n + 15) / 16) * kDlIB * kDlIB * sizeof(double)));
+    OKKT_HIP_TRY(hipMalloc((void**)&D.blk, (size_t)(maxb + 2) * sizeof(int)));
+    OKKT_HIP_TRY(hipMalloc((void**)&D.nonfinite, sizeof(unsigned long long)));
+  }
+  hipLaunchKernelGGL(k_dli_plan, dim3(1), dim3(64), 0, st, n, D.ptype, D.blk, D.nonfinite);
+  for (int j = maxb - 1; j >= 0; --j) {
+    // block j begins at column j (kDlIB - 1) at the earliest and ends kDlIB - 1 columns later at the earliest
+    const int64_t below = std::max<int64_t>(0, (int64_t)n - (int64_t)(j + 1) * (kDlIB - 1));
+    hipLaunchKernelGGL(k_dli_block, dim3((unsigned)(1 + (below + 255) / 256)), dim3(256), 0, st, D.F, n, D.ptype, D.blk, j, D.Zt, D.W);
+    if (below > 0) hipLaunchKernelGGL(k_dli_cols, dim3((unsigned)((below + 15) / 16)), dim3(64 * kDliWaves), 0, st, n, D.blk, j, D.Zt, D.W, D.Pt);
+    hipLaunchKernelGGL(k_dli_diag, dim3(1), dim3(kDlIB * kDlIB), 0, st, n, D.blk, j, D.Zt, D.Pt);
+  }
+  hipLaunchKernelGGL(k_dli_out, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, st, n, D.perm, D.Zt, d_Z, ld, D.nonfinite);
+  OKKT_HIP_TRY(hipGetLastError());
+  return "";
 }
 
 }  // namespace okkt

@@ -43,6 +43,8 @@ struct SelinvWork {
   int64_t analysis = -1;        // okkt_solver_s::n_analyze_calls the plan belongs to
   const double* arena = nullptr;  // ... and the front arena (a new device plan gets a new one)
   int64_t factor_seq = -1;      // the factorisation Z was computed from (-1: none)
+  int skip_sn = -1;             // the supernode the plan leaves out of the block steps (the Schur front, section 8.10; -1: none)
+  int64_t dense_seq = -1;       // Schur route: the okkt_schur_factor whose S^-1 seeded Z
   int64_t z_doubles = 0, scratch_doubles = 0, bytes = 0;
   double flops = 0;             // products of the block steps (2 m^2 w + 2 m w^2 per step), informational
   double* Z = nullptr;
@@ -60,7 +62,9 @@ struct SelinvWork {
 };
 
 // host plan and allocations for the current analysis (colptr / rowval: the analysed input pattern, index base = colptr[0])
-std::string selinv_setup(const Symbolic& S, const Numeric& N, const int64_t* colptr, const int64_t* rowval, SelinvWork& W);
+// skip_sn: a root supernode whose Z panel the caller fills before selinv_enqueue (the Schur front of the Schur route); it gets a panel
+// and no block step
+std::string selinv_setup(const Symbolic& S, const Numeric& N, const int64_t* colptr, const int64_t* rowval, SelinvWork& W, int skip_sn = -1);
 void selinv_release(SelinvWork& W);
 // Z from the factor in N (enqueued on N.stream) and the count of its non-finite entries into W.count (no synchronisation)
 std::string selinv_enqueue(const Numeric& N, SelinvWork& W);

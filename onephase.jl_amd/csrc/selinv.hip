@@ -319,8 +319,9 @@ void selinv_release(SelinvWork& W) {
   W = SelinvWork();
 }
 
-std::string selinv_setup(const Symbolic& S, const Numeric& N, const int64_t* colptr, const int64_t* rowval, SelinvWork& W) {
+std::string selinv_setup(const Symbolic& S, const Numeric& N, const int64_t* colptr, const int64_t* rowval, SelinvWork& W, int skip_sn) {
   selinv_release(W);
+  W.skip_sn = skip_sn;
   const int ns = S.nsuper;
   const int64_t n = S.n;
   auto fk = [&](int s, int& f, int& k) {
@@ -345,7 +346,7 @@ std::string selinv_setup(const Symbolic& S, const Numeric& N, const int64_t* col
     return r * r + (int64_t)f * k + (int64_t)((f + kSlB - 1) / kSlB) * kSlB * kSlB;
   };
   int64_t budget = kSlChunkDoubles;
-  for (int s = 0; s < ns; ++s) budget = std::max(budget, need(s));
+  for (int s = 0; s < ns; ++s) if (s != skip_sn) budget = std::max(budget, need(s));
   // levels from the root down, each cut into chunks within the budget
   std::vector<SlFront> fr;
   std::vector<SlItem> items;
@@ -359,8 +360,9 @@ std::string selinv_setup(const Symbolic& S, const Numeric& N, const int64_t* col
       SlChunk C;
       C.f_off = (int)fr.size();
       int64_t used = 0;
-      while (p < pe && (C.f_cnt == 0 || used + need(S.level_sn[p]) <= budget)) {
+      while (p < pe && (S.level_sn[p] == skip_sn || C.f_cnt == 0 || used + need(S.level_sn[p]) <= budget)) {
         const int s = S.level_sn[p++];
+        if (s == skip_sn) continue;
         int f, k;
         fk(s, f, k);
         SlFront F;
@@ -374,6 +376,7 @@ std::string selinv_setup(const Symbolic& S, const Numeric& N, const int64_t* col
         fr.push_back(F);
         ++C.f_cnt;
       }
+      if (C.f_cnt == 0) continue;      // the level held the skipped supernode alone
       scratch_max = std::max(scratch_max, used);
       C.g_off = (int64_t)items.size();
       for (int i = C.f_off; i < C.f_off + C.f_cnt; ++i)
@@ -401,7 +404,7 @@ std::string selinv_setup(const Symbolic& S, const Numeric& N, const int64_t* col
       W.chunks.push_back(std::move(C));
     }
   }
-  if ((int)fr.size() != ns) return "selected inversion: the level schedule does not cover every supernode";
+  if ((int)fr.size() != ns - (skip_sn >= 0 ? 1 : 0)) return "selected inversion: the level schedule does not cover every supernode";
   W.flops = flops;
   W.scratch_doubles = scratch_max;
   // diagonal positions and the map of the input entries (mirrored into the lower triangle of the permuted matrix)

@@ -75,6 +75,7 @@ struct okkt_solver_s {
   // dense factor of the Schur complement (dense_ldlt.hip): allocated by the first okkt_schur_factor after an
   // analysis and released with the refinement map; the pivot counts of the last okkt_factor_schur (A11's) for the whole-matrix inertia
   okkt::DenseLdltWork dl;
+  int64_t dense_seq = 0;        // okkt_schur_factor calls started: a selected inverse through the Schur route is stale after the next
   okkt_inertia a11_inertia = {0, 0, 0, 0};
   // symmetric equilibration (scaling.hip): the configuration of okkt_set_scaling (kept across analyses) and the
   // device state of the current analysis, allocated by the first scaled factorisation and released with the refinement map
@@ -113,11 +114,11 @@ int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* 
 void solver_refine_release(okkt_solver_s* h);
 // GMRES-based refinement driver (api.cpp): x = F \ b, then outer steps of one double-double residual and one
 // right-preconditioned GMRES(restart) cycle on A d = r each, right-hand sides in lockstep groups of up to four.  Pointers as
-// solver_refine_device's
+// solver_refine_device's.  schur_route (here and in the two estimates below): F^-1 is the Schur route's whole-system solve (section 8.10)
 int solver_gmres_device(okkt_solver_s* h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
-                        int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out);
+                        int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out, bool schur_route = false);
 // condition estimate of the factored F (the values d_nzval plus the factorisation's diagonal shift) and forward error bounds (api.cpp)
-int solver_condest_device(okkt_solver_s* h, const double* d_nzval, int32_t t, okkt_condest_info* info);
+int solver_condest_device(okkt_solver_s* h, const double* d_nzval, int32_t t, okkt_condest_info* info, bool schur_route = false);
 int solver_forward_error_device(okkt_solver_s* h, const double* d_nzval, const double* d_b, const double* d_x, int64_t nrhs, double* ferr_out,
-                                double* berr_out);
+                                double* berr_out, bool schur_route = false);
 }  // namespace okkt

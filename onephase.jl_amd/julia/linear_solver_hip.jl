@@ -288,6 +288,68 @@ function schur_solve_refine!(solver::linear_solver_HIP, A::SparseMatrixCSC{Float
     return info[]
 end
 
+# The Schur route made whole (DESIGN.md section 8.10): what judges a doubtful factor, for a handle in Schur mode.  Except schur_inverse
+# every call needs okkt_factor_schur and okkt_schur_factor of the handle's own S.  Not part of the reference interface.
+struct OkktSelinvInfo     # okkt_selinv_info of include/okkt.h
+    seconds_device::Float64
+    arena_bytes::Int64
+    nonfinite::Int64
+    status::Int32            # 1 when Z has non-finite entries
+    flops::Float64
+end
+
+# (S^-1, the number of its non-finite entries): ns x ns in the order of the set, both triangles the same bits; of the current dense
+# factor, the handle's own S or a caller's
+function schur_inverse(solver::linear_solver_HIP, ns::Integer)
+    Z = zeros(ns, ns)
+    rc = ccall((:okkt_schur_get_inverse, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), solver.handle, Z, ns)
+    rc < 0 && okkt_error(solver, "okkt_schur_get_inverse", rc)
+    return Z, ccall((:okkt_schur_inverse_nonfinite, OKKT_LIB), Int64, (Ptr{Cvoid},), solver.handle)
+end
+
+# Z = A^-1 on the pattern of the whole factor, kept on the device for okkt_get_inverse_diag / _on_pattern / _csc
+function schur_selinv(solver::linear_solver_HIP)
+    info = Ref(OkktSelinvInfo(0.0, 0, 0, 0, 0.0))
+    rc = ccall((:okkt_schur_selinv, OKKT_LIB), Cint, (Ptr{Cvoid}, Ref{OkktSelinvInfo}), solver.handle, info)
+    rc < 0 && okkt_error(solver, "okkt_schur_selinv", rc)
+    return info[]
+end
+
+# (log |det A|, sign)
+function schur_logdet(solver::linear_solver_HIP)
+    v = Ref(0.0)
+    s = Ref(Int32(0))
+    rc = ccall((:okkt_schur_logdet, OKKT_LIB), Cint, (Ptr{Cvoid}, Ref{Float64}, Ref{Int32}), solver.handle, v, s)
+    rc < 0 && okkt_error(solver, "okkt_schur_logdet", rc)
+    return v[], s[]
+end
+
+function schur_condest(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}; t::Integer=2)
+    info = Ref(OkktCondestInfo(0.0, 0.0, 0.0, 0, 0, 0))
+    rc = ccall((:okkt_schur_condest, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ref{OkktCondestInfo}), solver.handle, A.nzval, Int32(t), info)
+    rc < 0 && okkt_error(solver, "okkt_schur_condest", rc)
+    return info[]
+end
+
+function schur_forward_error(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}, my_rhs::Array{Float64,1}, x::Array{Float64,1})
+    ferr = zeros(1)
+    berr = zeros(1)
+    rc = ccall((:okkt_schur_forward_error, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+               solver.handle, A.nzval, my_rhs, x, 1, ferr, berr)
+    rc < 0 && okkt_error(solver, "okkt_schur_forward_error", rc)
+    return ferr[1], berr[1]
+end
+
+function schur_solve_gmres(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}, my_rhs::Array{Float64,1}, my_sol::Array{Float64,1};
+                           restart::Integer=30, max_iters::Integer=200, tol::Float64=0.0)
+    info = Ref(OkktGmresInfo(0, 0, 0, 0, 0.0, 0.0, 0.0, 0))
+    rc = ccall((:okkt_schur_solve_gmres, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Float64,
+                                                          Ref{OkktGmresInfo}, Ptr{Float64}),
+               solver.handle, A.nzval, my_rhs, my_sol, 1, Int32(restart), Int32(max_iters), tol, info, C_NULL)
+    rc < 0 && okkt_error(solver, "okkt_schur_solve_gmres", rc)
+    return info[]
+end
+
 function ls_solve(solver::linear_solver_HIP, my_rhs::AbstractArray, timer::class_advanced_timer)
     rhs = Vector{Float64}(my_rhs)      # SparseVector rhs is densified, as in julia.jl:105-113
     sol = zeros(length(rhs))
