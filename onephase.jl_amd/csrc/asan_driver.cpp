@@ -1,7 +1,8 @@
 // Host-side sanitizer run (make asan): the orderings, the symbolic analysis and the dataflow queue builder under AddressSanitizer and
 // UndefinedBehaviorSanitizer on small synthetic patterns -- a banded KKT (level-structure dissection), a 3-D grid, a small-world graph
 // (multilevel dissection with its helper threads) and an arrow matrix -- and the work-item lists of the pivot report (pivots.h) on each
-// of them and on a front tall enough for several chunks per column.  No device code, no HIP call.  SURVEY.md section 5 (host-side
+// of them and on a front tall enough for several chunks per column, and the flat records of the staged big-front assembly
+// (asm_pieces.h) on each of them and under a front of three chunks.  No device code, no HIP call.  SURVEY.md section 5 (host-side
 // sanitizer build); GPU sanitizers are not available on this pool.
 #include <cstdio>
 #include <cstdlib>
@@ -9,6 +10,7 @@
 #include <set>
 #include <vector>
 
+#include "asm_pieces.h"
 #include "numeric.h"
 #include "pivots.h"
 #include "symbolic.h"
@@ -20,6 +22,94 @@ static void csc_lower(int n, const std::set<std::pair<int, int>>& e, std::vector
   for (auto& p : e) cols[std::min(p.first, p.second)].push_back(std::max(p.first, p.second));
   cp.assign(n + 1, 0); ri.clear();
   for (int j = 0; j < n; ++j) { ri.push_back(j); for (int r : cols[j]) if (r != j) ri.push_back(r); cp[j + 1] = (int64_t)ri.size(); }
+}
+
+// The records of the staged assembly against a plain enumeration: for every column of every big front (more than 128 rows here) the
+// items are the columns jj of its children, ascending, with rel[jj] = the column; the pieces of the column's chunks must tile the rows
+// jj .. rc - 1 of every item exactly once, chunk after chunk, keep the order of the items inside every chunk, and none may be empty.
+// The A entries of the chunks of a column must tile the column's entries.
+static bool check_asm_pieces(const Symbolic& S, int chunk) {
+  const int ns = S.nsuper;
+  std::vector<char> big(ns, 0);
+  std::vector<int64_t> cb_base(ns, 0);
+  int64_t top = 0;
+  for (int s = 0; s < ns; ++s) {
+    const int64_t f = S.row_ptr[s + 1] - S.row_ptr[s], k = S.sn_col0[s + 1] - S.sn_col0[s];
+    big[s] = f > 128;
+    cb_base[s] = top + k * f + k;
+    top += f * f + (s & 1);      // odd and even bases
+  }
+  AsmPlan A;
+  if (!asm_build_pieces(S, big, cb_base, chunk, A).empty()) return false;
+  std::vector<std::vector<int>> kids(ns);
+  for (int c = 0; c < ns; ++c) if (S.sn_parent[c] >= 0) kids[S.sn_parent[c]].push_back(c);
+  int64_t items = 0, pieces = 0;
+  for (int p = 0; p < ns; ++p) {
+    if (!big[p]) { if (A.unit_base[p] != -1) return false; continue; }
+    const int64_t f = S.row_ptr[p + 1] - S.row_ptr[p];
+    const int nchunks = (int)((f + chunk - 1) / chunk);
+    for (int64_t pc = 0; pc < f; ++pc) {
+      // the items of the column
+      std::vector<int> ic, ijj, done;
+      for (int c : kids[p]) {
+        const int* rb = S.rel.data() + S.rel_ptr[c];
+        const int* re = S.rel.data() + S.rel_ptr[c + 1];
+        const int* it = std::lower_bound(rb, re, (int)pc);
+        if (it != re && *it == pc) { ic.push_back(c); ijj.push_back((int)(it - rb)); }
+      }
+      done = ijj;       // per item: the next row a piece has to start at
+      items += (int64_t)ic.size();
+      int64_t a_next = -1;
+      for (int t = 0; t < nchunks; ++t) {
+        const AsmUnit& U = A.units[(size_t)(A.unit_base[p] + (int64_t)t * f + pc)];
+        const int64_t r0 = std::max<int64_t>(pc, (int64_t)t * chunk), r1 = std::min<int64_t>(f, (int64_t)(t + 1) * chunk);
+        if (r0 >= r1) { if (U.np != 0 || U.na != 0) return false; continue; }
+        if (U.np < 0 || U.piece0 < 0 || U.piece0 + U.np > (int64_t)A.pieces.size()) return false;
+        // A entries: one range, in the chunk, contiguous from chunk to chunk
+        if (U.na < 0 || U.a0 < S.aent_ptr[p] || U.a0 + U.na > S.aent_ptr[p + 1]) return false;
+        for (int64_t e = U.a0; e < U.a0 + U.na; ++e) if (S.aent_dst[e] < pc * f + r0 || S.aent_dst[e] >= pc * f + r1) return false;
+        if (a_next >= 0 && U.a0 != a_next) return false;
+        a_next = U.a0 + U.na;
+        int q = 0;      // next item that may own a piece of this chunk
+        for (int i = 0; i < U.np; ++i, ++pieces) {
+          const AsmPiece& R = A.pieces[(size_t)(U.piece0 + i)];
+          if (R.n <= 0) return false;
+          // the first item from q on with a row in the chunk
+          for (; q < (int)ic.size(); ++q) {
+            const int c = ic[q];
+            const int rc = (int)(S.rel_ptr[c + 1] - S.rel_ptr[c]);
+            if (done[q] < rc && S.rel[S.rel_ptr[c] + done[q]] < r1) break;
+          }
+          if (q == (int)ic.size()) return false;
+          const int c = ic[q];
+          const int64_t fc = S.row_ptr[c + 1] - S.row_ptr[c];
+          const int rc = (int)(S.rel_ptr[c + 1] - S.rel_ptr[c]);
+          int hi = done[q];
+          while (hi < rc && S.rel[S.rel_ptr[c] + hi] < r1) ++hi;
+          if (S.rel[S.rel_ptr[c] + done[q]] < r0) return false;
+          if (R.src != cb_base[c] + (int64_t)ijj[q] * fc + done[q] || R.rel != S.rel_ptr[c] + done[q] || R.n != hi - done[q]) return false;
+          done[q] = hi;
+          ++q;
+        }
+        // no item with rows in this chunk was left out
+        for (int j = 0; j < (int)ic.size(); ++j) {
+          const int c = ic[j];
+          const int rc = (int)(S.rel_ptr[c + 1] - S.rel_ptr[c]);
+          if (done[j] < rc && S.rel[S.rel_ptr[c] + done[j]] < r1) return false;
+        }
+      }
+      for (int j = 0; j < (int)ic.size(); ++j) if (done[j] != (int)(S.rel_ptr[ic[j] + 1] - S.rel_ptr[ic[j]])) return false;
+      // every A entry of the column in one of its chunks
+      if (a_next >= 0) {
+        const int64_t* dst = S.aent_dst.data();
+        const int64_t lo = std::lower_bound(dst + S.aent_ptr[p], dst + S.aent_ptr[p + 1], pc * f + pc) - dst;
+        const int64_t hi = std::lower_bound(dst + S.aent_ptr[p], dst + S.aent_ptr[p + 1], (pc + 1) * f) - dst;
+        const AsmUnit& U0 = A.units[(size_t)(A.unit_base[p] + (pc / chunk) * f + pc)];
+        if (U0.a0 != lo || a_next != hi) return false;
+      }
+    }
+  }
+  return items == A.items && pieces == (int64_t)A.pieces.size();
 }
 
 static int run(const char* name, int n, const std::set<std::pair<int, int>>& e, int ordering) {
@@ -83,6 +173,9 @@ static int run(const char* name, int n, const std::set<std::pair<int, int>>& e, 
     ok = ok && entries == P.entries && P.ncols == ncov;
     if (!ok) { fprintf(stderr, "%s (ordering %d): the pivot-report items do not tile the factor (skip %d)\n", name, ordering, skip); return 1; }
   }
+  // the records of the staged assembly, with the library's chunks and with one small enough for several chunks on every pattern
+  for (int chunk : {512, 1024, 48})
+    if (!check_asm_pieces(S, chunk)) { fprintf(stderr, "%s (ordering %d): the assembly pieces do not tile the extend-add items (chunk %d)\n", name, ordering, chunk); return 1; }
   printf("%-12s ordering %d: n %d nnz(L) %lld supernodes %zu, %zu dataflow tasks\n", name, ordering, n, (long long)S.nnzL, S.sn_col0.size() - 1, ntask);
   return 0;
 }
@@ -133,6 +226,18 @@ int main() {
     std::set<std::pair<int, int>> e;
     for (int i = 1; i < n; ++i) e.insert({0, i});
     bad += run("full-column", n, e, 1);
+  }
+  {   // three leaf cliques under a separator of 2300 nodes that their elimination makes dense (natural ordering): a root front of three
+      // 1024-row chunks whose children's contribution blocks cover every row, every second row and a scattered third of the rows
+    const int nl = 30, nsep = 2300, n = 3 * nl + nsep;
+    std::set<std::pair<int, int>> e;
+    for (int g = 0; g < 3; ++g) {
+      for (int i = 0; i < nl; ++i) for (int j = i + 1; j < nl; ++j) e.insert({g * nl + i, g * nl + j});
+      for (int i = 0; i < nl; ++i)
+        for (int r = 0; r < nsep; ++r)
+          if (g == 0 || r == 0 || (g == 1 && r % 2 == 1) || (g == 2 && (r % 3 == 2 || (r > 1020 && r < 1030)))) e.insert({g * nl + i, 3 * nl + r});
+    }
+    bad += run("three-chunks", n, e, 1);
   }
   if (bad) { fprintf(stderr, "%d case(s) failed\n", bad); return 1; }
   printf("asan driver: all cases clean\n");

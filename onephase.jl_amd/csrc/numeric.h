@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "asm_pieces.h"
 #include "symbolic.h"
 
 namespace okkt {
@@ -64,6 +65,10 @@ struct DevPlan {
   const struct EaRec* ea_rec = nullptr;   // per item: the five fields above in one 32-byte record (two 16-byte loads instead of five scattered ones)
   int* cutv = nullptr;           // per child of a big front: positions of the parent's 1024-row boundaries in its rel list
   int64_t* acol_lo = nullptr;    // [n_bigcols + 1] first A entry of each big-front column
+  // flat work records of k_big_assemble_staged (asm_pieces.h): per (front column, row chunk) the run of its pieces and its A entries
+  int64_t* asm_unit_base = nullptr;       // [nsuper] first unit of a big front, -1 for small
+  const AsmUnit* asm_unit = nullptr;
+  const AsmPiece* asm_piece = nullptr;
   // solves (solve.hip): explicit inverses of the kSolveBlock-column diagonal blocks of the fronts with more than NB pivot
   // columns, a scratch copy of the same shape for the recursive inversion, partial vectors of the block products
   double* xinv = nullptr;
@@ -240,6 +245,8 @@ struct Numeric {
   std::vector<int> sn_f, sn_k;           // per supernode
   // Schur mode (Symbolic::nschur > 0): the Schur front (the last supernode; -1: off), its first big-column index (extend-add lists)
   // and a one-entry device list holding it
+  int asm_staged = 1;                    // the big fronts are assembled by k_big_assemble_staged (flat records, staged loads); OKKT_ASM_STAGED=0 switches back to k_big_assemble / k_big_assemble_chunked
+  int64_t asm_record_bytes = 0;          // size of its records on the device
   int schur_sn = -1;
   int64_t schur_gcb = 0;
   int* schur_list = nullptr;

@@ -431,6 +431,130 @@ __global__ __launch_bounds__(256) void k_big_assemble_chunked(DevPlan P, const i
   for (int i = lane; i < n; i += 64) col[i] = base[i];
 }
 
+// The same decomposition ((column, chunk) = one wave, the chunk in LDS, every front entry written once) and the same summation order,
+// driven by the flat records of asm_pieces.h: one unit record, then one coalesced load of the unit's piece records (16 bytes per
+// lane), then payload -- two dependent round trips instead of four (ea_ptr, ea_rec, cutv, payload).  The payload is staged in
+// registers: the 64-row groups of the unit's pieces form ONE sequence across piece boundaries, walked by a wave-uniform cursor;
+// two sets of kAsmStage groups alternate, the index and value loads of a whole set are issued before the set ahead of it is
+// applied, and the first set travels together with the A entries of the column.  The arrays are indexed statically, the per-group
+// row counts live in SGPRs.
+// Measured (S-metric): a wave lives through a chain of dependent round trips (front, unit, records,
+// payload, the store's drain) and carries only a few KiB, so what pays is waves, not depth: chunks of 512 rows (16 KiB of LDS per
+// workgroup: 8 waves per SIMD, the register limit, instead of 5) and sets of 2 groups (most units hold fewer than ten groups: the
+// groups of a set past the end still cost their instructions) -- 32 waves x 2 sets x 2 groups x 768 B = 96 KiB in flight per CU at
+// the peak.  Sets of 8 groups with chunks of 1024 rows: 0.2 ms per factorisation slower.
+#ifndef OKKT_ASM_STAGE
+#define OKKT_ASM_STAGE 2
+#endif
+#ifndef OKKT_ASM_STAGED_CHUNK
+#define OKKT_ASM_STAGED_CHUNK 512
+#endif
+constexpr int kAsmStage = OKKT_ASM_STAGE;
+constexpr int kAsmStagedChunk = OKKT_ASM_STAGED_CHUNK;     // rows per chunk of the staged kernel and of its records
+__global__ __launch_bounds__(256) void k_big_assemble_staged(DevPlan P, const int* __restrict__ list) {
+  __shared__ __attribute__((aligned(16))) double sm[4 * kAsmStagedChunk];
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int s = list[blockIdx.y];
+  if (stop_requested_wave(P)) return;
+  const int col0 = P.sn_col0[s];
+  const int k = P.sn_col0[s + 1] - col0;
+  const int f = (int)(P.row_ptr[s + 1] - P.row_ptr[s]);
+  const int pc = blockIdx.x * 4 + wv;
+  if (pc >= f) return;
+  const int t = blockIdx.z;
+  const int r0 = max(pc, t * kAsmStagedChunk), r1 = min(f, (t + 1) * kAsmStagedChunk);
+  if (r0 >= r1) return;
+  const AsmUnit U = P.asm_unit[P.asm_unit_base[s] + (int64_t)t * f + pc];
+  double* base = sm + wv * kAsmStagedChunk;      // base[row - r0]
+  const int n = r1 - r0;
+  constexpr int D = kAsmStage;
+  // the cursor over the unit's pieces, 64 records at a time (lane l holds piece p0 + l): piece p of the block (its record read out
+  // of lane p), rows off .. of it go into the next group
+  int np = 0, p = 0, off = 0, cn = 1;
+  int rsl = 0, rsh = 0, rrel = 0, rn = 0;
+  int64_t csrc = 0, crel = 0;
+  auto seek = [&]() {
+    csrc = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane(rsh, p) << 32) | (uint32_t)__builtin_amdgcn_readlane(rsl, p));
+    crel = __builtin_amdgcn_readlane(rrel, p);
+    cn = __builtin_amdgcn_readlane(rn, p);
+  };
+  auto load_block = [&](int p0) {
+    np = min(64, U.np - p0);
+    const AsmPiece R = P.asm_piece[U.piece0 + p0 + min(lane, np - 1)];
+    rsl = (int)(uint32_t)R.src; rsh = (int)(R.src >> 32); rrel = R.rel; rn = R.n;
+    p = 0; off = 0;
+    seek();
+  };
+  int dA[D], dB[D], cA[D], cB[D];
+  double vA[D], vB[D];
+  // requests the next D groups (clamped addresses, no branch around a load: a group past the end re-reads the last entry and counts 0 rows)
+  auto issue = [&](int (&d)[D], double (&v)[D], int (&c)[D]) {
+#pragma unroll
+    for (int u = 0; u < D; ++u) {
+      const int ii = min(off + lane, cn - 1);
+      d[u] = P.rel[crel + ii];
+      v[u] = P.arena[csrc + ii];
+      c[u] = p < np ? min(64, cn - off) : 0;
+      if (p < np) {
+        off += 64;
+        if (off >= cn) {
+          ++p; off = 0;
+          if (p < np) seek();
+        }
+      }
+    }
+    asm volatile("" ::: "memory");       // the requests stay ahead of the set that is applied next
+  };
+  // applies a set in group order; the rows of one group are distinct (a rel list is strictly increasing), two groups may meet in a row
+  auto apply = [&](const int (&d)[D], const double (&v)[D], const int (&c)[D]) {
+#pragma unroll
+    for (int u = 0; u < D; ++u) {
+      if (lane < c[u]) base[d[u] - r0] += v[u];
+      asm volatile("" ::: "memory");
+    }
+  };
+  // the first records and the first set of the payload are requested before the zero fill and the A entries (two more dependent
+  // round trips on a pivot column: entry lists, then values): they travel together
+  if (U.np > 0) { load_block(0); issue(dA, vA, cA); }
+  for (int i = lane; i < n; i += 64) base[i] = 0.0;
+  __threadfence_block();
+  if (pc < k) {
+    const int64_t lo = U.a0, hi = U.a0 + U.na;       // the column's A entries whose rows lie in [r0, r1)
+    const int64_t cbase = (int64_t)pc * f + r0;
+    if (!P.has_dup) {
+      for (int64_t e = lo + lane; e < hi; e += 64) base[(int)(P.aent_dst[e] - cbase)] = P.vals[P.aent_src[e]];
+    } else if (lane == 0) {
+      for (int64_t e = lo; e < hi; ++e) base[(int)(P.aent_dst[e] - cbase)] += P.vals[P.aent_src[e]];
+    }
+    __threadfence_block();
+    if (lane == 0 && pc >= r0 && pc < r1) base[pc - r0] += P.diagadd[col0 + pc];
+    __threadfence_block();
+  }
+  if (U.np > 0)
+    for (int p0 = 0;;) {
+      for (;;) {
+        issue(dB, vB, cB);
+        apply(dA, vA, cA);
+        if (cB[0] == 0) break;
+        issue(dA, vA, cA);
+        apply(dB, vB, cB);
+        if (cA[0] == 0) break;
+      }
+      p0 += 64;
+      if (p0 >= U.np) break;
+      load_block(p0);
+      issue(dA, vA, cA);
+    }
+  __threadfence_block();
+  // one write of the chunk, 16 bytes per lane from the first 16-byte-aligned entry on
+  double* col = P.arena + P.front_pos[s] + (size_t)pc * f + r0 + cb_off(P, s, pc, k);
+  const int head = (int)(((uintptr_t)col >> 3) & 1);
+  if (head && lane == 0) col[0] = base[0];
+  const int n2 = (n - head) >> 1;
+  for (int i = lane; i < n2; i += 64) *(double2*)(col + head + 2 * i) = make_double2(base[head + 2 * i], base[head + 2 * i + 1]);
+  if (((n - head) & 1) && lane == 0) col[n - 1] = base[n - 1];
+}
+
 
 
 
@@ -1297,6 +1421,7 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
   // that launch starts as soon as its own children are done, whatever the rest of its level is doing.
   // Partitioned plans keep the f x f buffers (boundary blocks cross the local / top schedules and the exchange kernels).
   N.release_cb = getenv("OKKT_RELEASE_CB") ? atoi(getenv("OKKT_RELEASE_CB")) : 1;
+  N.asm_staged = getenv("OKKT_ASM_STAGED") ? atoi(getenv("OKKT_ASM_STAGED")) : 1;
   if (parted) N.release_cb = 0;
   std::vector<int64_t> fpos(ns + 1, 0), cbshift(ns, 0);
   if (!N.release_cb) {
@@ -1484,6 +1609,28 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
     }
     if (!(e = upload(N, cutv, &d.cutv)).empty()) return e;
     if (!(e = upload(N, acol_lo, &d.acol_lo)).empty()) return e;
+    {
+      // the flat records of the staged assembly (asm_pieces.h): the same items, cut by chunk on the host
+      std::vector<char> big(ns, 0);
+      std::vector<int64_t> cb_base(ns, 0);
+      for (int s = 0; s < ns; ++s) {
+        const int64_t kc = S.sn_col0[s + 1] - S.sn_col0[s], fc = S.row_ptr[s + 1] - S.row_ptr[s];
+        big[s] = wpos[s] >= 0;
+        cb_base[s] = fpos[s] + cbshift[s] + kc * fc + kc;
+      }
+      AsmPlan A;
+      if (!(e = asm_build_pieces(S, big, cb_base, kAsmStagedChunk, A)).empty()) return e;
+      AsmUnit* du = nullptr;
+      AsmPiece* dp = nullptr;
+      if (!(e = upload(N, A.unit_base, &d.asm_unit_base)).empty()) return e;
+      if (!(e = upload(N, A.units, &du)).empty()) return e;
+      if (!(e = upload(N, A.pieces, &dp)).empty()) return e;
+      d.asm_unit = du;
+      d.asm_piece = dp;
+      N.asm_record_bytes = A.bytes();
+      if (getenv("OKKT_DEBUG_FRONTS")) fprintf(stderr, "okkt: staged assembly records %.1f MB (%lld units, %lld pieces of %lld items) = %.2f %% of the front arena\n", A.bytes() * 1e-6,
+                                              (long long)A.units.size(), (long long)A.pieces.size(), (long long)A.items, 100.0 * A.bytes() / (8.0 * N.arena_doubles));
+    }
     if (N.schur_sn >= 0) {
       N.schur_gcb = bigcol_base[N.schur_sn];
       if (!(e = upload(N, std::vector<int>{N.schur_sn}, &N.schur_list)).empty()) return e;
@@ -1630,7 +1777,9 @@ std::string numeric_factor_enqueue(Numeric& N, const double* d_vals, double tol,
     // Schur mode: the Schur front is assembled -- A22 plus the extend-add of its children's contribution blocks -- and not factored:
     // the assembled front is S = A22 - A21 A11^-1 A12 (lower triangle).  The big-front assembly kernels, one front.
     const int f = N.sn_f[N.schur_sn];
-    if (f > 2048) hipLaunchKernelGGL(k_big_assemble_chunked, dim3((f + 3) / 4, 1, (f + kAsmChunk - 1) / kAsmChunk), dim3(256), 0, st, P, N.schur_list);
+    static const int chunked_on = getenv("OKKT_ASM_CHUNKED") ? atoi(getenv("OKKT_ASM_CHUNKED")) : 1;
+    if (N.asm_staged && chunked_on) hipLaunchKernelGGL(k_big_assemble_staged, dim3((f + 3) / 4, 1, (f + kAsmStagedChunk - 1) / kAsmStagedChunk), dim3(256), 0, st, P, N.schur_list);
+    else if (f > 2048) hipLaunchKernelGGL(k_big_assemble_chunked, dim3((f + 3) / 4, 1, (f + kAsmChunk - 1) / kAsmChunk), dim3(256), 0, st, P, N.schur_list);
     else {
       const int lcol = std::max(256, (f + 63) / 64 * 64);
       hipLaunchKernelGGL(k_big_assemble<true>, dim3((f + 3) / 4, 1), dim3(256), (size_t)4 * lcol * sizeof(double), st, P, N.schur_list, lcol);
@@ -1745,8 +1894,12 @@ static std::string factor_sched(Numeric& N, DevPlan P, const std::vector<LevelSc
         if (lcol_max <= 0) lcol = 0;
         // lower levels (many fronts, short items): loads of four items batched; upper levels: item after item
         static const int chunked = getenv("OKKT_ASM_CHUNKED") ? atoi(getenv("OKKT_ASM_CHUNKED")) : 1;
-        static const int chunk_min = getenv("OKKT_ASM_CHUNK_MIN") ? atoi(getenv("OKKT_ASM_CHUNK_MIN")) : 2048;
-        if (g.maxf > chunk_min && chunked) hipLaunchKernelGGL(k_big_assemble_chunked, dim3((g.maxf + 3) / 4, g.cnt, (g.maxf + kAsmChunk - 1) / kAsmChunk), dim3(256), 0, st, P, list);
+        // the staged kernel takes every big front (measured: faster than the LDS-column kernel on the lower levels as well); the
+        // chunked kernel it replaces (OKKT_ASM_STAGED=0) starts above 2048 rows
+        static const int chunk_min_env = getenv("OKKT_ASM_CHUNK_MIN") ? atoi(getenv("OKKT_ASM_CHUNK_MIN")) : -1;
+        const int chunk_min = chunk_min_env >= 0 ? chunk_min_env : (N.asm_staged ? 0 : 2048);
+        if (g.maxf > chunk_min && chunked && N.asm_staged) hipLaunchKernelGGL(k_big_assemble_staged, dim3((g.maxf + 3) / 4, g.cnt, (g.maxf + kAsmStagedChunk - 1) / kAsmStagedChunk), dim3(256), 0, st, P, list);
+        else if (g.maxf > chunk_min && chunked) hipLaunchKernelGGL(k_big_assemble_chunked, dim3((g.maxf + 3) / 4, g.cnt, (g.maxf + kAsmChunk - 1) / kAsmChunk), dim3(256), 0, st, P, list);
         else if (g.maxf <= 2048) hipLaunchKernelGGL(k_big_assemble<true>, dim3((g.maxf + 3) / 4, g.cnt), dim3(256), (size_t)4 * lcol * sizeof(double), st, P, list, lcol);
         else hipLaunchKernelGGL(k_big_assemble<false>, dim3((g.maxf + 3) / 4, g.cnt), dim3(256), (size_t)4 * lcol * sizeof(double), st, P, list, lcol);
       }
