@@ -1,5 +1,5 @@
 // Condition estimation and forward error bounds (condest.hip): the device work of the Higham-Tisseur
-// block 1-norm estimator around the multi-right-hand-side solves (api.cpp drives it from the host).
+// block 1-norm estimator around the multi-right-hand-side solves (api_condest.cpp drives it from the host).
 #pragma once
 #include <hip/hip_runtime.h>
 

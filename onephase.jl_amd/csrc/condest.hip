@@ -2,7 +2,7 @@
 //
 // The Higham-Tisseur block 1-norm estimator (SIAM J. Matrix Anal. Appl. 21, 2000, Algorithm 2.4) applied to F^-1 (F symmetric:
 // F^-T = F^-1) or, for the forward error bound, to diag(f) F^-1.  Its products are solve passes of the existing multi-right-hand-
-// side path (api.cpp); this file holds everything else, all of it bandwidth- or latency-bound:
+// side path (api_condest.cpp); this file holds everything else, all of it bandwidth- or latency-bound:
 //   - ||F||_1: exact row sums of |F| over the refinement's row-wise map (refine.h) plus the factorisation's diagonal shift, sized
 //     as the residual kernels are (a lane group per short row, a workgroup per long row);
 //   - after Y = op X: the column 1-norms, S = sign(Y), the +-1 dot products that tell parallel columns apart (exact integer counts);

@@ -1,6 +1,6 @@
 // Vector kernels of GMRES-based iterative refinement, gfx950.
 //
-// The GMRES cycles of okkt_solve_gmres (api.cpp) orthogonalise each new vector w = A F^-1 v_j against the basis V = [v_0 .. v_j]
+// The GMRES cycles of okkt_solve_gmres (api_refine.cpp) orthogonalise each new vector w = A F^-1 v_j against the basis V = [v_0 .. v_j]
 // by classical Gram-Schmidt with one full reorthogonalisation (CGS2).  Per iteration three passes over V:
 //   k_kry_pass<dots>        h1 = V^T w (w read once per chunk of 16 basis vectors)
 //   k_kry_pass<orth, dots>  w = w - V h1, fused with the partial sums of h2 = V^T w

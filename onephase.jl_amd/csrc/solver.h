@@ -105,19 +105,19 @@ inline int schur_refuse(okkt_solver_s* h, const char* what) {
 int solver_ensure_numeric(okkt_solver_s* h);
 // okkt_set_scaling behind its argument checks (api.cpp): also what okkt_kkt_set_ls_scaling forwards to
 int solver_set_scaling(okkt_solver_s* h, int mode, int32_t sweeps, const double* s_user);
-// refinement driver (api.cpp): x = F \ b, then corrections from the double-double residual against d_nzval until omega <= tol,
+// refinement driver (api_refine.cpp): x = F \ b, then corrections from the double-double residual against d_nzval until omega <= tol,
 // stagnation, a non-finite value or max_steps.  d_rhs, d_sol: nrhs x n on the device (they may alias).  lap(tag), if given, is called at
 // the phase boundaries (tag 0: a solve ended, 1: residual / vector work ended); n_solves_out: right-hand sides solved
 int solver_refine_device(okkt_solver_s* h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
                          double tol, okkt_refine_info* info, double* omega_out, void (*lap)(void*, int) = nullptr, void* lap_ctx = nullptr,
                          int* n_solves_out = nullptr);
 void solver_refine_release(okkt_solver_s* h);
-// GMRES-based refinement driver (api.cpp): x = F \ b, then outer steps of one double-double residual and one
+// GMRES-based refinement driver (api_refine.cpp): x = F \ b, then outer steps of one double-double residual and one
 // right-preconditioned GMRES(restart) cycle on A d = r each, right-hand sides in lockstep groups of up to four.  Pointers as
 // solver_refine_device's.  schur_route (here and in the two estimates below): F^-1 is the Schur route's whole-system solve (section 8.10)
 int solver_gmres_device(okkt_solver_s* h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t restart,
                         int32_t max_iters, double tol, okkt_gmres_info* info, double* omega_out, bool schur_route = false);
-// condition estimate of the factored F (the values d_nzval plus the factorisation's diagonal shift) and forward error bounds (api.cpp)
+// condition estimate of the factored F (the values d_nzval plus the factorisation's diagonal shift) and forward error bounds (api_condest.cpp)
 int solver_condest_device(okkt_solver_s* h, const double* d_nzval, int32_t t, okkt_condest_info* info, bool schur_route = false);
 int solver_forward_error_device(okkt_solver_s* h, const double* d_nzval, const double* d_b, const double* d_x, int64_t nrhs, double* ferr_out,
                                 double* berr_out, bool schur_route = false);

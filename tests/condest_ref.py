@@ -1,4 +1,4 @@
-"""numpy restatement of the condition estimator of condest.hip / api.cpp: Higham and Tisseur's block 1-norm
+"""numpy restatement of the condition estimator of condest.hip / api_condest.cpp: Higham and Tisseur's block 1-norm
 estimator (Algorithm 2.4) applied to F^-1 (or diag(f) F^-1), with the same fixed generator, the same replacement of parallel sign
 columns and the same tie rules.  `solve(B)` returns F^-1 B for an n x t block; the tests drive it with exact dense solves."""
 import numpy as np
