@@ -623,6 +623,50 @@ int okkt_kkt_get_timers(okkt_kkt_handle k, okkt_kkt_timers* out);
 /* ipopt_strategy!: returns 1 on :success, 0 on :failure (delta > delta_max), <0 on error */
 int okkt_kkt_ipopt_strategy(okkt_kkt_handle k, double delta_prev, const okkt_kkt_pars* pars,
                             int32_t* num_fac_out, double* delta_out);
+
+/* ---- A Lanczos bound on lambda_min(H + J' Sigma J) for the delta loop ----
+ * With Sigma = diag(y ./ s) > 0, K(delta) = [[H + delta I, J'], [J, -inv(Sigma)]] has inertia (n, m, 0) exactly when
+ * Q(delta) = H + J' Sigma J + delta I is positive definite, and the Cholesky flag of the Schur kinds is decided by the same Q(delta).
+ * For any v with Rayleigh quotient rho = v'Q(0)v / v'v every attempt with delta <= -rho fails.  okkt_kkt_min_eig finds such a v by at
+ * most max_steps Lanczos steps (full reorthogonalisation) on Q(0) of the iterate of the last okkt_kkt_form_system, matrix-free from
+ * the H, J and Sigma the handle holds (no delta; the same operator whatever the kind and schur_dense_rows).  scaled = 1 runs Lanczos on
+ * D Q(0) D, d_i = 1 / sqrt(|schur_diag_i|) (1 where that entry is 0 or not finite); the certificate is taken on the unscaled Q(0)
+ * with v = D w either way.  Two calls give the same bits.  The call uses a workspace of its own ((max_steps + 1) n doubles and a few
+ * vectors, released with the handle): the resident right-hand side and direction and the handle's work vectors are not touched.
+ * Refused with OKKT_ERR_INVALID (okkt_kkt_last_error says why; the handle stays usable): the clever-symmetric kind, a call before
+ * okkt_kkt_form_system, max_steps > 64, scaled other than 0 / 1, and n or a row / column of J or a row of H of 2^24 entries or more
+ * (rho_margin would not cover the rounding of rho); host_symbolic_only handles get OKKT_ERR_NO_DEVICE. */
+typedef struct {
+  double theta_min, theta_max; /* extreme Ritz values of the operator Lanczos ran on (the scaled one when scaled = 1) */
+  double bound;                /* |beta_k s_k1|: an eigenvalue of that operator lies within this of theta_min */
+  double rho;                  /* Rayleigh quotient v'Q(0)v / v'v of the returned v on the UNSCALED Q(0), recomputed explicitly */
+  double rho_abs;              /* (|v|'|H||v| + sum_i sigma_i (|J||v|)_i^2) / v'v: the scale of rho's rounding error */
+  double rho_margin;           /* 2^-26 * rho_abs: attempts with delta <= -rho - rho_margin are certified to fail */
+  double resid;                /* ||Q(0) v - rho v||_2 / ||v||_2, explicit */
+  int32_t steps;               /* Lanczos steps taken */
+  int32_t status;              /* 0 bound <= tol * |theta_min|, 1 step limit, 2 invariant subspace (beta = 0), 3 non-finite */
+  double seconds_device;
+} okkt_kkt_eig_info;
+/* status 3: rho, rho_abs, rho_margin and resid are NaN and v_out is zero.  beta counts as 0 at 2^-44 of the largest Ritz value in
+ * magnitude.  At most min(max_steps, n) steps are taken. */
+int okkt_kkt_min_eig(okkt_kkt_handle k, int32_t max_steps /* 1..64, <= 0: 32 */, double tol /* <= 0: 2^-4 */,
+                     int32_t scaled /* 0 / 1 */, okkt_kkt_eig_info* info, double* v_out /* [n] host, or NULL */);
+/* okkt_kkt_ipopt_strategy with the same tau, first attempt, delta sequence, delta_max exit and completion of an early-exited last
+ * trial, except that okkt_kkt_min_eig(max_steps, default tol, scaled) runs once, right after the first failed attempt, and an attempt
+ * of the sequence with delta <= -rho - rho_margin and delta <= delta_max is not factored (nor scanned for diagonal dominance): it is
+ * counted in skipped_out instead of num_fac_out.  An attempt with delta > delta_max is never skipped.  With status 3 or rho >= 0
+ * nothing is skipped.  Status, delta_out and the factor left behind are those of okkt_kkt_ipopt_strategy.  info (or NULL): the
+ * estimate; steps = 0 when Lanczos never ran.  Refusals as okkt_kkt_min_eig. */
+int okkt_kkt_ipopt_strategy_eig(okkt_kkt_handle k, double delta_prev, const okkt_kkt_pars* pars,
+                                int32_t max_steps, int32_t scaled,
+                                int32_t* num_fac_out, double* delta_out, int32_t* skipped_out,
+                                okkt_kkt_eig_info* info /* or NULL; steps = 0 when Lanczos never ran */);
+/* Test hook, host only (no device, no handle): the tridiagonal solver of okkt_kkt_min_eig (csrc/lanczos_tridiag.h) on
+ * T = tridiag(beta[0 .. k-2]; alpha[0 .. k-1]), 1 <= k <= 64.  beta holds k entries: beta[k-1] is the residual coefficient beta_k of
+ * the Lanczos recurrence.  Returns theta_min, theta_max, the unit eigenvector s_out [k] of theta_min (largest entry positive) and
+ * bound = |beta[k-1] s_out[k-1]|.  OKKT_ERR_INVALID for k out of range, a NULL pointer or a non-finite entry. */
+int okkt_debug_tridiag_eig(int32_t k, const double* alpha, const double* beta, double* theta_min, double* theta_max,
+                           double* s_out, double* bound);
 /* compute_direction! for nrhs reduction-factor triples in one pass over the factor: the probe of the aggressive step
  * (Reduct_affine, take_step.jl:2-3) and the candidates of take_step2! (take_step.jl:34-66) share the factorised system.
  * System_rhs (system_rhs.jl:57-73) is evaluated on the device for every triple from the iterate of the last okkt_kkt_system_rhs;

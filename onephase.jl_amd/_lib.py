@@ -224,6 +224,26 @@ class OkktScalingInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktKktEigInfo(C.Structure):
+    """okkt_kkt_eig_info: the Lanczos estimate of lambda_min(H + J' Sigma J) (status 0 converged, 1 step limit, 2 invariant subspace,
+    3 non-finite); attempts of the delta loop with delta <= -rho - rho_margin are certified to fail."""
+    _fields_ = [
+        ("theta_min", C.c_double),
+        ("theta_max", C.c_double),
+        ("bound", C.c_double),
+        ("rho", C.c_double),
+        ("rho_abs", C.c_double),
+        ("rho_margin", C.c_double),
+        ("resid", C.c_double),
+        ("steps", C.c_int32),
+        ("status", C.c_int32),
+        ("seconds_device", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/okkt.h declares, with its signature
 _i64p = C.POINTER(C.c_int64)
 _f64p = C.POINTER(C.c_double)
@@ -343,6 +363,10 @@ SIGNATURES = {
     "okkt_kkt_get_timers": (C.c_int, [_vp, C.POINTER(OkktKktTimers)]),
     "okkt_kkt_get_direction": (C.c_int, [_vp, _f64p, _f64p, _f64p]),
     "okkt_kkt_ipopt_strategy": (C.c_int, [_vp, C.c_double, C.POINTER(OkktKktPars), C.POINTER(C.c_int32), _f64p]),
+    "okkt_kkt_min_eig": (C.c_int, [_vp, C.c_int32, C.c_double, C.c_int32, C.POINTER(OkktKktEigInfo), _f64p]),
+    "okkt_kkt_ipopt_strategy_eig": (C.c_int, [_vp, C.c_double, C.POINTER(OkktKktPars), C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p,
+                                              C.POINTER(C.c_int32), C.POINTER(OkktKktEigInfo)]),
+    "okkt_debug_tridiag_eig": (C.c_int, [C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]),
     "okkt_kkt_compute_directions": (C.c_int, [_vp, C.c_int32, _f64p, C.c_int32, _f64p, _f64p, _f64p, C.POINTER(OkktKktError)]),
     "okkt_kkt_is_diag_dom": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "okkt_kkt_diag_dom_warnings": (C.c_int, [_vp, C.POINTER(C.c_int32)]),

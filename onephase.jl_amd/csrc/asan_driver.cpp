@@ -2,7 +2,8 @@
 // UndefinedBehaviorSanitizer on small synthetic patterns -- a banded KKT (level-structure dissection), a 3-D grid, a small-world graph
 // (multilevel dissection with its helper threads) and an arrow matrix -- and the work-item lists of the pivot report (pivots.h) on each
 // of them and on a front tall enough for several chunks per column, and the flat records of the staged big-front assembly
-// (asm_pieces.h) on each of them and under a front of three chunks.  No device code, no HIP call.  SURVEY.md section 5 (host-side
+// (asm_pieces.h) on each of them and under a front of three chunks, and the tridiagonal solver of the Lanczos estimate
+// (lanczos_tridiag.h).  No device code, no HIP call.  SURVEY.md section 5 (host-side
 // sanitizer build); GPU sanitizers are not available on this pool.
 #include <cstdio>
 #include <cstdlib>
@@ -11,11 +12,62 @@
 #include <vector>
 
 #include "asm_pieces.h"
+#include "lanczos_tridiag.h"
 #include "numeric.h"
 #include "pivots.h"
 #include "symbolic.h"
 
 using namespace okkt;
+
+// The tridiagonal solver of okkt_kkt_min_eig (lanczos_tridiag.h) on the shapes its arrays are indexed hardest by: orders 1, 2 and 64
+// (its stack arrays are exactly 64 long), a zero off-diagonal entry in the middle and at both ends, entries 300 decades apart, the zero
+// matrix, and the refused orders 0 and 65.  Checks the residual of the returned pair against the matrix.
+static int check_tridiag() {
+  int bad = 0;
+  std::mt19937_64 rng(7);
+  std::uniform_real_distribution<double> u(-1.0, 1.0);
+  auto one = [&](int k, std::vector<double> a, std::vector<double> b, const char* name) {
+    double tmin = 0.0, tmax = 0.0;
+    std::vector<double> s((size_t)k, 0.0);   // exactly k long: a write past it is caught
+    const int rc = tridiag_extreme(k, a.data(), b.data(), &tmin, &tmax, s.data());
+    if (rc != 0) { fprintf(stderr, "tridiag %s: rc %d\n", name, rc); ++bad; return; }
+    double scale = 0.0, r2 = 0.0, s2 = 0.0;
+    for (int i = 0; i < k; ++i) scale = std::max(scale, std::abs(a[i]));
+    for (int i = 0; i + 1 < k; ++i) scale = std::max(scale, std::abs(b[i]));
+    if (scale == 0.0) scale = 1.0;
+    for (int i = 0; i < k; ++i) {
+      double r = (a[i] / scale) * s[i] - (tmin / scale) * s[i];
+      if (i > 0) r += (b[i - 1] / scale) * s[i - 1];
+      if (i + 1 < k) r += (b[i] / scale) * s[i + 1];
+      r2 += r * r; s2 += s[i] * s[i];
+    }
+    if (!(tmin <= tmax) || std::abs(s2 - 1.0) > 1e-12 || !(std::sqrt(r2) <= 1e-9)) {
+      fprintf(stderr, "tridiag %s: theta %g %g, |s|^2 %g, residual %g\n", name, tmin, tmax, s2, std::sqrt(r2));
+      ++bad;
+    }
+  };
+  for (int k : {1, 2, 3, 17, 63, 64}) {
+    std::vector<double> a((size_t)k), b((size_t)std::max(k - 1, 1));   // the solver reads k - 1 off-diagonal entries, no more
+    for (double& v : a) v = 10.0 * u(rng);
+    for (double& v : b) v = u(rng);
+    one(k, a, b, "random");
+    if (k >= 3) {
+      b[(size_t)(k / 2)] = 0.0; one(k, a, b, "zero in the middle");
+      b[0] = 0.0; b[(size_t)(k - 2)] = 0.0; one(k, a, b, "zeros at the ends");
+    }
+    for (double& v : b) v = 0.0;
+    one(k, a, b, "diagonal");
+    for (double& v : a) v = 0.0;
+    one(k, a, b, "zero");
+  }
+  one(6, {1e150, -1e-150, 2.0, -1e150, 1e-150, 1.0}, {1e-150, 1.0, 1e100, 1e-150, 1e149}, "300 decades");
+  {
+    double a[65] = {0}, t0 = 0.0, t1 = 0.0, s[65];
+    if (tridiag_extreme(0, a, a, &t0, &t1, s) != 1 || tridiag_extreme(65, a, a, &t0, &t1, s) != 1) { fprintf(stderr, "tridiag: order 0 / 65 not refused\n"); ++bad; }
+  }
+  if (!bad) printf("tridiag      orders 1 .. 64, split, scaled and refused cases clean\n");
+  return bad;
+}
 
 static void csc_lower(int n, const std::set<std::pair<int, int>>& e, std::vector<int64_t>& cp, std::vector<int64_t>& ri) {
   std::vector<std::vector<int>> cols(n);
@@ -239,6 +291,7 @@ int main() {
     }
     bad += run("three-chunks", n, e, 1);
   }
+  bad += check_tridiag();
   if (bad) { fprintf(stderr, "%d case(s) failed\n", bad); return 1; }
   printf("asan driver: all cases clean\n");
   return 0;

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "kkt_state.h"
+#include "lanczos.h"
 
 using namespace okkt;
 
@@ -707,6 +708,7 @@ int okkt_kkt_destroy(okkt_kkt_handle k) {
   if (!k) return OKKT_ERR_INVALID;
   if (k->ls && k->ls->device_ready) { (void)hipSetDevice(k->ls->device); (void)hipStreamSynchronize(k->ls->stream); }
   for (void* p : k->allocs) (void)hipFree(p);
+  lanczos_release(k);
   k->tm_form.destroy(); k->tm_factor.destroy(); k->tm_rhs.destroy(); k->tm_dir.destroy();
   if (k->ls) okkt_destroy(k->ls);
   delete k;
@@ -768,6 +770,9 @@ int okkt_kkt_set_structure(okkt_kkt_handle k, int64_t n, int64_t m, const int64_
     std::vector<int> Hrj, Jrj;
     csr_view(n, n, Hp, Hi, Hrp, Hrj, Hrmap);
     csr_view(m, n, Jp, Ji, Jrp, Jrj, Jrmap);
+    k->eig_maxlen = 0;
+    for (int64_t i = 0; i < m; ++i) k->eig_maxlen = std::max(k->eig_maxlen, Jrp[i + 1] - Jrp[i]);
+    for (int64_t j = 0; j < n; ++j) k->eig_maxlen = std::max(k->eig_maxlen, std::max(Jp[j + 1] - Jp[j], (Hp[j + 1] - Hp[j]) + (Hrp[j + 1] - Hrp[j])));
     int rc;
 #define UPL(dst, vec) if ((rc = kk_upload(k, vec, &k->dst)) != OKKT_OK) return rc
     UPL(Hp, Hp); UPL(Hi, Hi); UPL(Hrp, Hrp); UPL(Hrj, Hrj); UPL(Hrmap, Hrmap);
@@ -1170,8 +1175,12 @@ int okkt_kkt_get_timers(okkt_kkt_handle k, okkt_kkt_timers* out) {
   return OKKT_OK;
 }
 
-int okkt_kkt_ipopt_strategy(okkt_kkt_handle k, double delta_prev, const okkt_kkt_pars* pars, int32_t* num_fac_out, double* delta_out) {
-  if (!k || !num_fac_out || !delta_out) return OKKT_ERR_INVALID;
+// ipopt_strategy! (delta_strategy.jl:37-114): the one loop behind okkt_kkt_ipopt_strategy (eig = false) and
+// okkt_kkt_ipopt_strategy_eig (eig = true).  With eig the Lanczos estimate of lambda_min(Q(0)) runs once, right after the first failed
+// attempt, and an attempt of the sequence with delta <= -rho - rho_margin (and delta <= delta_max) is not factored: Q(0) + delta I has
+// a non-positive Rayleigh quotient at the returned vector, so the attempt is certain to fail
+static int ipopt_strategy_impl(okkt_kkt_s* k, double delta_prev, const okkt_kkt_pars* pars, bool eig, int32_t eig_steps, int32_t eig_scaled,
+                               int32_t* num_fac_out, double* delta_out, int32_t* skipped_out, okkt_kkt_eig_info* info) {
   okkt_kkt_pars P;
   okkt_kkt_default_pars(&P);
   if (pars) P = *pars;
@@ -1189,6 +1198,22 @@ int okkt_kkt_ipopt_strategy(okkt_kkt_handle k, double delta_prev, const okkt_kkt
     if (rc3 == OKKT_OK && dom == 1) ++k->diag_dom_warnings;
     return rc3;
   };
+  // eig: the estimate, once; skip_below = -rho - rho_margin when it certifies anything (status 3 or rho >= 0: nothing)
+  bool eig_ran = false, can_skip = false;
+  double skip_below = 0.0;
+  auto estimate_after_failure = [&]() -> int {
+    if (!eig || eig_ran) return OKKT_OK;
+    eig_ran = true;
+    okkt_kkt_eig_info E;
+    const int rc4 = kk_min_eig(k, eig_steps, 0.0, eig_scaled, &E, nullptr);
+    if (rc4 != OKKT_OK) return rc4;
+    if (info) *info = E;
+    if (E.status != 3 && E.rho < 0.0 && E.rho_margin >= 0.0) {
+      skip_below = -E.rho - E.rho_margin;
+      can_skip = skip_below > 0.0;
+    }
+    return OKKT_OK;
+  };
   int rc = okkt_kkt_diag_min(k, &dmin);
   if (rc != OKKT_OK) return rc;
   double tau = 1.5 * dmin;
@@ -1202,6 +1227,7 @@ int okkt_kkt_ipopt_strategy(okkt_kkt_handle k, double delta_prev, const okkt_kkt
     ++num_fac;
     if (rc == 1) { *num_fac_out = num_fac; *delta_out = delta; return 1; }
     if ((rc = scan_after_failure()) < 0) return rc;
+    if ((rc = estimate_after_failure()) < 0) return rc;
   }
   for (int i = 1; i <= P.max_it; ++i) {
     if (i == 1) {
@@ -1210,6 +1236,7 @@ int okkt_kkt_ipopt_strategy(okkt_kkt_handle k, double delta_prev, const okkt_kkt
     } else {
       delta = delta * P.delta_inc;
     }
+    if (can_skip && delta <= skip_below && delta <= P.delta_max) { ++*skipped_out; continue; }   // certified to fail: not factored
     rc = okkt_kkt_factor_trial(k, delta, nullptr);   // a failed attempt is discarded: it may stop early
     if (rc < 0) return rc;
     ++num_fac;
@@ -1217,6 +1244,7 @@ int okkt_kkt_ipopt_strategy(okkt_kkt_handle k, double delta_prev, const okkt_kkt
     *delta_out = delta;
     if (rc == 1) return 1;
     { const int rc3 = scan_after_failure(); if (rc3 < 0) return rc3; }
+    { const int rc4 = estimate_after_failure(); if (rc4 < 0) return rc4; }
     if (delta > P.delta_max) {   // :failure
       // The reference's default initialiser does not look at the status: gertz_init.jl:25-27 runs ipopt_strategy!,
       // kkt_associate_rhs! and compute_direction! whatever came back, i.e. it solves with the failed factor of the last
@@ -1229,6 +1257,27 @@ int okkt_kkt_ipopt_strategy(okkt_kkt_handle k, double delta_prev, const okkt_kkt
     }
   }
   return kk_fail(k, OKKT_ERR_INTERNAL, "max it");   // error("max it"), delta_strategy.jl:113
+}
+
+int okkt_kkt_ipopt_strategy(okkt_kkt_handle k, double delta_prev, const okkt_kkt_pars* pars, int32_t* num_fac_out, double* delta_out) {
+  if (!k || !num_fac_out || !delta_out) return OKKT_ERR_INVALID;
+  int32_t skipped = 0;
+  return ipopt_strategy_impl(k, delta_prev, pars, false, 0, 0, num_fac_out, delta_out, &skipped, nullptr);
+}
+
+int okkt_kkt_ipopt_strategy_eig(okkt_kkt_handle k, double delta_prev, const okkt_kkt_pars* pars, int32_t max_steps, int32_t scaled,
+                                int32_t* num_fac_out, double* delta_out, int32_t* skipped_out, okkt_kkt_eig_info* info) {
+  if (!k || !num_fac_out || !delta_out || !skipped_out) return OKKT_ERR_INVALID;
+  *skipped_out = 0;
+  if (info) std::memset(info, 0, sizeof(*info));
+  // the refusals of okkt_kkt_min_eig, before any attempt is factored
+  if (!k->ls || k->ls->opts.host_symbolic_only || !k->ls->device_ready) return kk_fail(k, OKKT_ERR_NO_DEVICE, "no HIP device (host_symbolic_only handle)");
+  if (k->kind == OKKT_KKT_CLEVER_SYMMETRIC) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_ipopt_strategy_eig: not for the clever-symmetric kind (its factored matrix is the merged and rescaled M, not K(delta))");
+  if (max_steps > 64) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_ipopt_strategy_eig: max_steps > 64");
+  if (scaled != 0 && scaled != 1) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_ipopt_strategy_eig: scaled must be 0 or 1");
+  if (k->n >= ((int64_t)1 << 24) || k->eig_maxlen >= ((int64_t)1 << 24))
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_ipopt_strategy_eig: n, the longest row or column of J or the longest row of H reaches 2^24: rho_margin = 2^-26 rho_abs would not cover the rounding of rho");
+  return ipopt_strategy_impl(k, delta_prev, pars, true, max_steps, scaled, num_fac_out, delta_out, skipped_out, info);
 }
 
 int okkt_kkt_system_rhs(okkt_kkt_handle k, const double* J_nzval_cur, const double* grad, const double* cons,

@@ -9,6 +9,8 @@
 
 #include "solver.h"
 
+namespace okkt { struct LanczosWork; }
+
 struct okkt_kkt_s {
   okkt_handle ls = nullptr;
   int kind = OKKT_KKT_SCHUR;
@@ -123,6 +125,10 @@ struct okkt_kkt_s {
   int *mind = nullptr, *row_grp = nullptr, *dAi = nullptr, *Arj = nullptr, *Hcol = nullptr, *Jcol = nullptr;
   double *mratio = nullptr, *row_ratio = nullptr, *gU = nullptr, *rowg = nullptr, *Dres = nullptr, *true_x_diag = nullptr;
   double *crhs = nullptr, *big3 = nullptr, *big4 = nullptr;
+  // okkt_kkt_min_eig (lanczos.hip): its workspace (allocated on first use, released with the handle) and the longest of the sums its
+  // operator nests (rows and columns of J, rows of the symmetric H), from okkt_kkt_set_structure
+  okkt::LanczosWork* lz = nullptr;
+  int64_t eig_maxlen = 0;
 };
 
 #define KK_TRY(k, expr)                                                                      \

@@ -40,6 +40,19 @@ mutable struct HIP_KKT_solver <: abstract_KKT_system_solver
     end
 end
 
+struct OkktKktEigInfo   # okkt_kkt_eig_info of include/okkt.h
+    theta_min::Float64
+    theta_max::Float64
+    bound::Float64
+    rho::Float64
+    rho_abs::Float64
+    rho_margin::Float64
+    resid::Float64
+    steps::Int32
+    status::Int32
+    seconds_device::Float64
+end
+
 struct OkktKktPars      # okkt_kkt_pars of include/okkt.h
     delta_start::Float64
     delta_min::Float64
@@ -166,13 +179,34 @@ function factor_implementation!(k::HIP_KKT_solver, timer::class_advanced_timer)
         (Ptr{Cvoid}, Float64, Ref{OkktInertia}), k.handle, delta, inert)))
 end
 
+# okkt_kkt_min_eig: (info, v) -- the Lanczos estimate of lambda_min(Q(0)), Q(0) = H + J' Sigma J of the last form_system!, and the vector
+# whose Rayleigh quotient on Q(0) is info.rho; every factor! with delta <= -info.rho - info.rho_margin has the wrong inertia
+function min_eig(k::HIP_KKT_solver, max_steps::Integer=0, tol::Float64=0.0, scaled::Integer=0)
+    info = Ref(OkktKktEigInfo(0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0.0))
+    v = zeros(dim(k.factor_it))
+    kkt_hip_check(k, "okkt_kkt_min_eig", ccall((:okkt_kkt_min_eig, OKKT_LIB), Cint,
+        (Ptr{Cvoid}, Int32, Float64, Int32, Ref{OkktKktEigInfo}, Ptr{Float64}), k.handle, max_steps, tol, scaled, info, v))
+    return info[], v
+end
+
 # ipopt_strategy! (delta_strategy.jl:37-114) for this solver type: the whole loop behind one ccall; (status, num_fac, delta)
 # are those of the reference's loop
 function ipopt_strategy!(iter::Class_iterate, k::HIP_KKT_solver, pars::Class_parameters, timer::class_advanced_timer)
     num_fac = Ref{Int32}(0); delta = Ref{Float64}(0.0)
     p = OkktKktPars(pars.delta.start, pars.delta.min, pars.delta.max, pars.delta.inc, pars.delta.dec, pars.delta.zero, Int32(pars.kkt.ItRefine_Num), Int32(500))
-    rc = kkt_hip_check(k, "okkt_kkt_ipopt_strategy", ccall((:okkt_kkt_ipopt_strategy, OKKT_LIB), Cint,
-        (Ptr{Cvoid}, Float64, Ref{OkktKktPars}, Ref{Int32}, Ref{Float64}), k.handle, get_delta(iter), p, num_fac, delta))
+    # pars.kkt.hip_delta_eig_steps > 0 ("kkt!hip_delta_eig_steps", "kkt!hip_delta_eig_scaled"): the same loop without the attempts that a
+    # Lanczos bound on lambda_min(H + J' Sigma J) certifies to fail (okkt_kkt_ipopt_strategy_eig); status and delta do not change
+    eig_steps = hasproperty(pars.kkt, :hip_delta_eig_steps) ? pars.kkt.hip_delta_eig_steps : 0
+    eig_scaled = hasproperty(pars.kkt, :hip_delta_eig_scaled) ? pars.kkt.hip_delta_eig_scaled : 0
+    if eig_steps > 0
+        skipped = Ref{Int32}(0); info = Ref(OkktKktEigInfo(0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0.0))
+        rc = kkt_hip_check(k, "okkt_kkt_ipopt_strategy_eig", ccall((:okkt_kkt_ipopt_strategy_eig, OKKT_LIB), Cint,
+            (Ptr{Cvoid}, Float64, Ref{OkktKktPars}, Int32, Int32, Ref{Int32}, Ref{Float64}, Ref{Int32}, Ref{OkktKktEigInfo}),
+            k.handle, get_delta(iter), p, eig_steps, eig_scaled, num_fac, delta, skipped, info))
+    else
+        rc = kkt_hip_check(k, "okkt_kkt_ipopt_strategy", ccall((:okkt_kkt_ipopt_strategy, OKKT_LIB), Cint,
+            (Ptr{Cvoid}, Float64, Ref{OkktKktPars}, Ref{Int32}, Ref{Float64}), k.handle, get_delta(iter), p, num_fac, delta))
+    end
     k.delta_x_vec = delta[] * ones(dim(iter)); k.delta_s_vec = zeros(ncon(iter))
     k.ready = :factored
     # delta_strategy.jl:94-98: a failed attempt on a diagonally dominant x-block prints a warning; the library ran the scan on the

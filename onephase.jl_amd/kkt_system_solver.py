@@ -118,6 +118,12 @@ class Class_kkt_solver_options:   # parameters.jl:4-46 (the entries the path rea
     # ("kkt!hip_ls_scaling", "kkt!hip_ls_scaling_sweeps")
     hip_ls_scaling: int = 0
     hip_ls_scaling_sweeps: int = 0
+    # Schur, Schur-direct and symmetric kinds, not okkt_opts fields (okkt_kkt_ipopt_strategy_eig): hip_delta_eig_steps > 0 = after the first
+    # failed attempt of ipopt_strategy! at most that many Lanczos steps (<= 64) bound lambda_min(H + J' Sigma J), and the attempts of the
+    # delta sequence that the bound certifies to fail are not factored; the returned status and delta do not change.  0 = off.
+    # hip_delta_eig_scaled = 1: Lanczos on the Jacobi-scaled operator ("kkt!hip_delta_eig_steps", "kkt!hip_delta_eig_scaled")
+    hip_delta_eig_steps: int = 0
+    hip_delta_eig_scaled: int = 0
 
 
 def okkt_opts_from_pars(kkt):
@@ -200,6 +206,11 @@ class HIP_KKT_solver:
         self.ls_refine_tol = float(opts.pop("hip_ls_refine_tol", self.pars.kkt.hip_ls_refine_tol))
         self.ls_scaling = int(opts.pop("hip_ls_scaling", self.pars.kkt.hip_ls_scaling))
         self.ls_scaling_sweeps = int(opts.pop("hip_ls_scaling_sweeps", self.pars.kkt.hip_ls_scaling_sweeps))
+        # the Lanczos bound of the delta loop is an argument of okkt_kkt_ipopt_strategy_eig: keywords override pars.kkt
+        self.delta_eig_steps = int(opts.pop("hip_delta_eig_steps", self.pars.kkt.hip_delta_eig_steps))
+        self.delta_eig_scaled = int(opts.pop("hip_delta_eig_scaled", self.pars.kkt.hip_delta_eig_scaled))
+        self.skipped = 0
+        self.delta_eig_info = None
         self._opts = opts
         self._lib = None
         self._k = None
@@ -475,8 +486,17 @@ class HIP_KKT_solver:
         p.delta_start, p.delta_min, p.delta_max, p.delta_inc, p.delta_dec, p.delta_zero = d.start, d.min, d.max, d.inc, d.dec, d.zero
         nfac = C.c_int32()
         delta = C.c_double()
-        rc = self._check(self._lib.okkt_kkt_ipopt_strategy(self._k, float(it.delta), C.byref(p), C.byref(nfac), C.byref(delta)),
-                         "okkt_kkt_ipopt_strategy")
+        if self.delta_eig_steps > 0:
+            # the same loop without the attempts a Lanczos bound on lambda_min(H + J' Sigma J) certifies to fail: the same status and delta
+            skipped, info = C.c_int32(), L.OkktKktEigInfo()
+            rc = self._check(self._lib.okkt_kkt_ipopt_strategy_eig(self._k, float(it.delta), C.byref(p), self.delta_eig_steps, self.delta_eig_scaled,
+                                                                   C.byref(nfac), C.byref(delta), C.byref(skipped), C.byref(info)),
+                             "okkt_kkt_ipopt_strategy_eig")
+            self.skipped = int(skipped.value)
+            self.delta_eig_info = info.as_dict()
+        else:
+            rc = self._check(self._lib.okkt_kkt_ipopt_strategy(self._k, float(it.delta), C.byref(p), C.byref(nfac), C.byref(delta)),
+                             "okkt_kkt_ipopt_strategy")
         self._delta = delta.value
         self.delta_x_vec = delta.value * np.ones(it.dim())
         self.delta_s_vec = np.zeros(it.ncon())
@@ -488,6 +508,19 @@ class HIP_KKT_solver:
             for _ in range(self.diag_dom_warnings):
                 print("WARNING: Inertia calculation incorrect")
         return ("success" if rc == 1 else "failure"), int(nfac.value), float(delta.value)
+
+    def min_eig(self, max_steps=0, tol=0.0, scaled=0, with_vector=True):
+        """okkt_kkt_min_eig: (info, v) -- the Lanczos estimate of lambda_min(Q(0)), Q(0) = H + J' Sigma J of the last form_system_b, as a
+        dict of okkt_kkt_eig_info, and the vector v whose Rayleigh quotient on Q(0) is info['rho'] (None without with_vector).  Every
+        factor_b with delta <= -rho - rho_margin has the wrong inertia.  max_steps <= 0: 32, tol <= 0: 2^-4."""
+        if self._k is None:
+            raise OkktError("initialize_b has not been called")
+        info = L.OkktKktEigInfo()
+        n = self._pattern[0] if self._pattern is not None else 0
+        v = np.zeros(n) if with_vector else None
+        self._check(self._lib.okkt_kkt_min_eig(self._k, int(max_steps), float(tol), int(scaled), C.byref(info),
+                                               L.p_f64(v) if with_vector else None), "okkt_kkt_min_eig")
+        return info.as_dict(), v
 
     def is_diag_dom(self):
         """is_diag_dom(kkt_solver.Q[1:n,1:n]) (delta_strategy.jl:1-9) at the delta of the last factor!, scanned on the device."""
