@@ -3,7 +3,9 @@ simplicial oracle on the same permutation.  The whole-tree tests (S-small, S-C3,
 ordering produces; here every pivot / CB edge, thin and tall front, small-front class, mixed level, forest, deep chain and fan-in
 of the catalogue is made to happen on purpose, and each is checked for its shape, inertia, D, L and its solutions (against the
 solution of the fp64 matrix refined in long double), for repeated solves and for a refactorisation on the same handle.
-The other routes (schedule switches read once per process) run the same designs in subprocesses (front_shapes_case.py)."""
+The other routes (schedule switches read once per process) run the same designs in subprocesses (front_shapes_case.py).
+Here the counted inertia always equals the request; pivot counting at a tolerance and the early exit of the delta loop on these
+designs are in test_gpu_inertia_designs.py."""
 import json
 import os
 import re
