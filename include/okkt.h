@@ -373,6 +373,64 @@ int okkt_get_multipliers_dev(okkt_handle h, double* d_g_out, int64_t* d_partner_
 /* the rejected columns of the last report (original indices) and their partners, descending g, ties by ascending original index;
  * returns their number (at most cap are written; either array may be NULL), < 0 on error */
 int64_t okkt_get_rejected_pivots(okkt_handle h, int64_t* idx_out, int64_t* partner_out, int64_t cap);
+/* ---- The factor as an operator: half solves, products with L, D, L^T, the growth factor -----------------
+ * FACTOR COORDINATES.  With the handle's permutation P (okkt_get_perm: index j of a vector in factor order is original index perm[j])
+ * and scaling S (section 8.8; the identity when the factor is not scaled) the library holds F~ = S P F P^T S = L D L^T, L unit lower
+ * triangular (okkt_get_factor_csc), D diagonal (okkt_get_diag), relaxation zeros of the supernodes included.  Vectors are nrhs columns
+ * of dim doubles stored one after another, as for okkt_solve; which coordinates a vector is in is said per call.
+ *
+ * Half solves.  okkt_solve_forward: z = D^-1 L^-1 P S b (factor order) -- the forward sweep of okkt_solve stopped where it ends.
+ * okkt_solve_backward: x = S P^T L^-T z (original order) -- the backward sweep started from the caller's z.  Both run right-hand
+ * sides in okkt_solve's groups of 4, 2 and 1 through okkt_solve's kernels, so okkt_solve_backward(okkt_solve_forward(b)) is okkt_solve(b)
+ * BIT FOR BIT.  rhs may alias z and z may alias sol.
+ * okkt_quadform: one forward sweep per group and one reduction: q_pos[r] = sum over d_j > 0 of d_j z_j^2, q_neg[r] = the same over
+ * d_j < 0 (so q_pos >= 0 >= q_neg and b^T F^-1 b = q_pos + q_neg); a pivot that is 0 or NaN contributes to neither.  The products
+ * d_j z_j z_j are formed error-free (fma) and summed in double-double by a fixed tree, then rounded once: each result is within
+ * 2^-52 (relative) of the exact sum over the z and D of the sweep, and two calls give the same bits.  q_pos / q_neg are host memory
+ * in both forms.
+ *
+ * Products.  okkt_factor_multiply, op:
+ *   OKKT_OP_L        y = L x                                            factor coordinates in and out, unit diagonal included, no scaling
+ *   OKKT_OP_LT       y = L^T x                                          the same
+ *   OKKT_OP_LDLT     y = S^-1 P^T  L   D   L^T  P S^-1  x               original coordinates: F x up to the factorisation's error
+ *   OKKT_OP_ABS_LDLT y = S^-1 P^T |L| |D| |L^T| P S^-1 |x|              original coordinates
+ * x may alias y.  Deterministic: no floating-point atomics, every sum in a fixed order; two calls give the same bits, and a column's
+ * result does not depend on the columns it shares a pass with.
+ *
+ * okkt_factor_error: the growth factor of the static-pivot factorisation and a sampled backward error of the factor against the
+ * values nzval (the matrix okkt_residual defines, plus the diagonal shift the factorisation added at assembly):
+ *   norm_abs_ldlt = || OKKT_OP_ABS_LDLT applied to the vector of ones ||_inf,  norm_f = ||F||_inf,  rho = norm_abs_ldlt / norm_f;
+ *   eta = max over the probes p < probes and the rows i of |(F v_p - LDLT v_p)_i| / ((|F| + ABS_LDLT) e)_i  (0 / 0 = 0; a non-finite
+ *         quotient counts as +Inf), eta_row the row that attains it (original index; the lowest on a tie, -1 when dim = 0);
+ *   LDLT v_p is the OKKT_OP_LDLT product, F v_p is accumulated in double-double (okkt_residual's pass) and the difference rounded once.
+ *   Probe p has entry i (original index) -1 when the top bit of mix64((p << 32) ^ i) is set and +1 otherwise, in 64-bit unsigned
+ *   arithmetic, mix64(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *   return z ^ (z >> 31)  (the finaliser of splitmix64).
+ * A factorisation that never pivots is backward stable exactly when rho is modest (Higham, Accuracy and Stability of Numerical
+ * Algorithms, section 11.1); g_j of okkt_pivot_report is a proxy for it.  Two calls give the same bits.
+ *
+ * Refused with OKKT_ERR_INVALID (the handle stays usable), as okkt_pivot_report: before a complete factorisation, after an early-exit
+ * factorisation that stopped short, on partitioned handles; moreover in Schur mode, for nrhs < 0, a NULL pointer, an unknown op,
+ * probes > 8.  host_symbolic_only handles get OKKT_ERR_NO_DEVICE.  The device memory (the work-item lists, two blocks of 4 x dim
+ * doubles, the partial sums of the big fronts) is allocated by the first product after an analysis and released with the analysis.
+ * No existing call changes: okkt_solve after any of these is bitwise what it was before. */
+int okkt_solve_forward(okkt_handle h, const double* rhs, double* z, int64_t nrhs);
+int okkt_solve_forward_dev(okkt_handle h, const double* d_rhs, double* d_z, int64_t nrhs);
+int okkt_solve_backward(okkt_handle h, const double* z, double* sol, int64_t nrhs);
+int okkt_solve_backward_dev(okkt_handle h, const double* d_z, double* d_sol, int64_t nrhs);
+int okkt_quadform(okkt_handle h, const double* rhs, int64_t nrhs, double* q_pos /* [nrhs] */, double* q_neg /* [nrhs] */);
+int okkt_quadform_dev(okkt_handle h, const double* d_rhs, int64_t nrhs, double* q_pos /* host */, double* q_neg /* host */);
+enum { OKKT_OP_L = 1, OKKT_OP_LT = 2, OKKT_OP_LDLT = 3, OKKT_OP_ABS_LDLT = 4 };
+int okkt_factor_multiply(okkt_handle h, int op, const double* x, double* y, int64_t nrhs);
+int okkt_factor_multiply_dev(okkt_handle h, int op, const double* d_x, double* d_y, int64_t nrhs);
+typedef struct {
+  double rho, norm_abs_ldlt, norm_f, eta;
+  int64_t eta_row;
+  int32_t probes;      /* probes used */
+} okkt_factor_error_info;
+int okkt_factor_error(okkt_handle h, const double* nzval, int32_t probes /* 1..8, <= 0: 2 */, okkt_factor_error_info* info);
+/* the same with nzval in device memory */
+int okkt_factor_error_dev(okkt_handle h, const double* d_nzval, int32_t probes, okkt_factor_error_info* info);
 /* Refinement through the Schur route: okkt_solve_refine's loop -- the same omega, stagnation rule, best
  * iterate, masked correction and one device-to-host read per step -- with every solve the fused whole-system solve of okkt_schur_solve.
  * nzval: the values of the whole A on the analysed pattern (residuals are against the whole matrix).  It needs a complete

@@ -25,6 +25,12 @@ OKKT_SCALE_RUIZ = 1
 OKKT_SCALE_USER = 2
 OKKT_SCALE = {"none": OKKT_SCALE_NONE, "ruiz": OKKT_SCALE_RUIZ, "user": OKKT_SCALE_USER}
 
+OKKT_OP_L = 1
+OKKT_OP_LT = 2
+OKKT_OP_LDLT = 3
+OKKT_OP_ABS_LDLT = 4
+OKKT_OP = {"L": OKKT_OP_L, "LT": OKKT_OP_LT, "LDLT": OKKT_OP_LDLT, "ABS_LDLT": OKKT_OP_ABS_LDLT}
+
 OKKT_OK = 0
 OKKT_ERR_INVALID = -1
 OKKT_ERR_NO_DEVICE = -2
@@ -209,6 +215,22 @@ class OkktPivotInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktFactorErrorInfo(C.Structure):
+    """okkt_factor_error_info: the growth factor rho = || |L||D||L^T| e ||_inf / ||F||_inf with its two norms, the sampled backward error
+    eta of the factor with the row that attains it (original index), and the probes used."""
+    _fields_ = [
+        ("rho", C.c_double),
+        ("norm_abs_ldlt", C.c_double),
+        ("norm_f", C.c_double),
+        ("eta", C.c_double),
+        ("eta_row", C.c_int64),
+        ("probes", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class OkktScalingInfo(C.Structure):
     """okkt_scaling_info: mode and sweeps of the current factor's scaling, the extrema of the row maxima of |S F S| over its non-zero
     rows, and the number of zero rows."""
@@ -303,6 +325,16 @@ SIGNATURES = {
     "okkt_get_multipliers": (C.c_int, [_vp, _f64p, _i64p]),
     "okkt_get_multipliers_dev": (C.c_int, [_vp, _vp, _vp]),
     "okkt_get_rejected_pivots": (C.c_int64, [_vp, _i64p, _i64p, C.c_int64]),
+    "okkt_solve_forward": (C.c_int, [_vp, _f64p, _f64p, C.c_int64]),
+    "okkt_solve_forward_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64]),
+    "okkt_solve_backward": (C.c_int, [_vp, _f64p, _f64p, C.c_int64]),
+    "okkt_solve_backward_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64]),
+    "okkt_quadform": (C.c_int, [_vp, _f64p, C.c_int64, _f64p, _f64p]),
+    "okkt_quadform_dev": (C.c_int, [_vp, _vp, C.c_int64, _f64p, _f64p]),
+    "okkt_factor_multiply": (C.c_int, [_vp, C.c_int, _f64p, _f64p, C.c_int64]),
+    "okkt_factor_multiply_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64]),
+    "okkt_factor_error": (C.c_int, [_vp, _f64p, C.c_int32, C.POINTER(OkktFactorErrorInfo)]),
+    "okkt_factor_error_dev": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OkktFactorErrorInfo)]),
     "okkt_schur_solve_refine": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
     "okkt_schur_solve_refine_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
     "okkt_schur_get_inverse": (C.c_int, [_vp, _f64p, C.c_int64]),

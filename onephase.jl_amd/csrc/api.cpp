@@ -3,7 +3,7 @@
 // (the reference's src/linear_system_solvers/julia.jl).  This file: errors, the device and numeric set-up, the handle with its pooled
 // stream sets, analysis, factor, solve, the getters, the okkt_dev_* helpers, the profile, the scaling, and what the files beside it
 // share (api_internal.h).  api_refine.cpp: residuals, refinement, GMRES-IR; api_condest.cpp: condition estimate and forward error;
-// api_schur.cpp: Schur mode, the dense Schur factor, its solves; api_selinv.cpp: selected inversion, log-determinant, pivot report.
+// api_schur.cpp: Schur mode, the dense Schur factor, its solves; api_selinv.cpp: selected inversion, log-determinant, pivot report; api_ops.cpp: half solves and products with the factor.
 // No exception leaves the layer (fence, api_internal.h).
 #include <mutex>
 #include <chrono>
@@ -226,6 +226,7 @@ void solver_refine_release(okkt_solver_s* h) {
   condest_release(h->cd);
   selinv_release(h->sl);
   pivots_release(h->pv);
+  factor_ops_release(h->fo);
   krylov_release(h->kr);
   dense_ldlt_release(h->dl);
   scaling_release(h->sc);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "asm_pieces.h"
+#include "factor_ops.h"
 #include "lanczos_tridiag.h"
 #include "numeric.h"
 #include "pivots.h"
@@ -224,6 +225,42 @@ static int run(const char* name, int n, const std::set<std::pair<int, int>>& e, 
     }
     ok = ok && entries == P.entries && P.ncols == ncov;
     if (!ok) { fprintf(stderr, "%s (ordering %d): the pivot-report items do not tile the factor (skip %d)\n", name, ordering, skip); return 1; }
+  }
+  // the work-item lists of the factor products (factor_ops.h): every column of L once on either side, the items of L^T x and of L x
+  // each tiling the entries below the diagonal, partial records inside their buffers, children on lower levels than their parents
+  {
+    std::vector<int64_t> gcb(S.nsuper, -1);
+    int64_t nbig = 0;
+    for (int s = 0; s < S.nsuper; ++s) {
+      const int64_t f = S.row_ptr[s + 1] - S.row_ptr[s];
+      if (f > 128) { gcb[s] = nbig; nbig += f; }
+    }
+    FoPlan P;
+    const std::string fe = factor_ops_build_plan(S, fpos, gcb, 128, P);
+    if (!fe.empty()) { fprintf(stderr, "%s (ordering %d): %s\n", name, ordering, fe.c_str()); return 1; }
+    bool ok = (int)P.small_off.size() == S.nlevels + 1 && P.small_off.back() == (int64_t)P.small.size() && P.l_big_off.back() == (int64_t)P.l_big.size() &&
+              P.l_merge_off.back() == (int64_t)P.l_merge.size();
+    std::vector<int> seen(n, 0);
+    int64_t e_small = 0, e_lt = 0, e_l = 0;
+    for (const FoSmall& q : P.small) {
+      ok = ok && q.f <= 128 && q.k <= q.f && q.s >= 0 && q.s < S.nsuper && q.L == fpos[q.s] && q.col0 == S.sn_col0[q.s];
+      for (int lc = 0; lc < q.k; ++lc) { ++seen[q.col0 + lc]; e_small += q.f - lc - 1; }
+    }
+    for (const FoLtMerge& q : P.lt_merge) { ++seen[q.out]; ok = ok && q.nch >= 1 && q.part >= 0 && q.part + q.nch <= P.lt_parts; }
+    for (const FoLtBig& q : P.lt_big) {
+      ok = ok && q.nc >= 1 && q.nc <= kFoLtCols && q.r0 <= q.r1 && q.r1 <= q.f && q.r1 - q.r0 <= kFoLtRows && q.r0 >= std::min(q.c0 + 1, q.f) &&
+           q.part >= 0 && q.part + (int64_t)(q.nc - 1) * q.nch < P.lt_parts;
+      for (int c = 0; c < q.nc; ++c) e_lt += std::max(0, q.r1 - std::max(q.r0, q.c0 + c + 1));
+    }
+    for (const FoLBig& q : P.l_big) {
+      ok = ok && q.nc >= 1 && q.nc <= kFoLCols && q.r0 < q.r1 && q.r1 <= q.f && q.r1 - q.r0 <= kFoLRows && q.part >= 0 && q.part + q.r1 <= P.l_parts;
+      for (int j = q.c0; j < q.c0 + q.nc; ++j) e_l += std::max(0, q.r1 - std::max(q.r0, j + 1));
+    }
+    for (const FoLMerge& q : P.l_merge) ok = ok && q.gcb >= 0 && q.gcb + q.f <= nbig && q.r0 < q.f && q.part + (int64_t)((q.k + kFoLCols - 1) / kFoLCols) * q.f <= P.l_parts;
+    for (int c = 0; c < n; ++c) ok = ok && seen[c] == 1;
+    for (int s = 0; s < S.nsuper; ++s) if (S.sn_parent[s] >= 0) ok = ok && S.sn_level[s] < S.sn_level[S.sn_parent[s]];
+    ok = ok && e_small + e_lt == P.entries && e_small + e_l == P.entries;
+    if (!ok) { fprintf(stderr, "%s (ordering %d): the factor-product items do not tile the factor\n", name, ordering); return 1; }
   }
   // the records of the staged assembly, with the library's chunks and with one small enough for several chunks on every pattern
   for (int chunk : {512, 1024, 48})

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "dd_arith.h"
 #include "refine.h"
 
 namespace okkt {
@@ -32,20 +33,7 @@ namespace {
     if (e__ != hipSuccess) return std::string(#expr) + ": " + hipGetErrorString(e__);      \
   } while (0)
 
-// Knuth's TwoSum: s + e == a + b exactly, for any order of magnitude of a and b
-__device__ __forceinline__ void two_sum(double a, double b, double& s, double& e) {
-  s = a + b;
-  const double bb = s - a;
-  e = (a - (s - bb)) + (b - bb);
-}
-// (h, l) += (p, q) in double-double
-__device__ __forceinline__ void dd_add(double& h, double& l, double p, double q) {
-  double s, e;
-  two_sum(h, p, s, e);
-  e = e + (l + q);
-  h = s + e;
-  l = e - (h - s);
-}
+// two_sum and dd_add: dd_arith.h
 // (h, l) += a * x (TwoProd), den += |a| |x|
 __device__ __forceinline__ void dd_madd(double& h, double& l, double& den, double a, double x) {
   const double p = a * x;

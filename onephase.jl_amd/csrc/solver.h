@@ -8,6 +8,7 @@
 #include "../../include/okkt.h"
 #include "condest.h"
 #include "dense_ldlt.h"
+#include "factor_ops.h"
 #include "krylov.h"
 #include "numeric.h"
 #include "pivots.h"
@@ -83,6 +84,9 @@ struct okkt_solver_s {
   // threshold pivot report (pivots.hip): the work-item lists, g and the partners, allocated by the first
   // okkt_pivot_report after an analysis and released with the refinement map; stale after the next factorisation (factor_seq)
   okkt::PivotWork pv;
+  // the factor as an operator (factor_ops.hip): the work-item lists of the products and their vectors, allocated
+  // by the first product after an analysis and released with the refinement map
+  okkt::FactorOpsWork fo;
 };
 
 namespace okkt {

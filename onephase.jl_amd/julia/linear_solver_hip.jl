@@ -276,6 +276,64 @@ function rejected_pivots(solver::linear_solver_HIP)
     return idx, partner
 end
 
+# The factor as an operator (DESIGN.md section 8.12).  Factor coordinates: the library holds S P F P' S = L D L'; entry j of a vector
+# in factor order is original index perm[j] (okkt_get_perm).  Not part of the reference interface.
+# z = D^-1 L^-1 P S b (factor order): ls_solve! stopped behind its forward sweep; my_rhs is a vector or a dim x nrhs matrix
+function ls_solve_forward(solver::linear_solver_HIP, my_rhs::Array{Float64})
+    z = similar(my_rhs)
+    rc = ccall((:okkt_solve_forward, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64), solver.handle, my_rhs, z, size(my_rhs, 2))
+    rc < 0 && okkt_error(solver, "okkt_solve_forward", rc)
+    return z
+end
+
+# x = S P' L^-T z (original order); ls_solve_backward(ls_solve_forward(b)) is ls_solve!'s x bit for bit
+function ls_solve_backward(solver::linear_solver_HIP, z::Array{Float64})
+    x = similar(z)
+    rc = ccall((:okkt_solve_backward, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64), solver.handle, z, x, size(z, 2))
+    rc < 0 && okkt_error(solver, "okkt_solve_backward", rc)
+    return x
+end
+
+# (q_pos, q_neg) per right-hand side from one forward sweep: the sums of d_j z_j^2 over the positive and the negative pivots;
+# b' F^-1 b = q_pos + q_neg
+function quadform(solver::linear_solver_HIP, my_rhs::Array{Float64})
+    nrhs = size(my_rhs, 2)
+    q_pos = zeros(nrhs)
+    q_neg = zeros(nrhs)
+    rc = ccall((:okkt_quadform, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}), solver.handle, my_rhs, nrhs, q_pos, q_neg)
+    rc < 0 && okkt_error(solver, "okkt_quadform", rc)
+    return q_pos, q_neg
+end
+
+const OKKT_OP_L = 1          # y = L x, factor coordinates, unit diagonal included, no scaling
+const OKKT_OP_LT = 2         # y = L' x, the same
+const OKKT_OP_LDLT = 3       # y = S^-1 P' L D L' P S^-1 x, original coordinates: F x up to the factorisation's error
+const OKKT_OP_ABS_LDLT = 4   # y = S^-1 P' |L| |D| |L'| P S^-1 |x|
+
+function factor_multiply(solver::linear_solver_HIP, op::Integer, x::Array{Float64})
+    y = similar(x)
+    rc = ccall((:okkt_factor_multiply, OKKT_LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Int64), solver.handle, op, x, y, size(x, 2))
+    rc < 0 && okkt_error(solver, "okkt_factor_multiply", rc)
+    return y
+end
+
+struct OkktFactorErrorInfo    # okkt_factor_error_info of include/okkt.h
+    rho::Float64             # norm_abs_ldlt / norm_f: the growth factor of the static-pivot factorisation
+    norm_abs_ldlt::Float64   # || |L||D||L'| e ||_inf (original coordinates)
+    norm_f::Float64          # ||F||_inf
+    eta::Float64             # max over the probes and rows of |(F v - L D L' v)_i| / ((|F| + |L||D||L'|) e)_i
+    eta_row::Int64           # 0-based original index of the row that attains it, -1 when dim = 0
+    probes::Int32
+end
+
+# the growth factor and the sampled backward error of the current factor against A.nzval (probes 1..8, <= 0: 2)
+function factor_error(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}; probes::Integer=2)
+    info = Ref(OkktFactorErrorInfo(0.0, 0.0, 0.0, 0.0, -1, 0))
+    rc = ccall((:okkt_factor_error, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ref{OkktFactorErrorInfo}), solver.handle, A.nzval, Int32(probes), info)
+    rc < 0 && okkt_error(solver, "okkt_factor_error", rc)
+    return info[]
+end
+
 # ls_solve_refine! through the Schur route: every solve is okkt_schur_solve's, the residuals are against the whole A.  Needs
 # okkt_factor_schur and okkt_schur_factor of the handle's own S.
 function schur_solve_refine!(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}, my_rhs::Array{Float64,1}, my_sol::Array{Float64,1};

@@ -630,6 +630,83 @@ class linear_solver_HIP(abstract_linear_system_solver):
         self._check(self._lib.okkt_get_rejected_pivots(self._h, L.p_i64(idx), L.p_i64(par), cnt), "okkt_get_rejected_pivots")
         return idx[:cnt], par[:cnt]
 
+    # -- the factor as an operator: half solves, products, the growth factor (not part of the reference interface)
+    def _half(self, fn, what, v):
+        self._need()
+        B, single = self._rhs_block(v, self._dim)
+        X = np.zeros_like(B)
+        self._check(fn(self._h, L.p_f64(B), L.p_f64(X), B.shape[0]), what)
+        return X[0] if single else X
+
+    def ls_solve_forward(self, rhs):
+        """okkt_solve_forward: z = D^-1 L^-1 P S b in factor order (index j is original index perm()[j]) -- okkt_solve stopped behind its
+        forward sweep.  rhs: a vector or one right-hand side per row.  On `linear_solver_HIP.of_kkt(kkt)` (here and below) the factor is
+        that of the matrix okkt_kkt_factor last factored."""
+        return self._half(self._lib.okkt_solve_forward, "okkt_solve_forward", rhs)
+
+    def ls_solve_backward(self, z):
+        """okkt_solve_backward: x = S P^T L^-T z in the original order; ls_solve_backward(ls_solve_forward(b)) is ls_solve(b) bit for bit."""
+        return self._half(self._lib.okkt_solve_backward, "okkt_solve_backward", z)
+
+    def ls_solve_forward_dev(self, d_rhs, d_z, nrhs=1):
+        self._need()
+        self._check(self._lib.okkt_solve_forward_dev(self._h, C.c_void_p(d_rhs), C.c_void_p(d_z), int(nrhs)), "okkt_solve_forward_dev")
+
+    def ls_solve_backward_dev(self, d_z, d_sol, nrhs=1):
+        self._need()
+        self._check(self._lib.okkt_solve_backward_dev(self._h, C.c_void_p(d_z), C.c_void_p(d_sol), int(nrhs)), "okkt_solve_backward_dev")
+
+    def quadform(self, rhs):
+        """okkt_quadform: (q_pos, q_neg) per right-hand side from one forward sweep: the sums of d_j z_j^2 over the positive and over the
+        negative pivots; b' F^-1 b = q_pos + q_neg."""
+        self._need()
+        B, single = self._rhs_block(rhs, self._dim)
+        qp = np.zeros(B.shape[0])
+        qn = np.zeros(B.shape[0])
+        self._check(self._lib.okkt_quadform(self._h, L.p_f64(B), B.shape[0], L.p_f64(qp), L.p_f64(qn)), "okkt_quadform")
+        return (qp[0], qn[0]) if single else (qp, qn)
+
+    def quadform_dev(self, d_rhs, nrhs=1):
+        """quadform with the right-hand sides resident in HBM; the results come back to the host."""
+        self._need()
+        qp = np.zeros(max(int(nrhs), 1))
+        qn = np.zeros(max(int(nrhs), 1))
+        self._check(self._lib.okkt_quadform_dev(self._h, C.c_void_p(d_rhs), int(nrhs), L.p_f64(qp), L.p_f64(qn)), "okkt_quadform_dev")
+        return qp[: int(nrhs)], qn[: int(nrhs)]
+
+    @staticmethod
+    def _op(op):
+        return L.OKKT_OP[op] if isinstance(op, str) else int(op)
+
+    def factor_multiply(self, op, x):
+        """okkt_factor_multiply: op "L" | "LT" (factor coordinates, unit diagonal included, no scaling) | "LDLT" | "ABS_LDLT" (original
+        coordinates: S^-1 P^T L D L^T P S^-1 x, and the same with absolute values throughout).  x: a vector or one per row."""
+        self._need()
+        B, single = self._rhs_block(x, self._dim)
+        Y = np.zeros_like(B)
+        self._check(self._lib.okkt_factor_multiply(self._h, self._op(op), L.p_f64(B), L.p_f64(Y), B.shape[0]), "okkt_factor_multiply")
+        return Y[0] if single else Y
+
+    def factor_multiply_dev(self, op, d_x, d_y, nrhs=1):
+        self._need()
+        self._check(self._lib.okkt_factor_multiply_dev(self._h, self._op(op), C.c_void_p(d_x), C.c_void_p(d_y), int(nrhs)),
+                    "okkt_factor_multiply_dev")
+
+    def factor_error(self, nzval_or_matrix, probes=2):
+        """okkt_factor_error: the growth factor rho = || |L||D||L^T| e ||_inf / ||F||_inf of the static-pivot factor and the sampled
+        backward error eta of the factor against these values.  Returns okkt_factor_error_info as a dict."""
+        self._need()
+        vals = self._values(nzval_or_matrix)
+        info = L.OkktFactorErrorInfo()
+        self._check(self._lib.okkt_factor_error(self._h, L.p_f64(vals), int(probes), C.byref(info)), "okkt_factor_error")
+        return info.as_dict()
+
+    def factor_error_dev(self, d_nzval, probes=2):
+        self._need()
+        info = L.OkktFactorErrorInfo()
+        self._check(self._lib.okkt_factor_error_dev(self._h, C.c_void_p(d_nzval), int(probes), C.byref(info)), "okkt_factor_error_dev")
+        return info.as_dict()
+
     def schur_solve_refine(self, nzval_or_matrix, rhs, max_steps=3, tol=0.0):
         """ls_solve_refine through the Schur route (okkt_schur_solve_refine): every solve is schur_solve's, the residuals are against
         the whole A.  Needs ls_factor_schur and schur_factor() of the handle's own S.  Returns (x, info) as ls_solve_refine."""
