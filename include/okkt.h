@@ -431,6 +431,52 @@ typedef struct {
 int okkt_factor_error(okkt_handle h, const double* nzval, int32_t probes /* 1..8, <= 0: 2 */, okkt_factor_error_info* info);
 /* the same with nzval in device memory */
 int okkt_factor_error_dev(okkt_handle h, const double* d_nzval, int32_t probes, okkt_factor_error_info* info);
+/* ---- Sparse right-hand sides: tree-pruned solves and entries of the inverse -----------------------------
+ * okkt_solve_sparse solves F x = b for nrhs sparse columns b and returns the entries x_idx of every x.  The forward sweep visits only
+ * the supernodes on the paths from the non-zeros of P b to the roots of the elimination forest, the backward sweep only the paths from
+ * the requested entries to the roots; small fronts run as the whole tasks okkt_solve runs them in.  The visited fronts go through
+ * okkt_solve's kernels in okkt_solve's order, so the result is, at the requested entries, what okkt_solve returns for the densified b:
+ * equal as numbers (a zero may differ in sign).  Columns are taken in okkt_solve's groups of 4, 2 and 1; a group runs on the union of
+ * its columns' sets; when a sweep's set is every supernode the ordinary sweep runs.  Deterministic: two calls give the same bytes.
+ *
+ * b: colptr[nrhs + 1] (colptr[0] >= 0, non-decreasing), rowidx and val of the entries colptr[q] .. colptr[q + 1] of column q, 0-based
+ * original numbering, any order inside a column; an empty column gives a zero column.  x_idx NULL: x_out is nrhs x dim (column q at
+ * x_out + q * dim) and nx is not read; else nrhs x nx, x_out[q * nx + t] = x_q[x_idx[t]] (duplicates allowed).  The index arrays are
+ * host memory in both forms (the sets are host work); the _dev form takes the values and the result in device memory.
+ * okkt_get_inverse_columns: (F^-1)[rows, cols], column-major nrows x ncols (rows NULL: all dim rows, nrows not read) -- okkt_solve_sparse
+ * with the unit columns e_cols[j].
+ * info (or NULL), all counts for the union of the call's columns: the supernodes in the two closures (reach), the supernodes the
+ * launches visit (run >= reach), the fringe (fronts that do not run forward but whose parent does: their contribution vectors are
+ * zeroed) and its entries, the bytes of the panels visited and of all panels, the groups, pruned (0: every group ran the ordinary
+ * sweeps), and the time on the device.
+ * okkt_sparse_reach: host only, also on host_symbolic_only handles, after okkt_analyze: the sets a call with non-zero rows b_rows (the
+ * union of its columns; duplicates allowed) and requested rows x_idx (NULL: all) would use.  active_out (or NULL): dim bytes in factor
+ * order (okkt_get_perm), bit 0 = the column's supernode runs in the forward sweep, bit 1 = in the backward sweep, bit 2 = it is fringe.
+ *
+ * Refused with OKKT_ERR_INVALID (the handle stays usable): a NULL pointer that is needed, nrhs < 0, nx < 0 (ncols, nrows, nb
+ * likewise), a decreasing colptr, an index out of range, a row twice in one column of b; before okkt_analyze;
+ * in Schur mode; on partitioned handles; before a complete factorisation and after an early exit that stopped short (not
+ * okkt_sparse_reach).  host_symbolic_only handles get OKKT_ERR_NO_DEVICE from all but okkt_sparse_reach.  nrhs = 0, and nx = 0 with
+ * x_idx given, succeed and do nothing.  No existing call changes: okkt_solve after any of these is bitwise what it was before. */
+typedef struct {
+  int64_t nsuper;
+  int64_t fwd_reach, bwd_reach;      /* supernodes in the closures (union over the call's columns) */
+  int64_t fwd_run, bwd_run;          /* supernodes the launches visit (>= reach: small fronts run as whole tasks) */
+  int64_t fringe, fringe_entries;    /* children zeroed; sum of f - k over them */
+  int64_t fwd_panel_bytes, bwd_panel_bytes, factor_panel_bytes;
+  int32_t batches, pruned;           /* pruned = 0: the ordinary sweeps ran */
+  double seconds_device;
+} okkt_sparse_info;
+int okkt_solve_sparse(okkt_handle h, int64_t nrhs, const int64_t* b_colptr, const int64_t* b_rowidx, const double* b_val,
+                      int64_t nx, const int64_t* x_idx, double* x_out, okkt_sparse_info* info /* or NULL */);
+int okkt_solve_sparse_dev(okkt_handle h, int64_t nrhs, const int64_t* b_colptr, const int64_t* b_rowidx, const double* d_b_val,
+                          int64_t nx, const int64_t* x_idx, double* d_x_out, okkt_sparse_info* info /* or NULL */);
+int okkt_get_inverse_columns(okkt_handle h, int64_t ncols, const int64_t* cols, int64_t nrows, const int64_t* rows, double* out,
+                             okkt_sparse_info* info /* or NULL */);
+int okkt_get_inverse_columns_dev(okkt_handle h, int64_t ncols, const int64_t* cols, int64_t nrows, const int64_t* rows, double* d_out,
+                                 okkt_sparse_info* info /* or NULL */);
+int okkt_sparse_reach(okkt_handle h, int64_t nb, const int64_t* b_rows, int64_t nx, const int64_t* x_idx, okkt_sparse_info* info,
+                      uint8_t* active_out /* or NULL */);
 /* Refinement through the Schur route: okkt_solve_refine's loop -- the same omega, stagnation rule, best
  * iterate, masked correction and one device-to-host read per step -- with every solve the fused whole-system solve of okkt_schur_solve.
  * nzval: the values of the whole A on the analysed pattern (residuals are against the whole matrix).  It needs a complete

@@ -231,6 +231,29 @@ class OkktFactorErrorInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktSparseInfo(C.Structure):
+    """okkt_sparse_info: the sets of a sparse solve (union over the call's columns) -- supernodes in the closures, supernodes the launches
+    visit, the fringe, the bytes of the panels visited, the groups, pruned (0: the ordinary sweeps ran), device seconds."""
+    _fields_ = [
+        ("nsuper", C.c_int64),
+        ("fwd_reach", C.c_int64),
+        ("bwd_reach", C.c_int64),
+        ("fwd_run", C.c_int64),
+        ("bwd_run", C.c_int64),
+        ("fringe", C.c_int64),
+        ("fringe_entries", C.c_int64),
+        ("fwd_panel_bytes", C.c_int64),
+        ("bwd_panel_bytes", C.c_int64),
+        ("factor_panel_bytes", C.c_int64),
+        ("batches", C.c_int32),
+        ("pruned", C.c_int32),
+        ("seconds_device", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class OkktScalingInfo(C.Structure):
     """okkt_scaling_info: mode and sweeps of the current factor's scaling, the extrema of the row maxima of |S F S| over its non-zero
     rows, and the number of zero rows."""
@@ -335,6 +358,11 @@ SIGNATURES = {
     "okkt_factor_multiply_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64]),
     "okkt_factor_error": (C.c_int, [_vp, _f64p, C.c_int32, C.POINTER(OkktFactorErrorInfo)]),
     "okkt_factor_error_dev": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OkktFactorErrorInfo)]),
+    "okkt_solve_sparse": (C.c_int, [_vp, C.c_int64, _i64p, _i64p, _f64p, C.c_int64, _i64p, _f64p, C.POINTER(OkktSparseInfo)]),
+    "okkt_solve_sparse_dev": (C.c_int, [_vp, C.c_int64, _i64p, _i64p, _vp, C.c_int64, _i64p, _vp, C.POINTER(OkktSparseInfo)]),
+    "okkt_get_inverse_columns": (C.c_int, [_vp, C.c_int64, _i64p, C.c_int64, _i64p, _f64p, C.POINTER(OkktSparseInfo)]),
+    "okkt_get_inverse_columns_dev": (C.c_int, [_vp, C.c_int64, _i64p, C.c_int64, _i64p, _vp, C.POINTER(OkktSparseInfo)]),
+    "okkt_sparse_reach": (C.c_int, [_vp, C.c_int64, _i64p, C.c_int64, _i64p, C.POINTER(OkktSparseInfo), C.POINTER(C.c_uint8)]),
     "okkt_schur_solve_refine": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
     "okkt_schur_solve_refine_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
     "okkt_schur_get_inverse": (C.c_int, [_vp, _f64p, C.c_int64]),

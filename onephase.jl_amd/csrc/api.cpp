@@ -3,7 +3,7 @@
 // (the reference's src/linear_system_solvers/julia.jl).  This file: errors, the device and numeric set-up, the handle with its pooled
 // stream sets, analysis, factor, solve, the getters, the okkt_dev_* helpers, the profile, the scaling, and what the files beside it
 // share (api_internal.h).  api_refine.cpp: residuals, refinement, GMRES-IR; api_condest.cpp: condition estimate and forward error;
-// api_schur.cpp: Schur mode, the dense Schur factor, its solves; api_selinv.cpp: selected inversion, log-determinant, pivot report; api_ops.cpp: half solves and products with the factor.
+// api_schur.cpp: Schur mode, the dense Schur factor, its solves; api_selinv.cpp: selected inversion, log-determinant, pivot report; api_ops.cpp: half solves and products with the factor; api_sparse.cpp: sparse right-hand sides.
 // No exception leaves the layer (fence, api_internal.h).
 #include <mutex>
 #include <chrono>
@@ -227,6 +227,7 @@ void solver_refine_release(okkt_solver_s* h) {
   selinv_release(h->sl);
   pivots_release(h->pv);
   factor_ops_release(h->fo);
+  sparse_release(h->sp);
   krylov_release(h->kr);
   dense_ldlt_release(h->dl);
   scaling_release(h->sc);
@@ -518,7 +519,7 @@ int okkt_analyze(okkt_handle h, int64_t dim, const int64_t* colptr, const int64_
     if (h->opts.ordering == 2 && (int64_t)h->user_perm.size() != dim)
       return solver_set_error(h, OKKT_ERR_INVALID, "ordering=user: okkt_set_perm must supply dim entries first");
     auto t0 = std::chrono::steady_clock::now();
-    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned || h->kr.V || h->dl.F || h->sc.ready || h->pv.planned)) {   // the refinement map (and Z) belong to the old pattern
+    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned || h->kr.V || h->dl.F || h->sc.ready || h->pv.planned || h->sp.copied)) {   // the refinement map (and Z) belong to the old pattern
       (void)hipSetDevice(h->device);
       (void)hipStreamSynchronize(h->stream);
       solver_refine_release(h);

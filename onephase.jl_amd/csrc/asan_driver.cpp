@@ -3,7 +3,7 @@
 // (multilevel dissection with its helper threads) and an arrow matrix -- and the work-item lists of the pivot report (pivots.h) on each
 // of them and on a front tall enough for several chunks per column, and the flat records of the staged big-front assembly
 // (asm_pieces.h) on each of them and under a front of three chunks, and the tridiagonal solver of the Lanczos estimate
-// (lanczos_tridiag.h).  No device code, no HIP call.  SURVEY.md section 5 (host-side
+// (lanczos_tridiag.h), and the sets of the sparse right-hand sides (solve_sparse_host.cpp).  No device code, no HIP call.  SURVEY.md section 5 (host-side
 // sanitizer build); GPU sanitizers are not available on this pool.
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +16,7 @@
 #include "lanczos_tridiag.h"
 #include "numeric.h"
 #include "pivots.h"
+#include "solve_sparse.h"
 #include "symbolic.h"
 
 using namespace okkt;
@@ -265,6 +266,37 @@ static int run(const char* name, int n, const std::set<std::pair<int, int>>& e, 
   // the records of the staged assembly, with the library's chunks and with one small enough for several chunks on every pattern
   for (int chunk : {512, 1024, 48})
     if (!check_asm_pieces(S, chunk)) { fprintf(stderr, "%s (ordering %d): the assembly pieces do not tile the extend-add items (chunk %d)\n", name, ordering, chunk); return 1; }
+  // the sets of the sparse right-hand sides (solve_sparse_host.cpp): what runs is closed under the parent relation and made of whole
+  // units, the fringe is exactly the children of running fronts that do not run, the counts add up; repeated batches on one set of marks
+  {
+    SparseWork W;
+    sparse_host_setup(S, o, W);
+    std::mt19937 rng(n + ordering);
+    for (int trial = 0; trial < 8; ++trial) {
+      std::vector<int> b(trial == 7 ? n : 1 + (int)(rng() % 5)), x(trial % 2 ? 1 + (int)(rng() % 5) : 0);
+      for (size_t t = 0; t < b.size(); ++t) b[t] = trial == 7 ? (int)t : (int)(rng() % n);
+      for (int& v : x) v = (int)(rng() % n);
+      SparseSets A;
+      sparse_reach(S, W, b.data(), (int64_t)b.size(), x.data(), (int64_t)x.size(), x.empty(), A);
+      std::vector<char> fr(S.nsuper, 0), br(S.nsuper, 0);
+      for (int s : A.fwd_fronts) fr[s] = 1;
+      for (int s = 0; s < S.nsuper; ++s) br[s] = A.bwd_full || W.brun[s] == W.epoch;
+      bool ok = (int64_t)A.fwd_fronts.size() == A.fwd_run && A.fwd_run >= A.fwd_reach && A.bwd_run >= A.bwd_reach && A.fwd_full == (A.fwd_run == S.nsuper);
+      for (int v : b) ok = ok && fr[S.col2sn[v]];
+      for (int v : x) ok = ok && br[S.col2sn[v]];
+      int64_t fringe = 0, fentries = 0, bonly = 0;
+      for (int s = 0; s < S.nsuper; ++s) {
+        const int p = S.sn_parent[s];
+        if (fr[s]) ok = ok && (p < 0 || fr[p]) && fr[W.U.unit_root[s]];
+        if (br[s]) ok = ok && (p < 0 || br[p]) && br[W.U.unit_root[s]];
+        if (!fr[s] && p >= 0 && fr[p]) { ++fringe; fentries += (S.row_ptr[s + 1] - S.row_ptr[s]) - (S.sn_col0[s + 1] - S.sn_col0[s]); }
+        if (br[s] && !fr[s]) ++bonly;
+      }
+      ok = ok && fringe == A.fringe && fentries == A.fringe_entries && fringe == (int64_t)A.fringe_fronts.size() && bonly == (int64_t)A.bwd_only_fronts.size();
+      if (trial == 7) ok = ok && A.fwd_full && A.fringe == 0;
+      if (!ok) { fprintf(stderr, "%s (ordering %d): the sets of a sparse solve are not closed or miscounted (trial %d)\n", name, ordering, trial); return 1; }
+    }
+  }
   printf("%-12s ordering %d: n %d nnz(L) %lld supernodes %zu, %zu dataflow tasks\n", name, ordering, n, (long long)S.nnzL, S.sn_col0.size() - 1, ntask);
   return 0;
 }

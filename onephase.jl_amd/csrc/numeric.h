@@ -242,6 +242,7 @@ struct Numeric {
   std::vector<double> prof_flops;        // algorithmic flops of each profiled launch
   std::vector<std::pair<int, int>> big_fk;  // (f, k) of sched entries (host copy, big fronts only need it)
   std::vector<int> sched_host;
+  std::vector<int> ssched_host;          // the device plan's ssched (solve_setup)
   std::vector<int> sn_f, sn_k;           // per supernode
   // Schur mode (Symbolic::nschur > 0): the Schur front (the last supernode; -1: off), its first big-column index (extend-add lists)
   // and a one-entry device list holding it

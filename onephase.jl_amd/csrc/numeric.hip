@@ -15,6 +15,7 @@
 // adds the children's contribution blocks in a fixed order -- no floating-point atomics.
 #include "numeric.h"
 #include "front_device.h"
+#include "solve_sparse.h"
 #include <map>
 
 #include <algorithm>
@@ -1211,86 +1212,12 @@ std::string numeric_setup(const Symbolic& S, const SymbolicOptions& opts, hipStr
   // task of its own and the rule is applied to the children.  Big fronts are units of their own.
   // (a partitioned plan: a task must not cross the cut -- only subtrees whose fronts all have the owner of their root become tasks;
   // round 3, until then partitioned plans ran one launch per level of fronts)
-  static const bool parted_tasks = !(getenv("OKKT_PARTED_TASKS") && atoi(getenv("OKKT_PARTED_TASKS")) == 0);
-  const bool use_tasks = (!parted || parted_tasks) && !(getenv("OKKT_TASKS") && atoi(getenv("OKKT_TASKS")) == 0);
-  // plans of the level-structure dissection (banded systems) are all small fronts and nothing but launch latency: finer tasks
-  // (12 front units, ratio 1.1) cut the hanging chain at the CUTEst size from 0.19 + 0.15 ms to 0.11 + 0.10 ms, N_h = 20 000 from
-  // 0.37 + 0.29 to 0.24 + 0.19 ms (round 3 sweep); the general plans keep the coarser round-2 setting
-  const bool level_nd = S.ordering_used == 4 && S.max_front <= N.small_max;   // the banded plans: all small fronts (a mesh-like system ordered by the level structure keeps the general setting)
-  const double task_abs = getenv("OKKT_TASK_ABS") ? atof(getenv("OKKT_TASK_ABS")) : (level_nd ? 12.0 : 48.0);
-  const double task_ratio = getenv("OKKT_TASK_RATIO") ? atof(getenv("OKKT_TASK_RATIO")) : (level_nd ? 1.1 : 1.5);
-  std::vector<int> task_lo(ns), unit_root(ns), ulevel(ns, 0);
-  auto fof = [&](int s2) { return (int)(S.row_ptr[s2 + 1] - S.row_ptr[s2]); };
-  // forbid[s]: front s is a unit of its own (neither the root nor a member of a multi-front task); see the second pass below
-  std::vector<char> forbid(ns, 0);
-  // Schur mode: the last supernode is the Schur front -- a unit of its own that no schedule holds (assembled by numeric_factor_enqueue
-  // behind the interior, never factored, left out of the solve sweeps)
-  N.schur_sn = S.nschur > 0 ? ns - 1 : -1;
-  if (N.schur_sn >= 0) forbid[N.schur_sn] = 1;
-  auto form_units = [&]() {
-    std::fill(ulevel.begin(), ulevel.end(), 0);
-    std::vector<char> allsmall(ns), assigned(ns, 0);
-    std::vector<int> first(ns);
-    std::vector<double> ctot(ns), cpath(ns), cmaxchild(ns, 0.0);
-    for (int s2 = 0; s2 < ns; ++s2) {
-      const int f = fof(s2), k = S.sn_col0[s2 + 1] - S.sn_col0[s2];
-      allsmall[s2] = f <= N.small_max && !forbid[s2];
-      first[s2] = s2;
-      ctot[s2] = 1.0 + (double)f * f * k / 8192.0;
-      cpath[s2] = ctot[s2];
-    }
-    for (int s2 = 0; s2 < ns; ++s2) {           // children before parents
-      cpath[s2] += cmaxchild[s2];
-      const int p2 = S.sn_parent[s2];
-      if (p2 < 0) continue;
-      if (!allsmall[s2] || (parted && S.sn_owner[s2] != S.sn_owner[p2])) allsmall[p2] = 0;      // "all small" also means "all of one part"
-      first[p2] = std::min(first[p2], first[s2]);
-      ctot[p2] += ctot[s2];
-      cmaxchild[p2] = std::max(cmaxchild[p2], cpath[s2]);
-    }
-    for (int s2 = ns - 1; s2 >= 0; --s2) {      // parents before children: the largest admissible subtrees win
-      if (assigned[s2]) continue;
-      task_lo[s2] = s2;
-      unit_root[s2] = s2;
-      assigned[s2] = 1;
-      if (!use_tasks || !allsmall[s2] || !(ctot[s2] <= task_abs || ctot[s2] <= task_ratio * cpath[s2])) continue;
-      task_lo[s2] = first[s2];
-      for (int t = first[s2]; t < s2; ++t) { assigned[t] = 1; unit_root[t] = s2; task_lo[t] = t; }
-    }
-    for (int s2 = 0; s2 < ns; ++s2) {           // level of a unit = height in the tree of units
-      const int p2 = S.sn_parent[s2];
-      if (p2 < 0 || unit_root[p2] == unit_root[s2]) continue;
-      ulevel[unit_root[p2]] = std::max(ulevel[unit_root[p2]], ulevel[unit_root[s2]] + 1);
-    }
-  };
-  form_units();
-  {
-    // Second pass (round 6).  A level WITHOUT big fronts whose tasks are nearly all one-wave tasks (fronts of at most 32 rows) but for
-    // a handful with a mid-size front ran that handful in launches of its own -- one 256-thread workgroup for 67 us of the
-    // factorisation's critical path and 21 + 19 us of every solve at the metric size (53 869 one-wave tasks and ONE task with a
-    // front of 65 .. 128 rows in level 0).  Those mid-size fronts become units of their own: they move up to the level above their
-    // children, where the rule in build() below lets them join the big fronts of that level; what is left of their subtrees is
-    // one-wave tasks like everything around it.
-    static const int lone_max = getenv("OKKT_FOLD_LONE") ? atoi(getenv("OKKT_FOLD_LONE")) : 3;
-    int nl = 0;
-    for (int s2 = 0; s2 < ns; ++s2) if (unit_root[s2] == s2) nl = std::max(nl, ulevel[s2] + 1);
-    std::vector<int> nbig(nl, 0), nmid(nl, 0), nwave(nl, 0);
-    auto unit_maxf = [&](int s2) { int f = 0; for (int t = task_lo[s2]; t <= s2; ++t) f = std::max(f, fof(t)); return f; };
-    for (int s2 = 0; s2 < ns; ++s2) {
-      if (unit_root[s2] != s2) continue;
-      const int f = unit_maxf(s2);
-      ++(f <= 32 ? nwave : (f <= N.small_max ? nmid : nbig))[ulevel[s2]];
-    }
-    bool any = false;
-    if (lone_max > 0 && use_tasks && !parted)
-      for (int s2 = 0; s2 < ns; ++s2) {
-        if (unit_root[s2] != s2) continue;
-        const int l = ulevel[s2];
-        if (nbig[l] != 0 || nmid[l] == 0 || nmid[l] > lone_max || nwave[l] < 64 || unit_maxf(s2) <= 32) continue;
-        for (int t = task_lo[s2]; t <= s2; ++t) if (fof(t) > 32) { forbid[t] = 1; any = true; }
-      }
-    if (any) form_units();
-  }
+  // (form_front_units, solve_sparse_host.cpp: the sparse solves activate the same units)
+  FrontUnits FU;
+  form_front_units(S, N.small_max, FU);
+  const std::vector<int>&task_lo = FU.task_lo, &unit_root = FU.unit_root, &ulevel = FU.ulevel;
+  const bool parted_tasks = FU.parted_tasks;
+  N.schur_sn = FU.schur_sn;
   int nulev = 0;
   for (int s2 = 0; s2 < ns; ++s2) if (unit_root[s2] == s2 && s2 != N.schur_sn) nulev = std::max(nulev, ulevel[s2] + 1);
   std::vector<std::vector<int>> units_at(nulev);

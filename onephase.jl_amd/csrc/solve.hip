@@ -15,6 +15,7 @@
 //   * panel reads are 16 bytes per lane (two rows), 8 - 16 loads in flight per lane.
 // Results are deterministic: every output entry is owned by one workgroup that sums in a fixed order.
 #include "numeric.h"
+#include "solve_sparse.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -1500,6 +1501,7 @@ std::string solve_setup(const Symbolic& S, Numeric& N) {
   build(N.levels_top, N.slevels_top);
   std::string e;
   if (!(e = up(N, ssched, &d.ssched)).empty()) return e;
+  N.ssched_host = ssched;
   if (!(e = up(N, xinv_pos, &d.xinv_pos)).empty()) return e;
   if (!(e = up(N, ypart_pos, &d.ypart_pos)).empty()) return e;
   if (!(e = up(N, ythin_pos, &d.ythin_pos)).empty()) return e;
@@ -1560,10 +1562,23 @@ std::string solve_invert_enqueue(Numeric& N, hipStream_t st, const SolveLevel& L
   return "";
 }
 
+// The schedule a sweep runs over: the level lists of the plan, or sublists of them that carry their levels' bounds (a pruned sweep,
+// solve_sparse.hip).  own: the levels are N.levels (their block inversions have per-level events); waits: launches whose workgroups
+// wait for one another inside the launch (the flow launch of the small fronts, the fused thin and wide forms) may be used
+struct SweepView {
+  const std::vector<LevelSchedule>& levels;
+  const std::vector<SolveLevel>& sl;
+  const int* sched;
+  const int* ssched;
+  bool own, waits;
+};
+
 template <int R>
-static std::string fwd_enqueue_r(Numeric& N, const std::vector<LevelSchedule>& levels, const std::vector<SolveLevel>& sl, hipStream_t st, int l_lo, int l_hi) {
+static std::string fwd_enqueue_r(Numeric& N, const SweepView& V, hipStream_t st, int l_lo, int l_hi) {
   DevPlan P = N.d;
-  const bool flow = &levels == &N.levels && N.flow_levels >= 2 && N.flow_flags && l_lo == 0 && l_hi >= N.flow_levels;
+  const std::vector<LevelSchedule>& levels = V.levels;
+  const std::vector<SolveLevel>& sl = V.sl;
+  const bool flow = V.own && V.waits && N.flow_levels >= 2 && N.flow_flags && l_lo == 0 && l_hi >= N.flow_levels;
   for (size_t l = (size_t)l_lo; l < std::min((size_t)l_hi, levels.size()); ++l) {
     const LevelSchedule& L = levels[l];
     if (flow && l == 0) {     // the small-front tasks of the levels [0, flow_levels) in one launch
@@ -1581,27 +1596,27 @@ static std::string fwd_enqueue_r(Numeric& N, const std::vector<LevelSchedule>& l
       const Segment& g = L.seg[c];
       if (!g.cnt) continue;
       const size_t lds = (size_t)R * g.maxf * sizeof(double);
-      if (c == 0) hipLaunchKernelGGL((k_fs_small<64, R>), dim3(g.cnt), dim3(64), lds, st, P, P.sched + g.off, g.maxf, (int*)nullptr, 0, 0);
-      else hipLaunchKernelGGL((k_fs_small<256, R>), dim3(g.cnt), dim3(256), lds, st, P, P.sched + g.off, g.maxf, (int*)nullptr, 0, 0);
+      if (c == 0) hipLaunchKernelGGL((k_fs_small<64, R>), dim3(g.cnt), dim3(64), lds, st, P, V.sched + g.off, g.maxf, (int*)nullptr, 0, 0);
+      else hipLaunchKernelGGL((k_fs_small<256, R>), dim3(g.cnt), dim3(256), lds, st, P, V.sched + g.off, g.maxf, (int*)nullptr, 0, 0);
     }
-    if (&levels == &N.levels && (size_t)l < N.inv_level_pending.size() && N.inv_level_pending[l]) {      // this level's block inverses (enqueued by the factorisation on the auxiliary stream)
+    if (V.own && (size_t)l < N.inv_level_pending.size() && N.inv_level_pending[l]) {      // this level's block inverses (enqueued by the factorisation on the auxiliary stream)
       OKKT_HIP_TRY(hipStreamWaitEvent(st, N.inv_level_events[l], 0));
       N.inv_level_pending[l] = 0;
     }
     const SolveLevel& S = sl[l];
-    if (S.thin_cnt && N.solve_fuse && N.solve_flags) {
+    if (S.thin_cnt && V.waits && N.solve_fuse && N.solve_flags) {
       // one launch: workgroup 0 of a front computes y and raises its flag, the others apply the panel rows behind it
-      hipLaunchKernelGGL(k_fwd_thin_fused<R>, dim3((S.thin_maxr + 127) / 128 + 1, S.thin_cnt), dim3(256), 0, st, P, P.ssched + S.thin_off, N.nb, N.solve_flags, N.solve_epoch);
+      hipLaunchKernelGGL(k_fwd_thin_fused<R>, dim3((S.thin_maxr + 127) / 128 + 1, S.thin_cnt), dim3(256), 0, st, P, V.ssched + S.thin_off, N.nb, N.solve_flags, N.solve_epoch);
     } else if (S.thin_cnt) {
-      hipLaunchKernelGGL(k_fwd_thin_y<R>, dim3(S.thin_cnt), dim3(256), 0, st, P, P.ssched + S.thin_off, N.nb);
-      if (S.thin_maxr > 0) hipLaunchKernelGGL(k_fwd_thin_upd<R>, dim3((S.thin_maxr + 127) / 128, S.thin_cnt), dim3(256), 0, st, P, P.ssched + S.thin_off);
+      hipLaunchKernelGGL(k_fwd_thin_y<R>, dim3(S.thin_cnt), dim3(256), 0, st, P, V.ssched + S.thin_off, N.nb);
+      if (S.thin_maxr > 0) hipLaunchKernelGGL(k_fwd_thin_upd<R>, dim3((S.thin_maxr + 127) / 128, S.thin_cnt), dim3(256), 0, st, P, V.ssched + S.thin_off);
     }
     if (S.wide_cnt) {
-      const int* list = P.ssched + S.wide_off;
+      const int* list = V.ssched + S.wide_off;
       const int nblk = (S.wide_maxk + kSB - 1) / kSB;
       const size_t lds = ((size_t)R * kSB + (size_t)8 * R * kUpdRows) * sizeof(double);
       bool flow_done = false;
-      if (N.solve_flow && N.solve_counters64 && P.sver && nblk <= kFlowBlocks) {
+      if (V.waits && N.solve_flow && N.solve_counters64 && P.sver && nblk <= kFlowBlocks) {
         SweepFlow T;
         T.nblk = nblk;
         int64_t tot = 0;
@@ -1622,7 +1637,7 @@ static std::string fwd_enqueue_r(Numeric& N, const std::vector<LevelSchedule>& l
         const int kbmax = std::min(kSB, S.wide_maxk - b * kSB);
         const int rem = std::max(S.wide_maxf - b * kSB, 0);        // upper bound on the rows below the start of block b (a narrower last block leaves more rows than maxf - (b + 1) kSB)
         const int ny = (kbmax + 63) / 64, nupd = std::max(1, (rem + kUpdRows - 1) / kUpdRows);
-        if (N.solve_fuse && N.solve_counters64 && ny * kCS * S.wide_cnt <= N.solve_fuse_wide_max) {
+        if (V.waits && N.solve_fuse && N.solve_counters64 && ny * kCS * S.wide_cnt <= N.solve_fuse_wide_max) {
           hipLaunchKernelGGL(k_fwd_wide_fused<R>, dim3(ny * kCS + nupd, S.wide_cnt), dim3(256), lds, st, P, list, b, ny, N.solve_counters64, ++N.solve_epoch64);
         } else {
           if (P.solve_mid && b == 0 && S.wide_mink <= P.solve_mid) hipLaunchKernelGGL(k_fwd_mid<R>, dim3(S.wide_cnt), dim3(kMidThreads), (size_t)R * (kSB + 16 * 64) * sizeof(double), st, P, list, N.nb);
@@ -1639,9 +1654,11 @@ static std::string fwd_enqueue_r(Numeric& N, const std::vector<LevelSchedule>& l
 }
 
 template <int R>
-static std::string bwd_enqueue_r(Numeric& N, const std::vector<LevelSchedule>& levels, const std::vector<SolveLevel>& sl, hipStream_t st, int l_lo, int l_hi) {
+static std::string bwd_enqueue_r(Numeric& N, const SweepView& V, hipStream_t st, int l_lo, int l_hi) {
   DevPlan P = N.d;
-  const bool flow = &levels == &N.levels && N.flow_levels >= 2 && N.flow_flags && l_lo == 0 && l_hi >= N.flow_levels;
+  const std::vector<LevelSchedule>& levels = V.levels;
+  const std::vector<SolveLevel>& sl = V.sl;
+  const bool flow = V.own && V.waits && N.flow_levels >= 2 && N.flow_flags && l_lo == 0 && l_hi >= N.flow_levels;
   for (int l = std::min(l_hi, (int)levels.size()) - 1; l >= l_lo; --l) {
     const LevelSchedule& L = levels[l];
     if (flow && l == N.flow_levels - 1) {     // the levels [0, flow_levels) in one launch, parents at the lower block indices
@@ -1654,14 +1671,14 @@ static std::string bwd_enqueue_r(Numeric& N, const std::vector<LevelSchedule>& l
     }
     const SolveLevel& S = sl[l];
     if (S.wide_cnt) {
-      const int* list = P.ssched + S.wide_off;
+      const int* list = V.ssched + S.wide_off;
       if (S.wide_maxf > 0) hipLaunchKernelGGL(k_bwd_pre<R>, dim3((S.wide_maxk + 3) / 4, S.wide_cnt), dim3(256), 0, st, P, list);
       const int nblk = (S.wide_maxk + kSB - 1) / kSB;
       const size_t lds = (size_t)R * kSB * sizeof(double);
       for (int b = nblk - 1; b >= 0; --b) {
         const int kbmax = std::min(kSB, S.wide_maxk - b * kSB);
         const int nx = (kbmax + 63) / 64, nupd = (b * kSB + 63) / 64 + 1;
-        if (N.solve_fuse && N.solve_counters64 && nx * kCS * S.wide_cnt <= N.solve_fuse_wide_max) {
+        if (V.waits && N.solve_fuse && N.solve_counters64 && nx * kCS * S.wide_cnt <= N.solve_fuse_wide_max) {
           hipLaunchKernelGGL(k_bwd_wide_fused<R>, dim3(nx * kCS + nupd, S.wide_cnt), dim3(256), lds, st, P, list, b, nx, N.solve_counters64, ++N.solve_epoch64);
         } else {
           if (P.solve_mid && b == 0 && S.wide_mink <= P.solve_mid) hipLaunchKernelGGL(k_bwd_mid<R>, dim3(S.wide_cnt), dim3(kMidThreads), (size_t)R * (kSB + 16 * 64) * sizeof(double), st, P, list, N.nb);
@@ -1672,10 +1689,10 @@ static std::string bwd_enqueue_r(Numeric& N, const std::vector<LevelSchedule>& l
         }
       }
     }
-    if (S.thin_cnt && N.solve_fuse && N.solve_counters) {
-      hipLaunchKernelGGL(k_bwd_thin_fused<R>, dim3((S.thin_maxk + 3) / 4 + 1, S.thin_cnt), dim3(256), 0, st, P, P.ssched + S.thin_off, N.nb, N.solve_counters);
+    if (S.thin_cnt && V.waits && N.solve_fuse && N.solve_counters) {
+      hipLaunchKernelGGL(k_bwd_thin_fused<R>, dim3((S.thin_maxk + 3) / 4 + 1, S.thin_cnt), dim3(256), 0, st, P, V.ssched + S.thin_off, N.nb, N.solve_counters);
     } else if (S.thin_cnt) {
-      const int* list = P.ssched + S.thin_off;
+      const int* list = V.ssched + S.thin_off;
       if (S.thin_maxr > 0) hipLaunchKernelGGL(k_bwd_pre<R>, dim3((S.thin_maxk + 3) / 4, S.thin_cnt), dim3(256), 0, st, P, list);
       hipLaunchKernelGGL(k_bwd_thin<R>, dim3(S.thin_cnt), dim3(256), 0, st, P, list, N.nb);
     }
@@ -1683,8 +1700,8 @@ static std::string bwd_enqueue_r(Numeric& N, const std::vector<LevelSchedule>& l
       const Segment& g = L.seg[c];
       if (!g.cnt) continue;
       const size_t lds = (size_t)R * g.maxf * sizeof(double);
-      if (c == 0) hipLaunchKernelGGL((k_bs_small<64, R>), dim3(g.cnt), dim3(64), lds, st, P, P.sched + g.off, g.maxf, (int*)nullptr, 0);
-      else hipLaunchKernelGGL((k_bs_small<256, R>), dim3(g.cnt), dim3(256), lds, st, P, P.sched + g.off, g.maxf, (int*)nullptr, 0);
+      if (c == 0) hipLaunchKernelGGL((k_bs_small<64, R>), dim3(g.cnt), dim3(64), lds, st, P, V.sched + g.off, g.maxf, (int*)nullptr, 0);
+      else hipLaunchKernelGGL((k_bs_small<256, R>), dim3(g.cnt), dim3(256), lds, st, P, V.sched + g.off, g.maxf, (int*)nullptr, 0);
     }
   }
   OKKT_HIP_TRY(hipGetLastError());
@@ -1692,16 +1709,15 @@ static std::string bwd_enqueue_r(Numeric& N, const std::vector<LevelSchedule>& l
 }
 
 
-static std::string sweep(Numeric& N, bool fwd, const std::vector<LevelSchedule>& levels, const std::vector<SolveLevel>& sl, hipStream_t st, int R,
-                         int l_lo = 0, int l_hi = 1 << 30) {
-  if (fwd) return R == 1 ? fwd_enqueue_r<1>(N, levels, sl, st, l_lo, l_hi) : (R == 2 ? fwd_enqueue_r<2>(N, levels, sl, st, l_lo, l_hi) : fwd_enqueue_r<4>(N, levels, sl, st, l_lo, l_hi));
-  return R == 1 ? bwd_enqueue_r<1>(N, levels, sl, st, l_lo, l_hi) : (R == 2 ? bwd_enqueue_r<2>(N, levels, sl, st, l_lo, l_hi) : bwd_enqueue_r<4>(N, levels, sl, st, l_lo, l_hi));
+static std::string sweep(Numeric& N, bool fwd, const SweepView& V, hipStream_t st, int R, int l_lo = 0, int l_hi = 1 << 30) {
+  if (fwd) return R == 1 ? fwd_enqueue_r<1>(N, V, st, l_lo, l_hi) : (R == 2 ? fwd_enqueue_r<2>(N, V, st, l_lo, l_hi) : fwd_enqueue_r<4>(N, V, st, l_lo, l_hi));
+  return R == 1 ? bwd_enqueue_r<1>(N, V, st, l_lo, l_hi) : (R == 2 ? bwd_enqueue_r<2>(N, V, st, l_lo, l_hi) : bwd_enqueue_r<4>(N, V, st, l_lo, l_hi));
 }
 
 // which = 0: the local subtrees (everything when the plan is not partitioned); which = 1: the top schedule of a partitioned plan
 static std::string sweep_which(Numeric& N, bool fwd, int which, int R) {
-  if (which != 0) return sweep(N, fwd, N.levels_top, N.slevels_top, N.stream, R);
-  return sweep(N, fwd, N.levels, N.slevels, N.stream, R);
+  if (which != 0) return sweep(N, fwd, SweepView{N.levels_top, N.slevels_top, N.d.sched, N.d.ssched, false, true}, N.stream, R);
+  return sweep(N, fwd, SweepView{N.levels, N.slevels, N.d.sched, N.d.ssched, true, true}, N.stream, R);
 }
 
 std::string solve_fwd_enqueue(Numeric& N, int which, int R) {
@@ -1711,6 +1727,17 @@ std::string solve_fwd_enqueue(Numeric& N, int which, int R) {
 }
 std::string solve_bwd_enqueue(Numeric& N, int which, int R) {
   return sweep_which(N, false, which, R);
+}
+
+// Sublists of N.levels (solve_sparse.h): the same bodies, the launches without in-launch waits.  The forward call honours the events
+// of the factorisation's block inversions as solve_fwd_enqueue does.
+std::string solve_fwd_enqueue_lists(Numeric& N, const SweepLists& L, int R) {
+  if (N.inv_wait) { OKKT_HIP_TRY(hipStreamWaitEvent(N.stream, N.inv_event, 0)); N.inv_wait = false; }
+  ++N.solve_epoch;
+  return sweep(N, true, SweepView{*L.levels, *L.slevels, L.sched, L.ssched, true, false}, N.stream, R);
+}
+std::string solve_bwd_enqueue_lists(Numeric& N, const SweepLists& L, int R) {
+  return sweep(N, false, SweepView{*L.levels, *L.slevels, L.sched, L.ssched, true, false}, N.stream, R);
 }
 
 std::string schur_gather_enqueue(Numeric& N, double* d_r2, int nr, int R) {

@@ -15,6 +15,7 @@
 #include "refine.h"
 #include "scaling.h"
 #include "selinv.h"
+#include "solve_sparse.h"
 #include "symbolic.h"
 
 struct okkt_solver_s {
@@ -87,6 +88,9 @@ struct okkt_solver_s {
   // the factor as an operator (factor_ops.hip): the work-item lists of the products and their vectors, allocated
   // by the first product after an analysis and released with the refinement map
   okkt::FactorOpsWork fo;
+  // sparse right-hand sides (solve_sparse_host.cpp / .hip): the units and marks of the reach (host, built by the first
+  // call after an analysis), the units' places in the schedules and the list buffers (device, released with the refinement map)
+  okkt::SparseWork sp;
 };
 
 namespace okkt {

@@ -334,6 +334,71 @@ function factor_error(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int6
     return info[]
 end
 
+# Sparse right-hand sides (DESIGN.md section 8.13): solves that visit only the supernodes between the non-zeros of b, the wanted rows
+# and the roots of the elimination forest.  Indices are 1-based here and converted.  Not part of the reference interface.
+struct OkktSparseInfo     # okkt_sparse_info of include/okkt.h
+    nsuper::Int64
+    fwd_reach::Int64             # supernodes in the closures (union over the call's columns)
+    bwd_reach::Int64
+    fwd_run::Int64               # supernodes the launches visit (>= reach: small fronts run as whole tasks)
+    bwd_run::Int64
+    fringe::Int64                # fronts whose contribution vectors are zeroed, and their entries
+    fringe_entries::Int64
+    fwd_panel_bytes::Int64
+    bwd_panel_bytes::Int64
+    factor_panel_bytes::Int64
+    batches::Int32
+    pruned::Int32                # 0: the ordinary sweeps ran
+    seconds_device::Float64
+end
+okkt_sparse_info_zero() = Ref(OkktSparseInfo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0))
+
+# X (length(rows) x nrhs; rows = nothing: dim x nrhs) with X[t, q] = x_q[rows[t]] for the columns of B, and the info: equal to
+# ls_solve! of the densified columns at those entries
+function ls_solve_sparse(solver::linear_solver_HIP, B::SparseMatrixCSC{Float64,Int64}; rows::Union{Nothing,Vector{Int64}}=nothing)
+    nrhs = size(B, 2)
+    colptr = B.colptr .- 1
+    rowidx = B.rowval .- 1
+    nx = rows === nothing ? size(B, 1) : length(rows)
+    xidx = rows === nothing ? Int64[] : rows .- 1
+    X = zeros(nx, nrhs)
+    info = okkt_sparse_info_zero()
+    rc = ccall((:okkt_solve_sparse, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64},
+                                                     Ref{OkktSparseInfo}),
+               solver.handle, nrhs, colptr, rowidx, B.nzval, nx, rows === nothing ? C_NULL : xidx, X, info)
+    rc < 0 && okkt_error(solver, "okkt_solve_sparse", rc)
+    return X, info[]
+end
+
+# (F^-1)[rows, cols] (rows = nothing: all), entries off the pattern of L included
+function inverse_columns(solver::linear_solver_HIP, cols::Vector{Int64}; rows::Union{Nothing,Vector{Int64}}=nothing, dim::Integer=0)
+    nr = rows === nothing ? Int64(dim) : length(rows)
+    rows === nothing && dim <= 0 && error("inverse_columns: give dim when rows = nothing")
+    c0 = cols .- 1
+    r0 = rows === nothing ? Int64[] : rows .- 1
+    Z = zeros(nr, length(cols))
+    info = okkt_sparse_info_zero()
+    rc = ccall((:okkt_get_inverse_columns, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Float64}, Ref{OkktSparseInfo}),
+               solver.handle, length(cols), c0, nr, rows === nothing ? C_NULL : r0, Z, info)
+    rc < 0 && okkt_error(solver, "okkt_get_inverse_columns", rc)
+    return Z
+end
+
+inverse_block(solver::linear_solver_HIP, idx::Vector{Int64}) = inverse_columns(solver, idx; rows=idx)
+
+# host only (also on host_symbolic_only handles after the analysis): the sets ls_solve_sparse would use.  Returns the info and dim bytes
+# in factor order: bit 0 = the column's supernode runs in the forward sweep, bit 1 = in the backward sweep, bit 2 = it is fringe
+function sparse_reach(solver::linear_solver_HIP, b_rows::Vector{Int64}, dim::Integer; x_rows::Union{Nothing,Vector{Int64}}=nothing)
+    b0 = b_rows .- 1
+    x0 = x_rows === nothing ? Int64[] : x_rows .- 1
+    active = zeros(UInt8, dim)
+    info = okkt_sparse_info_zero()
+    rc = ccall((:okkt_sparse_reach, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ref{OkktSparseInfo}, Ptr{UInt8}),
+               solver.handle, length(b0), b0, length(x0), x_rows === nothing ? C_NULL : x0, info, active)
+    rc < 0 && okkt_error(solver, "okkt_sparse_reach", rc)
+    return info[], active
+end
+
 # ls_solve_refine! through the Schur route: every solve is okkt_schur_solve's, the residuals are against the whole A.  Needs
 # okkt_factor_schur and okkt_schur_factor of the handle's own S.
 function schur_solve_refine!(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}, my_rhs::Array{Float64,1}, my_sol::Array{Float64,1};

@@ -707,6 +707,92 @@ class linear_solver_HIP(abstract_linear_system_solver):
         self._check(self._lib.okkt_factor_error_dev(self._h, C.c_void_p(d_nzval), int(probes), C.byref(info)), "okkt_factor_error_dev")
         return info.as_dict()
 
+    # -- sparse right-hand sides: tree-pruned solves and entries of the inverse (not part of the reference interface)
+    def _sparse_columns(self, B):
+        """(colptr, rowidx, val, nrhs) of a scipy.sparse matrix with one right-hand side per column, or of an (idx, val) pair (one column)."""
+        if isinstance(B, tuple):
+            idx, val = L.i64(np.atleast_1d(B[0])), L.f64(np.atleast_1d(B[1]))
+            if idx.shape != val.shape or idx.ndim != 1:
+                raise OkktError("ls_solve_sparse: (idx, val) must be two vectors of one length")
+            return np.array([0, len(idx)], dtype=np.int64), idx, val, 1
+        M = sp.csc_matrix(B)
+        if M.shape[0] != self._dim:
+            raise OkktError(f"ls_solve_sparse: B has {M.shape[0]} rows, the analysed dimension is {self._dim}")
+        M.sum_duplicates()
+        return L.i64(M.indptr), L.i64(M.indices), L.f64(M.data), M.shape[1]
+
+    @staticmethod
+    def _opt_i64(a):
+        return (None, None) if a is None else (lambda v: (v, L.p_i64(v)))(L.i64(np.atleast_1d(a)))
+
+    def ls_solve_sparse(self, B, rows=None):
+        """okkt_solve_sparse: F x = b for sparse right-hand sides, visiting only the supernodes between the non-zeros of b, the wanted
+        rows and the roots of the elimination forest.  B: scipy.sparse, one right-hand side per column, or an (idx, val) pair.  rows
+        (None: all): the entries of x that are wanted.  Returns (X, info): X[q, t] = x_q[rows[t]] (a vector for an (idx, val) pair),
+        equal to ls_solve of the densified b at those entries, and okkt_sparse_info as a dict.  On `linear_solver_HIP.of_kkt(kkt)`
+        (here and below) the factor is that of the matrix okkt_kkt_factor last factored."""
+        self._need()
+        colptr, rowidx, val, nrhs = self._sparse_columns(B)
+        xi, xp = self._opt_i64(rows)
+        nx = self._dim if xi is None else len(xi)
+        X = np.zeros((nrhs, nx))
+        info = L.OkktSparseInfo()
+        self._check(self._lib.okkt_solve_sparse(self._h, nrhs, L.p_i64(colptr), L.p_i64(rowidx) if len(rowidx) else None,
+                                                L.p_f64(val) if len(val) else None, nx, xp, L.p_f64(X) if X.size else None, C.byref(info)),
+                    "okkt_solve_sparse")
+        return (X[0] if isinstance(B, tuple) else X), info.as_dict()
+
+    def ls_solve_sparse_dev(self, colptr, rowidx, d_val, d_x_out, rows=None):
+        """ls_solve_sparse with the values and the result (nrhs x len(rows), or nrhs x dim) resident in HBM; the indices stay on the
+        host, where the sets are computed.  Returns okkt_sparse_info as a dict."""
+        self._need()
+        colptr, rowidx = L.i64(colptr), L.i64(rowidx)
+        xi, xp = self._opt_i64(rows)
+        info = L.OkktSparseInfo()
+        self._check(self._lib.okkt_solve_sparse_dev(self._h, len(colptr) - 1, L.p_i64(colptr), L.p_i64(rowidx) if len(rowidx) else None, C.c_void_p(d_val),
+                                                    0 if xi is None else len(xi), xp, C.c_void_p(d_x_out), C.byref(info)), "okkt_solve_sparse_dev")
+        return info.as_dict()
+
+    def inverse_columns(self, cols, rows=None, with_info=False):
+        """okkt_get_inverse_columns: (F^-1)[rows, cols] as a len(rows) x len(cols) array (rows None: all), from sparse solves with the
+        unit columns -- entries off the pattern of L included."""
+        self._need()
+        ci, cp = self._opt_i64(cols)
+        xi, xp = self._opt_i64(rows)
+        nr = self._dim if xi is None else len(xi)
+        out = np.zeros((len(ci), nr))
+        info = L.OkktSparseInfo()
+        self._check(self._lib.okkt_get_inverse_columns(self._h, len(ci), cp, nr, xp, L.p_f64(out) if out.size else None, C.byref(info)),
+                    "okkt_get_inverse_columns")
+        Z = np.ascontiguousarray(out.T)
+        return (Z, info.as_dict()) if with_info else Z
+
+    def inverse_columns_dev(self, cols, d_out, rows=None):
+        self._need()
+        ci, cp = self._opt_i64(cols)
+        xi, xp = self._opt_i64(rows)
+        info = L.OkktSparseInfo()
+        self._check(self._lib.okkt_get_inverse_columns_dev(self._h, len(ci), cp, 0 if xi is None else len(xi), xp, C.c_void_p(d_out), C.byref(info)),
+                    "okkt_get_inverse_columns_dev")
+        return info.as_dict()
+
+    def inverse_block(self, idx):
+        """(F^-1)[idx, idx]: inverse_columns(idx, idx)."""
+        return self.inverse_columns(idx, idx)
+
+    def sparse_reach(self, b_rows, x_rows=None):
+        """okkt_sparse_reach (host only; works on host_symbolic_only handles after analyze): the sets ls_solve_sparse would use for
+        non-zero rows b_rows and wanted rows x_rows.  Returns (info, active): okkt_sparse_info as a dict and dim bytes in factor order,
+        bit 0 = the column's supernode runs in the forward sweep, bit 1 = in the backward sweep, bit 2 = it is fringe."""
+        self._need()
+        bi, bp = self._opt_i64([] if b_rows is None else b_rows)
+        xi, xp = self._opt_i64(x_rows)
+        active = np.zeros(max(self._dim, 1), dtype=np.uint8)
+        info = L.OkktSparseInfo()
+        self._check(self._lib.okkt_sparse_reach(self._h, len(bi), bp if len(bi) else None, 0 if xi is None else len(xi), xp, C.byref(info),
+                                                active.ctypes.data_as(C.POINTER(C.c_uint8))), "okkt_sparse_reach")
+        return info.as_dict(), active[: self._dim]
+
     def schur_solve_refine(self, nzval_or_matrix, rhs, max_steps=3, tol=0.0):
         """ls_solve_refine through the Schur route (okkt_schur_solve_refine): every solve is schur_solve's, the residuals are against
         the whole A.  Needs ls_factor_schur and schur_factor() of the handle's own S.  Returns (x, info) as ls_solve_refine."""
