@@ -249,6 +249,63 @@ int okkt_forward_error(okkt_handle h, const double* nzval, const double* rhs, co
 /* the same with device pointers for nzval, rhs and x; ferr_out and berr_out are host memory */
 int okkt_forward_error_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, const double* d_x, int64_t nrhs,
                            double* ferr_out, double* berr_out);
+/* ---- Eigenpairs nearest zero: block shift-invert Krylov-Schur through the factor ----------------------
+ * F is the matrix the handle factored (the unscaled one, also under okkt_set_scaling).  nlead = 0 or dim: the standard problem
+ * F v = lambda v, operator Op = F^-1 of order n = dim.  0 < nlead < dim: the pencil F v = lambda B v, B = diag(I_nlead, 0) in the
+ * caller's index order, operator Op = E F^-1 E' of order n = nlead (pad with zeros, solve, keep the leading part): the eigenvalues of
+ * the Schur complement F11 - F12 F22^-1 F21.  The nev eigenvalues of smallest modulus are returned by ascending |lambda| (of two equal
+ * moduli the positive one first) with their vectors.
+ *   Method: a hashed start block of `block` columns (splitmix64 of (seed, column, row) mapped to (-1, 1)); per sweep one okkt_solve
+ * pass with `block` right-hand sides, the new block column of G = V' Op V formed in full, the dense symmetric eigen-solver on G on the
+ * host, the residual norms ||Op V s - theta V s||_2 / |theta| of the leading Ritz pairs on the device; the next block is Op(Q)
+ * orthogonalised against the whole basis (two classical Gram-Schmidt passes; a column that shrinks below 2^-33 of its norm is dropped,
+ * a block that vanishes is replaced by a fresh hashed one).  When fewer slots than the next block has columns remain in max_basis the
+ * basis is compressed to the leading min(m, nev + block) Ritz vectors; the next block is taken before the compression and never
+ * truncated.  Converged: the nev leading residuals are <= tol.
+ *   Returned vectors: v = F^-1 E' x scaled, x the Ritz vector (in standard mode that is Op V s, which the method holds anyway; in
+ * pencil mode one more solve pass over the nev vectors), full length dim, column j at vecs + j * dim.  The leading n entries have unit
+ * 2-norm and the entry of largest modulus among them (lowest index among ties) is positive.  With this v, lambda B v - F v =
+ * lambda E' (x - Op x / theta): a converged pair has ||lambda B v - F v||_2 <= tol |lambda| (1 + tol) plus the rounding of the solve.
+ *   resid: with nzval (the values of F on the analysed pattern, as for okkt_residual) the true residuals ||lambda B v - F v||_2 from
+ * the double-double residual pass, info->true_residuals = 1; with nzval = NULL the residuals of the Ritz pairs the iteration stopped on.
+ *   Deterministic: no atomics, sums in an order that depends on n alone; two calls give the same bits.
+ *   Eigenvalues of multiplicity above `block` are not guaranteed to be found with all their copies.
+ * Refused with OKKT_ERR_INVALID (the handle stays usable): nev outside 1..32 or above n; block outside 1..4; max_basis other than 0 or
+ * 2 nev + 3 block .. 128; max_restarts < 0; tol < 0 or NaN; nlead outside 0..dim; before a complete factorisation, after an early-exit
+ * factorisation that stopped short, on partitioned handles and in Schur mode.  OKKT_ERR_NO_DEVICE on host_symbolic_only handles (after
+ * the argument checks). */
+typedef struct {
+  int32_t nev;          /* 1..32, <= n */
+  int32_t block;        /* 1..4: right-hand sides per solve pass */
+  int32_t max_basis;    /* 2 nev + 3 block .. 128; 0: max(48, 2 nev + 3 block), at most 128 and at most max(n, 2 nev + 3 block) */
+  int32_t max_restarts; /* >= 0 */
+  double tol;           /* >= 0; 0: 2^-26 */
+  int64_t nlead;        /* 0 or dim: standard problem; else the pencil's leading block */
+  uint64_t seed;
+} okkt_eigs_opts;
+typedef struct {
+  int32_t status;          /* 0 converged; 1 restart limit (nconv leading pairs met tol, the outputs hold the current Ritz pairs); 2 the whole
+                              space was spanned (m = n); 3 an operator product was not finite (lambda and resid NaN, vecs untouched) */
+  int32_t nconv;           /* leading pairs whose residual met tol */
+  int32_t sweeps;          /* operator applications to a block */
+  int32_t solves;          /* right-hand sides solved: the block widths summed over the sweeps, plus nev in pencil mode */
+  int32_t restarts;
+  int32_t basis;           /* max_basis in effect */
+  int32_t fresh_blocks;    /* hashed blocks drawn after the first */
+  int32_t dropped_columns; /* columns the drop rule removed */
+  int32_t true_residuals;  /* 1: resid holds ||lambda B v - F v||_2; 0: the Ritz residuals */
+  int64_t bytes;           /* device workspace held by the handle for this feature */
+} okkt_eigs_info;
+int okkt_eigs(okkt_handle h, const okkt_eigs_opts* opts, const double* nzval /* or NULL */, double* lambda /* [nev] */,
+              double* vecs /* [dim x nev] or NULL */, double* resid /* [nev] */, okkt_eigs_info* info /* or NULL */);
+/* the same with nzval and vecs in device memory; lambda, resid and info are host memory */
+int okkt_eigs_dev(okkt_handle h, const okkt_eigs_opts* opts, const double* d_nzval, double* lambda, double* d_vecs, double* resid,
+                  okkt_eigs_info* info);
+/* Test hook, host only (no device, no handle): the dense symmetric eigen-solver of okkt_eigs (csrc/sym_eig.h, cyclic Jacobi) on the
+ * m x m row-major matrix a, 1 <= m <= 128, of which the upper triangle is read.  theta [m]: the eigenvalues by descending modulus;
+ * s [m x m] row-major: column j the unit eigenvector of theta[j].  Returns 0, 2 when the sweep limit was reached, OKKT_ERR_INVALID for
+ * m out of range, a NULL pointer or a non-finite entry (the outputs untouched). */
+int okkt_debug_sym_eig(int32_t m, const double* a, double* theta, double* s);
 /* ---- Schur mode: partial factorisation with a dense Schur complement ----------------------------------
  * A is the analysed symmetric matrix of order dim; the Schur set is idx[0..ns), distinct 0-based original indices, and orders the
  * rows and columns of S; A11 is A without the set (the interior), A22 the set's block.  The handle factors A11 and assembles
@@ -817,6 +874,14 @@ int okkt_kkt_set_ls_refine(okkt_kkt_handle k, int32_t max_steps, double tol);
  * (clever-symmetric kind); Q + delta I (Schur kinds); with schur_dense_rows on, the bordered A (order n + k): then cond1 is kappa_1 of A,
  * not of Q.  Refused (OKKT_ERR_INVALID) before a complete factorisation. */
 int okkt_kkt_condest(okkt_kkt_handle k, int32_t t, okkt_condest_info* info);
+/* okkt_eigs for the system okkt_kkt_factor last factored: the eigenvalues of smallest modulus of
+ * Q(delta) = H + J' Sigma J + delta I at the factored delta and the x-parts of their vectors (vecs_x: n x nev, or NULL).  nlead is set
+ * here (opts->nlead is ignored): the pencil with nlead = n where the factored matrix is larger than Q (the symmetric kind with m > 0,
+ * the Schur kinds with schur_dense_rows), else the standard problem.  resid holds the true residuals against the assembled values
+ * with delta on the H block.  Refused (OKKT_ERR_INVALID): before a complete factorisation, and the clever-symmetric kind, whose
+ * factored matrix is rescaled and reduced. */
+int okkt_kkt_eigs(okkt_kkt_handle k, const okkt_eigs_opts* opts, double* lambda /* [nev] */, double* vecs_x /* [n x nev] or NULL */,
+                  double* resid /* [nev] */, okkt_eigs_info* info /* or NULL */);
 /* OKKT_KKT_SYMMETRIC only: the forward error bound (okkt_forward_error) of the last okkt_kkt_compute_direction's solve, against the
  * factored K + delta.  Refused until such a direction exists for the current factorisation and rhs; the other kinds refuse it as they
  * refuse okkt_kkt_set_ls_refine. */

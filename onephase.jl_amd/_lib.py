@@ -289,6 +289,38 @@ class OkktKktEigInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktEigsOpts(C.Structure):
+    """okkt_eigs_opts: nev, block, max_basis (0: default), max_restarts, tol (0: 2^-26), nlead (0 or dim: standard problem), seed."""
+    _fields_ = [
+        ("nev", C.c_int32),
+        ("block", C.c_int32),
+        ("max_basis", C.c_int32),
+        ("max_restarts", C.c_int32),
+        ("tol", C.c_double),
+        ("nlead", C.c_int64),
+        ("seed", C.c_uint64),
+    ]
+
+
+class OkktEigsInfo(C.Structure):
+    """okkt_eigs_info: status (0 converged, 1 restart limit, 2 whole space spanned, 3 non-finite) and the counts of the iteration."""
+    _fields_ = [
+        ("status", C.c_int32),
+        ("nconv", C.c_int32),
+        ("sweeps", C.c_int32),
+        ("solves", C.c_int32),
+        ("restarts", C.c_int32),
+        ("basis", C.c_int32),
+        ("fresh_blocks", C.c_int32),
+        ("dropped_columns", C.c_int32),
+        ("true_residuals", C.c_int32),
+        ("bytes", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/okkt.h declares, with its signature
 _i64p = C.POINTER(C.c_int64)
 _f64p = C.POINTER(C.c_double)
@@ -440,6 +472,10 @@ SIGNATURES = {
     "okkt_kkt_set_ls_scaling": (C.c_int, [_vp, C.c_int, C.c_int32]),
     "okkt_kkt_condest": (C.c_int, [_vp, C.c_int32, C.POINTER(OkktCondestInfo)]),
     "okkt_kkt_direction_error_bound": (C.c_int, [_vp, _f64p]),
+    "okkt_eigs": (C.c_int, [_vp, C.POINTER(OkktEigsOpts), _f64p, _f64p, _f64p, _f64p, C.POINTER(OkktEigsInfo)]),
+    "okkt_eigs_dev": (C.c_int, [_vp, C.POINTER(OkktEigsOpts), _vp, _f64p, _vp, _f64p, C.POINTER(OkktEigsInfo)]),
+    "okkt_kkt_eigs": (C.c_int, [_vp, C.POINTER(OkktEigsOpts), _f64p, _f64p, _f64p, C.POINTER(OkktEigsInfo)]),
+    "okkt_debug_sym_eig": (C.c_int, [C.c_int32, _f64p, _f64p, _f64p]),
     "okkt_kkt_compute_indicies": (C.c_int, [_vp, _f64p, C.POINTER(C.c_int64)]),
     "okkt_kkt_get_indicies": (C.c_int, [_vp, _i64p, _i64p, _i64p, _f64p, _f64p, _f64p, _f64p]),
     "okkt_kkt_get_clever_vectors": (C.c_int, [_vp, _f64p, _f64p, _f64p, _f64p, _f64p]),

@@ -228,6 +228,7 @@ void solver_refine_release(okkt_solver_s* h) {
   pivots_release(h->pv);
   factor_ops_release(h->fo);
   sparse_release(h->sp);
+  eigs_release(h->eg);
   krylov_release(h->kr);
   dense_ldlt_release(h->dl);
   scaling_release(h->sc);

@@ -3,7 +3,8 @@
 // (multilevel dissection with its helper threads) and an arrow matrix -- and the work-item lists of the pivot report (pivots.h) on each
 // of them and on a front tall enough for several chunks per column, and the flat records of the staged big-front assembly
 // (asm_pieces.h) on each of them and under a front of three chunks, and the tridiagonal solver of the Lanczos estimate
-// (lanczos_tridiag.h), and the sets of the sparse right-hand sides (solve_sparse_host.cpp).  No device code, no HIP call.  SURVEY.md section 5 (host-side
+// (lanczos_tridiag.h), and the dense symmetric eigen-solver of okkt_eigs (sym_eig.h), and the sets of the sparse right-hand sides
+// (solve_sparse_host.cpp).  No device code, no HIP call.  SURVEY.md section 5 (host-side
 // sanitizer build); GPU sanitizers are not available on this pool.
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +18,7 @@
 #include "numeric.h"
 #include "pivots.h"
 #include "solve_sparse.h"
+#include "sym_eig.h"
 #include "symbolic.h"
 
 using namespace okkt;
@@ -68,6 +70,52 @@ static int check_tridiag() {
     if (tridiag_extreme(0, a, a, &t0, &t1, s) != 1 || tridiag_extreme(65, a, a, &t0, &t1, s) != 1) { fprintf(stderr, "tridiag: order 0 / 65 not refused\n"); ++bad; }
   }
   if (!bad) printf("tridiag      orders 1 .. 64, split, scaled and refused cases clean\n");
+  return bad;
+}
+
+// The dense symmetric eigen-solver of okkt_eigs (sym_eig.h) with outputs and work of exactly m and m x m entries: orders 1, 2, 127 and
+// 128 (its stack arrays are exactly 128 long), a leading dimension above m, graded, diagonal and zero matrices, and the refused orders 0
+// and 129.  Checks A S = S theta and the order of the output.
+static int check_sym_eig() {
+  int bad = 0;
+  std::mt19937_64 rng(11);
+  std::uniform_real_distribution<double> u(-1.0, 1.0);
+  auto one = [&](int m, int lda, const std::vector<double>& a, const char* name) {
+    std::vector<double> theta((size_t)m), s((size_t)m * m), work((size_t)m * m);
+    const int rc = sym_eig(m, a.data(), lda, theta.data(), s.data(), work.data());
+    if (rc != 0) { fprintf(stderr, "sym_eig %s m=%d: rc %d\n", name, m, rc); ++bad; return; }
+    double scale = 0.0, worst = 0.0;
+    for (int i = 0; i < m; ++i) for (int j = i; j < m; ++j) scale = std::max(scale, std::abs(a[(size_t)i * lda + j]));
+    if (scale == 0.0) scale = 1.0;
+    for (int j = 0; j < m; ++j)
+      for (int i = 0; i < m; ++i) {
+        double r = -(theta[j] / scale) * s[(size_t)i * m + j];
+        for (int k = 0; k < m; ++k) r += (a[(size_t)std::min(i, k) * lda + std::max(i, k)] / scale) * s[(size_t)k * m + j];
+        worst = std::max(worst, std::abs(r));
+      }
+    bool ordered = true;
+    for (int j = 0; j + 1 < m; ++j) ordered = ordered && std::abs(theta[j]) >= std::abs(theta[j + 1]);
+    if (!ordered || !(worst <= 1e-11)) { fprintf(stderr, "sym_eig %s m=%d: residual %g, ordered %d\n", name, m, worst, (int)ordered); ++bad; }
+  };
+  for (int m : {1, 2, 3, 17, 127, 128}) {
+    const int lda = m + (m % 3);
+    std::vector<double> a((size_t)m * lda, 0.0);
+    for (int i = 0; i < m; ++i) for (int j = i; j < m; ++j) a[(size_t)i * lda + j] = u(rng);
+    one(m, lda, a, "random");
+    for (int i = 0; i < m; ++i) for (int j = i; j < m; ++j) a[(size_t)i * lda + j] *= std::pow(10.0, -7.0 * (i + j) / (2.0 * m));
+    one(m, lda, a, "graded");
+    for (int i = 0; i < m; ++i) for (int j = i + 1; j < m; ++j) a[(size_t)i * lda + j] = 0.0;
+    one(m, lda, a, "diagonal");
+    std::fill(a.begin(), a.end(), 0.0);
+    one(m, lda, a, "zero");
+  }
+  {
+    std::vector<double> a(129 * 129, 1.0), t(129), s(129 * 129), w(129 * 129);
+    if (sym_eig(0, a.data(), 1, t.data(), s.data(), w.data()) != 1 || sym_eig(129, a.data(), 129, t.data(), s.data(), w.data()) != 1) {
+      fprintf(stderr, "sym_eig: order 0 / 129 not refused\n"); ++bad;
+    }
+  }
+  if (!bad) printf("sym_eig      orders 1 .. 128, graded, diagonal, zero and refused cases clean\n");
   return bad;
 }
 
@@ -361,6 +409,7 @@ int main() {
     bad += run("three-chunks", n, e, 1);
   }
   bad += check_tridiag();
+  bad += check_sym_eig();
   if (bad) { fprintf(stderr, "%d case(s) failed\n", bad); return 1; }
   printf("asan driver: all cases clean\n");
   return 0;

@@ -1910,6 +1910,39 @@ int okkt_kkt_direction_error_bound(okkt_kkt_handle k, double* ferr) {
   return rc < 0 ? kk_check_ls(k, rc, "direction error bound") : rc;
 }
 
+// the eigenpairs nearest zero of Q(delta) = H + J' Sigma J + delta I through the factor: the pencil with the
+// x-block leading where the factored matrix is larger than Q, the true residuals against the assembled values with delta on the H block
+int okkt_kkt_eigs(okkt_kkt_handle k, const okkt_eigs_opts* opts, double* lambda, double* vecs_x, double* resid, okkt_eigs_info* info) {
+  if (!k) return OKKT_ERR_INVALID;
+  if (!opts || !lambda || !resid) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_eigs: null pointer");
+  if (k->kind == OKKT_KKT_CLEVER_SYMMETRIC)
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_eigs: not for the clever-symmetric kind (its factored matrix is the merged and rescaled M, not K(delta))");
+  if (!k->factored || !k->ls->factored)
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_eigs: no complete factorisation (factor! first; a discarded trial of the delta loop does not count)");
+  hipStream_t st = kk_stream(k);
+  const int64_t n = k->n;
+  int rc;
+  if (!k->rf_vals) { if ((rc = kk_alloc(k, (size_t)std::max<int64_t>(k->nnzA, 1), &k->rf_vals))) return rc; }
+  if (k->nnzA) KK_TRY(k, hipMemcpyAsync(k->rf_vals, k->Avals, (size_t)k->nnzA * 8, hipMemcpyDeviceToDevice, st));
+  if (n) hipLaunchKernelGGL(k_shift_diag, grid1(n), dim3(256), 0, st, n, k->diagA, k->delta, k->rf_vals);
+  okkt_eigs_opts o = *opts;
+  o.nlead = k->dimA > n ? n : 0;
+  okkt_eigs_info I;
+  std::memset(&I, 0, sizeof(I));
+  try {
+    rc = solver_eigs_device(k->ls, &o, k->rf_vals, lambda, nullptr, resid, &I);
+  } catch (...) {   // the host vectors of the projected problem
+    return kk_fail(k, OKKT_ERR_ALLOC, "okkt_kkt_eigs: out of host memory");
+  }
+  if (rc < 0) return kk_check_ls(k, rc, "okkt_eigs");
+  if (info) *info = I;
+  if (vecs_x && n) {
+    if (I.status == 3) { for (int64_t i = 0; i < n * o.nev; ++i) vecs_x[i] = NAN; }
+    else KK_TRY(k, hipMemcpy2D(vecs_x, (size_t)n * 8, k->ls->eg.X, (size_t)k->dimA * 8, (size_t)n * 8, (size_t)o.nev, hipMemcpyDeviceToHost));
+  }
+  return rc;
+}
+
 int okkt_kkt_get_dense_rows(okkt_kkt_handle k, int64_t* count_out, int64_t* rows_out) {
   if (!k || !count_out) return OKKT_ERR_INVALID;
   if (!k->structured) return kk_fail(k, OKKT_ERR_INVALID, "structure not set");

@@ -8,6 +8,7 @@
 #include "../../include/okkt.h"
 #include "condest.h"
 #include "dense_ldlt.h"
+#include "eigs.h"
 #include "factor_ops.h"
 #include "krylov.h"
 #include "numeric.h"
@@ -91,6 +92,9 @@ struct okkt_solver_s {
   // sparse right-hand sides (solve_sparse_host.cpp / .hip): the units and marks of the reach (host, built by the first
   // call after an analysis), the units' places in the schedules and the list buffers (device, released with the refinement map)
   okkt::SparseWork sp;
+  // eigenpairs nearest zero (eigs.hip): the basis V, Op V and the block vectors of the Krylov-Schur method, allocated
+  // by the first okkt_eigs after an analysis (grown for a larger basis) and released with the refinement map
+  okkt::EigsWork eg;
 };
 
 namespace okkt {
@@ -129,4 +133,8 @@ int solver_gmres_device(okkt_solver_s* h, const double* d_nzval, const double* d
 int solver_condest_device(okkt_solver_s* h, const double* d_nzval, int32_t t, okkt_condest_info* info, bool schur_route = false);
 int solver_forward_error_device(okkt_solver_s* h, const double* d_nzval, const double* d_b, const double* d_x, int64_t nrhs, double* ferr_out,
                                 double* berr_out, bool schur_route = false);
+// the eigenpairs of the factored F nearest zero (api_eigs.cpp): okkt_eigs_dev behind its pointer checks.  The vectors
+// stay in h->eg.X (dim x nev) as well; d_vecs may be NULL
+int solver_eigs_device(okkt_solver_s* h, const okkt_eigs_opts* o, const double* d_nzval, double* lambda, double* d_vecs, double* resid,
+                       okkt_eigs_info* info);
 }  // namespace okkt

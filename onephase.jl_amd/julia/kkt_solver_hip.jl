@@ -101,6 +101,20 @@ function kkt_condest(k::HIP_KKT_solver; t::Integer=2)
                                                k.handle, Int32(t), info))
     return info[]
 end
+# okkt_kkt_eigs: (lambda, X, resid, info) -- the nev eigenvalues of smallest modulus of H + J' Sigma J + delta I at the delta of the last
+# factor!, the x-parts of their vectors in the columns of X (n x nev) and the true residuals (DESIGN.md section 8.14)
+function kkt_eigs(k::HIP_KKT_solver, nev::Integer, n::Integer; block::Integer=4, max_basis::Integer=0, max_restarts::Integer=20,
+                  tol::Float64=0.0, seed::Integer=1)
+    opts = Ref(OkktEigsOpts(Int32(nev), Int32(block), Int32(max_basis), Int32(max_restarts), tol, Int64(0), UInt64(seed)))
+    info = Ref(OkktEigsInfo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    lambda = zeros(max(nev, 1))
+    resid = zeros(max(nev, 1))
+    X = zeros(max(n, 1), max(nev, 1))
+    kkt_hip_check(k, "okkt_kkt_eigs", ccall((:okkt_kkt_eigs, OKKT_LIB), Cint,
+                                            (Ptr{Cvoid}, Ref{OkktEigsOpts}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{OkktEigsInfo}),
+                                            k.handle, opts, lambda, X, resid, info))
+    return lambda[1:nev], X[1:n, 1:nev], resid[1:nev], info[]
+end
 # okkt_kkt_direction_error_bound (symmetric kind): the forward error bound of the last direction's solve against K + delta
 function direction_error_bound(k::HIP_KKT_solver)
     ferr = Ref(0.0)

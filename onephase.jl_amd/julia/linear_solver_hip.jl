@@ -211,6 +211,45 @@ function ls_forward_error(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,
     return ferr[1], berr[1]
 end
 
+struct OkktEigsOpts       # okkt_eigs_opts of include/okkt.h
+    nev::Int32
+    block::Int32
+    max_basis::Int32     # 0: the default
+    max_restarts::Int32
+    tol::Float64         # 0: 2^-26
+    nlead::Int64         # 0 or dim: the standard problem; else the leading block of the pencil (a count, not an index)
+    seed::UInt64
+end
+
+struct OkktEigsInfo       # okkt_eigs_info of include/okkt.h
+    status::Int32        # 0 converged, 1 restart limit, 2 the whole space was spanned, 3 non-finite
+    nconv::Int32
+    sweeps::Int32
+    solves::Int32
+    restarts::Int32
+    basis::Int32
+    fresh_blocks::Int32
+    dropped_columns::Int32
+    true_residuals::Int32
+    bytes::Int64
+end
+
+# The nev eigenvalues of smallest modulus of the factored F (or of the pencil F v = lambda B v, B = diag(I_nlead, 0)) by block shift-invert
+# Krylov-Schur through the factor: (lambda, V, resid, info), the vectors in the columns of V.  With A the residuals are the true
+# ||lambda B v - F v||_2 against A.nzval.  Not part of the reference interface (DESIGN.md section 8.14).
+function ls_eigs(solver::linear_solver_HIP, nev::Integer, A::Union{SparseMatrixCSC{Float64,Int64},Nothing}=nothing; block::Integer=4,
+                 max_basis::Integer=0, max_restarts::Integer=20, tol::Float64=0.0, nlead::Integer=0, seed::Integer=1, dim::Integer=(A === nothing ? 0 : size(A, 1)))
+    opts = Ref(OkktEigsOpts(Int32(nev), Int32(block), Int32(max_basis), Int32(max_restarts), tol, Int64(nlead), UInt64(seed)))
+    info = Ref(OkktEigsInfo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    lambda = zeros(max(nev, 1))
+    resid = zeros(max(nev, 1))
+    V = zeros(max(dim, 1), max(nev, 1))
+    rc = ccall((:okkt_eigs, OKKT_LIB), Cint, (Ptr{Cvoid}, Ref{OkktEigsOpts}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{OkktEigsInfo}),
+               solver.handle, opts, A === nothing ? C_NULL : A.nzval, lambda, dim > 0 ? V : C_NULL, resid, info)
+    rc < 0 && okkt_error(solver, "okkt_eigs", rc)
+    return lambda[1:nev], V[1:dim, 1:nev], resid[1:nev], info[]
+end
+
 struct OkktScalingInfo    # okkt_scaling_info of include/okkt.h
     mode::Int32          # 0 none, 1 Ruiz sweeps rounded to powers of two, 2 the caller's vector
     sweeps::Int32

@@ -562,6 +562,25 @@ class HIP_KKT_solver:
         self._check(self._lib.okkt_kkt_condest(self._k, int(t), C.byref(info)), "okkt_kkt_condest")
         return info.as_dict()
 
+    def eigs(self, nev, block=4, max_basis=0, max_restarts=20, tol=0.0, seed=1, vectors=True):
+        """okkt_kkt_eigs: (lam, V, resid, info) -- the nev eigenvalues of smallest modulus of Q(delta) = H + J' Sigma J + delta I at the
+        delta of the last factor_b, by ascending |lambda|, the x-parts of their vectors (one per row; None with vectors=False), the true
+        residuals against the factored system and okkt_eigs_info as a dict.  Refused for the clever-symmetric kind."""
+        if self._k is None:
+            raise OkktError("initialize_b has not been called")
+        o = L.OkktEigsOpts()
+        o.nev, o.block, o.max_basis, o.max_restarts = int(nev), int(block), int(max_basis), int(max_restarts)
+        o.tol, o.nlead, o.seed = float(tol), 0, int(seed)
+        n = self._pattern[0] if self._pattern is not None else 0
+        cnt = max(int(nev), 1)
+        lam = np.zeros(cnt)
+        res = np.zeros(cnt)
+        V = np.zeros((cnt, max(n, 1))) if vectors else None
+        info = L.OkktEigsInfo()
+        self._check(self._lib.okkt_kkt_eigs(self._k, C.byref(o), L.p_f64(lam), None if V is None else L.p_f64(V), L.p_f64(res),
+                                            C.byref(info)), "okkt_kkt_eigs")
+        return lam[: int(nev)], (None if V is None else V[: int(nev), :n]), res[: int(nev)], info.as_dict()
+
     def direction_error_bound(self):
         """okkt_kkt_direction_error_bound: the forward error bound of the symmetric kind's last direction solve against K + delta."""
         f = C.c_double()

@@ -374,6 +374,44 @@ class linear_solver_HIP(abstract_linear_system_solver):
                     "okkt_forward_error")
         return (ferr[0], berr[0]) if single else (ferr, berr)
 
+    # -- eigenpairs nearest zero through the factor (not part of the reference interface)
+    @staticmethod
+    def _eigs_opts(nev, block, max_basis, max_restarts, tol, nlead, seed):
+        o = L.OkktEigsOpts()
+        o.nev, o.block, o.max_basis, o.max_restarts = int(nev), int(block), int(max_basis), int(max_restarts)
+        o.tol, o.nlead, o.seed = float(tol), int(nlead), int(seed)
+        return o
+
+    def eigs(self, nev, nzval_or_matrix=None, block=4, max_basis=0, max_restarts=20, tol=0.0, nlead=0, seed=1, vectors=True):
+        """okkt_eigs: the nev eigenvalues of smallest modulus of the factored F (nlead = 0 or dim), or of the pencil F v = lambda B v
+        with B = diag(I_nlead, 0), by block shift-invert Krylov-Schur through the factor.  Returns (lam, V, resid, info): lam by
+        ascending |lambda|, V with one full-length vector per row (None with vectors=False), resid the true residuals
+        ||lambda B v - F v||_2 when the values (or the matrix) are given, else the Ritz residuals, info = okkt_eigs_info as a dict.  On
+        `linear_solver_HIP.of_kkt(kkt)` F is the matrix okkt_kkt_factor last factored."""
+        self._need()
+        o = self._eigs_opts(nev, block, max_basis, max_restarts, tol, nlead, seed)
+        vals = None if nzval_or_matrix is None else self._values(nzval_or_matrix)
+        cnt = max(int(nev), 1)
+        lam = np.zeros(cnt)
+        res = np.zeros(cnt)
+        V = np.zeros((cnt, max(self._dim, 1))) if vectors else None
+        info = L.OkktEigsInfo()
+        self._check(self._lib.okkt_eigs(self._h, C.byref(o), None if vals is None else L.p_f64(vals), L.p_f64(lam),
+                                        None if V is None else L.p_f64(V), L.p_f64(res), C.byref(info)), "okkt_eigs")
+        return lam[: int(nev)], (None if V is None else V[: int(nev), : self._dim]), res[: int(nev)], info.as_dict()
+
+    def eigs_dev(self, nev, d_nzval=None, d_vecs=None, block=4, max_basis=0, max_restarts=20, tol=0.0, nlead=0, seed=1):
+        """eigs with the values and the vectors (dim x nev, or None) in HBM (device pointers); returns (lam, resid, info)."""
+        self._need()
+        o = self._eigs_opts(nev, block, max_basis, max_restarts, tol, nlead, seed)
+        cnt = max(int(nev), 1)
+        lam = np.zeros(cnt)
+        res = np.zeros(cnt)
+        info = L.OkktEigsInfo()
+        self._check(self._lib.okkt_eigs_dev(self._h, C.byref(o), None if d_nzval is None else C.c_void_p(d_nzval), L.p_f64(lam),
+                                            None if d_vecs is None else C.c_void_p(d_vecs), L.p_f64(res), C.byref(info)), "okkt_eigs_dev")
+        return lam[: int(nev)], res[: int(nev)], info.as_dict()
+
     # -- symmetric equilibration before the factorisation (not part of the reference interface; DESIGN.md section 8.8)
     def set_scaling(self, mode, sweeps=0, s=None):
         """okkt_set_scaling: mode "none" | "ruiz" | "user" (or OKKT_SCALE_*).  "ruiz": every factorisation computes s by `sweeps`
