@@ -680,6 +680,69 @@ int64_t okkt_debug_dataflow_queue(int32_t nfronts, const int32_t* f, const int32
  * bytes, 7 the per-step kernels' leading dimension.  Returns the value, or a negative error code.  tests/test_dataflow_fragments.py. */
 int64_t okkt_debug_dataflow_fragment(int32_t map, int32_t what, int32_t wave, int32_t lane, int32_t kk, int32_t idx);
 
+/* ---- Uniform batches: B systems on the analysed pattern of one handle ---------------------------------
+ * A batch shares everything the analysis made -- the ordering, the front lists, the schedule, all index arrays on the device -- and
+ * gives every item a slot of its own in HBM: a front arena, D, the diagonal shift, a line of pivot counters and the vectors of the
+ * solve sweeps.  Every item is a complete factorisation: its own values, its own shift, its own inertia and flag, no early exit; one
+ * item's zero or non-finite pivots are counted in that item alone.  Supported for plans whose fronts are ALL small fronts (order <=
+ * small_front_max, at most 136): those fronts are factored by one workgroup each with the front in LDS, so a batch is the same
+ * per-front device code on a grid with one more coordinate.  Item b's factor is bit for bit what okkt_factor of the same values (and
+ * shift) leaves on a fresh handle, and its solution with nrhs columns bit for bit okkt_solve's with the same nrhs.
+ * Two launch shapes.  Level mode: one launch per level of the task tree, grid = tasks of the level x B; the launch count does not
+ * depend on B.  Item mode: one workgroup per item walks all tasks of the plan in schedule order -- one launch per factorisation and
+ * one per group of up to four right-hand sides.  No workgroup of either mode waits for another inside a launch.  OKKT_BATCH_AUTO
+ * is level mode (no measured batch size at which item mode pays); okkt_batch_set_mode forces a mode on the
+ * handle, and where it has not, the environment variable OKKT_BATCH_MODE (1 = level, 2 = item; read by okkt_batch_reserve) does.
+ * okkt_batch_query: host only, also on host_symbolic_only handles.  eligible = 0 comes with the first reason that applies, in the
+ * order of the codes below.  bytes_per_item: HBM of one slot with solve work for nrhs_max columns (the sweeps carry up to four at a
+ * time); before the device plan exists the arena is counted as dense f x f buffers (okkt_stats.arena_bytes), an upper bound.
+ * levels / tasks_per_item: levels and workgroup tasks of the task tree.  launches_*: kernel launches of one okkt_factor_batch, and of
+ * one okkt_solve_batch per group of up to four right-hand sides, in each mode.
+ * okkt_batch_reserve allocates B slots (index arrays are never duplicated) and replaces a previous reservation; OKKT_ERR_ALLOC with
+ * a message when B x bytes_per_item does not fit, OKKT_ERR_INVALID with the reason when the plan is not eligible, for B outside
+ * 1..65535 or nrhs_max < 1; OKKT_ERR_NO_DEVICE on host_symbolic_only handles.  A re-analysis releases the slots, and so does
+ * okkt_dist_set_partition; a reservation whose device plan has been rebuilt on another footing since (a partition, a Schur set) is
+ * released by the next batch call, which returns OKKT_ERR_INVALID.
+ * okkt_factor_batch(_dev): item b reads nzval + b * val_stride (val_stride = 0: every item the same array; else >= nnz).  shift: host
+ * array of B entries or NULL; shift[b] is added to the first nshift diagonal entries in the original numbering, as okkt_kkt_factor's
+ * delta is.  inertia_out[b] / flag_out[b] (host, either may be NULL): what okkt_factor would have reported and returned (1 / 0) for
+ * that item.  Returns OKKT_OK or a negative status.  The handle's own factor is not touched.
+ * okkt_solve_batch(_dev): rhs and sol are [B][nrhs][dim]; nrhs <= the reserved nrhs_max; rhs may alias sol.  Needs a batch factored
+ * with the same B or a larger one.
+ * okkt_batch_select(b): slot b -> the handle's own numeric state (L panels, D, the shift, the inertia, the factored flag); afterwards
+ * every entry point behaves as after okkt_factor of that item's values and shift. */
+#define OKKT_BATCH_OK 0
+#define OKKT_BATCH_NOT_ANALYZED 1
+#define OKKT_BATCH_PARTITIONED 2
+#define OKKT_BATCH_SCHUR 3
+#define OKKT_BATCH_SCALING 4
+#define OKKT_BATCH_BIG_FRONTS 5
+#define OKKT_BATCH_AUTO 0
+#define OKKT_BATCH_LEVEL 1
+#define OKKT_BATCH_ITEM 2
+typedef struct {
+  int32_t eligible, reason;
+  int64_t bytes_per_item;
+  int64_t tasks_per_item;
+  int32_t levels, max_front;
+  int32_t launches_factor_level, launches_solve_level;
+  int32_t launches_factor_item, launches_solve_item;
+} okkt_batch_info;
+int okkt_batch_query(okkt_handle h, int64_t nrhs_max, okkt_batch_info* out);
+int okkt_batch_reserve(okkt_handle h, int64_t B, int64_t nrhs_max);
+int okkt_batch_release(okkt_handle h);
+int okkt_batch_set_mode(okkt_handle h, int mode /* OKKT_BATCH_AUTO / _LEVEL / _ITEM */);
+int okkt_batch_mode_used(okkt_handle h);      /* the mode of the last okkt_factor_batch (0 before the first) */
+int okkt_factor_batch(okkt_handle h, int64_t B, const double* nzval, int64_t val_stride, const double* shift /* [B] or NULL */,
+                      int64_t nshift, int64_t n, int64_t m, int sym_kind, okkt_inertia* inertia_out /* [B] or NULL */,
+                      int32_t* flag_out /* [B] or NULL */);
+int okkt_factor_batch_dev(okkt_handle h, int64_t B, const double* d_nzval, int64_t val_stride, const double* shift /* host */,
+                          int64_t nshift, int64_t n, int64_t m, int sym_kind, okkt_inertia* inertia_out /* host */,
+                          int32_t* flag_out /* host */);
+int okkt_solve_batch(okkt_handle h, int64_t B, const double* rhs, double* sol, int64_t nrhs);
+int okkt_solve_batch_dev(okkt_handle h, int64_t B, const double* d_rhs, double* d_sol, int64_t nrhs);
+int okkt_batch_select(okkt_handle h, int64_t b);
+
 
 /* ---- multi-GPU: subtree-to-GPU sharding of ONE factorisation (one process per GPU) -------------------
  * No reference counterpart (the reference is single-process).  Every rank analyses the same
@@ -822,6 +885,17 @@ int okkt_kkt_ipopt_strategy_eig(okkt_kkt_handle k, double delta_prev, const okkt
                                 int32_t max_steps, int32_t scaled,
                                 int32_t* num_fac_out, double* delta_out, int32_t* skipped_out,
                                 okkt_kkt_eig_info* info /* or NULL; steps = 0 when Lanczos never ran */);
+/* The same loop with its attempts taken `width` (1 .. 64) at a time: the delta sequence is known in advance, so
+ * a group of attempts is ONE okkt_factor_batch_dev on the formed values (val_stride = 0) with the candidates as shifts.  The first attempt
+ * in sequence order that succeeds, or that exceeds delta_max, ends the loop, and its slot is selected into the handle: the status,
+ * delta_out, the factor left behind, okkt_kkt_diag_dom_warnings and a following okkt_kkt_compute_direction are bit for bit those of
+ * okkt_kkt_ipopt_strategy.  num_fac_out is the serial count (the index of the chosen attempt + 1), launches_out the number of batched
+ * factorisations.  Slots for `width` items are reserved on the linear solver's handle at the first call.  Refused with
+ * OKKT_ERR_INVALID (okkt_kkt_last_error says why; the handle stays usable): the clever-symmetric kind, whose shift rewrites the values;
+ * a plan that takes no batch (okkt_batch_query); the linear solver's scaling on; width out of range; a call before form_system.
+ * host_symbolic_only handles get OKKT_ERR_NO_DEVICE. */
+int okkt_kkt_ipopt_strategy_batch(okkt_kkt_handle k, double delta_prev, const okkt_kkt_pars* pars, int32_t width,
+                                  int32_t* num_fac_out, double* delta_out, int32_t* launches_out);
 /* Test hook, host only (no device, no handle): the tridiagonal solver of okkt_kkt_min_eig (csrc/lanczos_tridiag.h) on
  * T = tridiag(beta[0 .. k-2]; alpha[0 .. k-1]), 1 <= k <= 64.  beta holds k entries: beta[k-1] is the residual coefficient beta_k of
  * the Lanczos recurrence.  Returns theta_min, theta_max, the unit eigenvector s_out [k] of theta_min (largest entry positive) and

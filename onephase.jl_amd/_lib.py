@@ -31,6 +31,15 @@ OKKT_OP_LDLT = 3
 OKKT_OP_ABS_LDLT = 4
 OKKT_OP = {"L": OKKT_OP_L, "LT": OKKT_OP_LT, "LDLT": OKKT_OP_LDLT, "ABS_LDLT": OKKT_OP_ABS_LDLT}
 
+# uniform batches: why a plan takes none (okkt_batch_info.reason), and the launch shapes
+OKKT_BATCH_OK = 0
+OKKT_BATCH_NOT_ANALYZED = 1
+OKKT_BATCH_PARTITIONED = 2
+OKKT_BATCH_SCHUR = 3
+OKKT_BATCH_SCALING = 4
+OKKT_BATCH_BIG_FRONTS = 5
+OKKT_BATCH_MODE = {"auto": 0, "level": 1, "item": 2}
+
 OKKT_OK = 0
 OKKT_ERR_INVALID = -1
 OKKT_ERR_NO_DEVICE = -2
@@ -254,6 +263,26 @@ class OkktSparseInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktBatchInfo(C.Structure):
+    """okkt_batch_info: whether the analysed plan takes a uniform batch (reason: OKKT_BATCH_*), the HBM of one item's slot, the tasks and
+    levels of the task tree, the kernel launches of a batched factorisation / solve in level and in item mode."""
+    _fields_ = [
+        ("eligible", C.c_int32),
+        ("reason", C.c_int32),
+        ("bytes_per_item", C.c_int64),
+        ("tasks_per_item", C.c_int64),
+        ("levels", C.c_int32),
+        ("max_front", C.c_int32),
+        ("launches_factor_level", C.c_int32),
+        ("launches_solve_level", C.c_int32),
+        ("launches_factor_item", C.c_int32),
+        ("launches_solve_item", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class OkktScalingInfo(C.Structure):
     """okkt_scaling_info: mode and sweeps of the current factor's scaling, the extrema of the row maxima of |S F S| over its non-zero
     rows, and the number of zero rows."""
@@ -410,6 +439,18 @@ SIGNATURES = {
                                          _f64p]),
     "okkt_schur_solve_gmres_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(OkktGmresInfo),
                                              _f64p]),
+    "okkt_batch_query": (C.c_int, [_vp, C.c_int64, C.POINTER(OkktBatchInfo)]),
+    "okkt_batch_reserve": (C.c_int, [_vp, C.c_int64, C.c_int64]),
+    "okkt_batch_release": (C.c_int, [_vp]),
+    "okkt_batch_set_mode": (C.c_int, [_vp, C.c_int]),
+    "okkt_batch_mode_used": (C.c_int, [_vp]),
+    "okkt_factor_batch": (C.c_int, [_vp, C.c_int64, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(OkktInertia),
+                                    C.POINTER(C.c_int32)]),
+    "okkt_factor_batch_dev": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(OkktInertia),
+                                        C.POINTER(C.c_int32)]),
+    "okkt_solve_batch": (C.c_int, [_vp, C.c_int64, _f64p, _f64p, C.c_int64]),
+    "okkt_solve_batch_dev": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int64]),
+    "okkt_batch_select": (C.c_int, [_vp, C.c_int64]),
     "okkt_set_scaling": (C.c_int, [_vp, C.c_int, C.c_int32, _f64p]),
     "okkt_get_scaling": (C.c_int, [_vp, _f64p, C.POINTER(OkktScalingInfo)]),
     "okkt_get_scaling_dev": (C.c_int, [_vp, _vp]),
@@ -456,6 +497,8 @@ SIGNATURES = {
     "okkt_kkt_get_direction": (C.c_int, [_vp, _f64p, _f64p, _f64p]),
     "okkt_kkt_ipopt_strategy": (C.c_int, [_vp, C.c_double, C.POINTER(OkktKktPars), C.POINTER(C.c_int32), _f64p]),
     "okkt_kkt_min_eig": (C.c_int, [_vp, C.c_int32, C.c_double, C.c_int32, C.POINTER(OkktKktEigInfo), _f64p]),
+    "okkt_kkt_ipopt_strategy_batch": (C.c_int, [_vp, C.c_double, C.POINTER(OkktKktPars), C.c_int32, C.POINTER(C.c_int32), _f64p,
+                                                 C.POINTER(C.c_int32)]),
     "okkt_kkt_ipopt_strategy_eig": (C.c_int, [_vp, C.c_double, C.POINTER(OkktKktPars), C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p,
                                               C.POINTER(C.c_int32), C.POINTER(OkktKktEigInfo)]),
     "okkt_debug_tridiag_eig": (C.c_int, [C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]),

@@ -4,7 +4,7 @@
 // of them and on a front tall enough for several chunks per column, and the flat records of the staged big-front assembly
 // (asm_pieces.h) on each of them and under a front of three chunks, and the tridiagonal solver of the Lanczos estimate
 // (lanczos_tridiag.h), and the dense symmetric eigen-solver of okkt_eigs (sym_eig.h), and the sets of the sparse right-hand sides
-// (solve_sparse_host.cpp).  No device code, no HIP call.  SURVEY.md section 5 (host-side
+// (solve_sparse_host.cpp), and the grids of the uniform batches (batch_host.cpp).  No device code, no HIP call.  SURVEY.md section 5 (host-side
 // sanitizer build); GPU sanitizers are not available on this pool.
 #include <cstdio>
 #include <cstdlib>
@@ -18,6 +18,8 @@
 #include "numeric.h"
 #include "pivots.h"
 #include "solve_sparse.h"
+#include "batch.h"
+#include "../../include/okkt.h"
 #include "sym_eig.h"
 #include "symbolic.h"
 
@@ -344,6 +346,23 @@ static int run(const char* name, int n, const std::set<std::pair<int, int>>& e, 
       if (trial == 7) ok = ok && A.fwd_full && A.fringe == 0;
       if (!ok) { fprintf(stderr, "%s (ordering %d): the sets of a sparse solve are not closed or miscounted (trial %d)\n", name, ordering, trial); return 1; }
     }
+  }
+  // the grids of a uniform batch (batch_host.cpp): with a limit that every front passes, every level holds at least one task, the levels
+  // hold every task once and no level's largest front exceeds the plan's; one row less and the plan is refused, nothing counted
+  {
+    BatchShape B, C;
+    batch_shape(S, (int)S.max_front, B);
+    batch_shape(S, (int)S.max_front - 1, C);
+    int64_t cnt = 0;
+    bool ok = B.reason == OKKT_BATCH_OK && B.levels >= 1 && (int)B.level_cnt.size() == B.levels && (int)B.level_maxf.size() == B.levels && B.tasks <= S.nsuper;
+    for (int l = 0; ok && l < B.levels; ++l) {
+      ok = B.level_cnt[l] >= 1 && B.level_maxf[l] >= 1 && B.level_maxf[l] <= S.max_front;
+      cnt += B.level_cnt[l];
+    }
+    ok = ok && cnt == B.tasks && C.reason == OKKT_BATCH_BIG_FRONTS && C.tasks == 0 && C.levels == 0;
+    ok = ok && batch_slot_doubles(S, S.arena_doubles, 4) - batch_slot_doubles(S, S.arena_doubles, 1) == 3 * (2 * S.n + S.sum_r) &&
+         batch_arena_stride(S, S.arena_doubles) % 2 == 0 && batch_arena_stride(S, S.arena_doubles) >= S.arena_doubles + 512 + 2 * S.max_front;
+    if (!ok) { fprintf(stderr, "%s (ordering %d): the grids of a batch do not hold every task once\n", name, ordering); return 1; }
   }
   printf("%-12s ordering %d: n %d nnz(L) %lld supernodes %zu, %zu dataflow tasks\n", name, ordering, n, (long long)S.nnzL, S.sn_col0.size() - 1, ntask);
   return 0;

@@ -75,6 +75,28 @@ __device__ __forceinline__ bool stop_requested_wave(const DevPlan& P) {
   return __builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&P.counters[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0;
 }
 
+// Right-looking LDL^T of the leading npiv columns of an LDS-resident lower-triangular front.
+// F is column-major with leading dimension ldf; wcol is scratch of length f.
+template <int TPB>
+__device__ __forceinline__ void ldl_partial_lds(double* F, double* wcol, int ldf, int f, int npiv) {
+  constexpr int G = TPB / 32;
+  const int tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
+  for (int j = 0; j < npiv; ++j) {
+    const double rd = 1.0 / F[j + j * ldf];  // one division per pivot; l = w * (1/d)
+    for (int i = j + 1 + tid; i < f; i += TPB) {
+      const double w = F[i + j * ldf];
+      wcol[i] = w;             // w_i = l_ij * d_j
+      F[i + j * ldf] = w * rd; // l_ij
+    }
+    __syncthreads();
+    for (int c = j + 1 + grp; c < f; c += G) {
+      const double wc = wcol[c];
+      for (int i = c + lane; i < f; i += 32) F[i + c * ldf] -= F[i + j * ldf] * wc;
+    }
+    __syncthreads();
+  }
+}
+
 // 1/d from v_rcp_f64 and two Newton steps (about 1 ulp); d = 0 gives inf/NaN like the division would
 __device__ __forceinline__ double fast_rcp_f64(double d) {
   double r = __builtin_amdgcn_rcp(d);

@@ -1280,6 +1280,103 @@ int okkt_kkt_ipopt_strategy_eig(okkt_kkt_handle k, double delta_prev, const okkt
   return ipopt_strategy_impl(k, delta_prev, pars, true, max_steps, scaled, num_fac_out, delta_out, skipped_out, info);
 }
 
+// ipopt_strategy! with its attempts taken `width` at a time: the sequence of ipopt_strategy_impl -- the tau rule,
+// the first attempt at delta_zero, delta_inc, the delta_max exit -- is known before any attempt is factored, so a group of attempts is
+// ONE okkt_factor_batch_dev on the formed values (val_stride = 0) with the candidates as shifts.  The first attempt in sequence order
+// that succeeds, or exceeds delta_max, ends the loop; its slot becomes the handle's factor.  Status, delta, the factor left behind and
+// the diagonal-dominance warnings are those of the serial loop; num_fac_out is the serial count (index of the chosen attempt + 1),
+// launches_out the batched factorisations.
+int okkt_kkt_ipopt_strategy_batch(okkt_kkt_handle k, double delta_prev, const okkt_kkt_pars* pars, int32_t width, int32_t* num_fac_out,
+                                  double* delta_out, int32_t* launches_out) {
+  if (!k || !num_fac_out || !delta_out || !launches_out) return OKKT_ERR_INVALID;
+  *num_fac_out = 0;
+  *launches_out = 0;
+  if (!k->ls || k->ls->opts.host_symbolic_only || !k->ls->device_ready) return kk_fail(k, OKKT_ERR_NO_DEVICE, "no HIP device (host_symbolic_only handle)");
+  if (k->kind == OKKT_KKT_CLEVER_SYMMETRIC)
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_ipopt_strategy_batch: not for the clever-symmetric kind (its shift rewrites the values: the attempts do not share one value array)");
+  if (width < 1 || width > 64) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_ipopt_strategy_batch: width outside 1 .. 64");
+  if (!k->formed) return kk_fail(k, OKKT_ERR_INVALID, "kkt solver not ready to factor: form_system has not been called");
+  okkt_solver_s* ls = k->ls;
+  if (ls->sc.mode != OKKT_SCALE_NONE) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_ipopt_strategy_batch: the linear solver's scaling is on (okkt_kkt_set_ls_scaling with OKKT_SCALE_NONE first)");
+  okkt_batch_info q;
+  int rc = okkt_batch_query(ls, 1, &q);
+  if (rc != OKKT_OK) return kk_check_ls(k, rc, "batch query");
+  if (!q.eligible) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_ipopt_strategy_batch: the plan takes no batch (okkt_batch_query reason " + std::to_string(q.reason) + "; plans of small fronts only)");
+  if (!ls->bt.s.arena || ls->bt.B < width) {
+    rc = okkt_batch_reserve(ls, width, std::max<int64_t>(ls->bt.nrhs_max, 1));
+    if (rc != OKKT_OK) return kk_check_ls(k, rc, "batch reserve");
+  }
+  okkt_kkt_pars P;
+  okkt_kkt_default_pars(&P);
+  if (pars) P = *pars;
+  k->diag_dom_warnings = 0;
+  double dmin = 0.0;
+  if ((rc = okkt_kkt_diag_min(k, &dmin)) != OKKT_OK) return rc;
+  double tau = 1.5 * dmin;
+  double delta = P.delta_zero;
+  *delta_out = delta;
+  // the attempts in the order of ipopt_strategy_impl: (delta, inside the loop: the delta_max exit applies)
+  bool zero_first = tau > 0.0;
+  if (zero_first) tau = 0.0;
+  int it = 0;
+  auto next_attempt = [&](double* d, bool* in_loop) -> bool {
+    if (zero_first) { zero_first = false; *d = P.delta_zero; *in_loop = false; return true; }
+    if (it >= P.max_it) return false;
+    ++it;
+    if (it == 1) delta = delta_prev != 0.0 ? std::max(P.delta_min - tau, delta_prev * P.delta_dec) : P.delta_start - tau;
+    else delta = delta * P.delta_inc;
+    *d = delta;
+    *in_loop = true;
+    return true;
+  };
+  const int64_t mm = k->kind == OKKT_KKT_SYMMETRIC ? k->m : k->kd;
+  const int sym = (k->kind == OKKT_KKT_SYMMETRIC || k->kd) ? OKKT_SYM_SYMMETRIC : OKKT_SYM_DEFINITE;
+  const bool zero_tol = k->kind != OKKT_KKT_SYMMETRIC && k->kd;      // the bordered Schur system counts as the Cholesky rule does (kkt_factor_impl)
+  k->factored = false;
+  k->have_dir = false;
+  k->sym_dir_ok = false;
+  k->clever_vecs_ok = false;
+  int num_fac = 0;
+  for (;;) {
+    double cand[64];
+    bool loop[64];
+    int32_t flags[64];
+    int g = 0;
+    while (g < width && next_attempt(&cand[g], &loop[g])) {
+      ++g;
+      if (loop[g - 1] && cand[g - 1] > P.delta_max) break;      // this attempt ends the loop whatever its inertia
+    }
+    if (g == 0) return kk_fail(k, OKKT_ERR_INTERNAL, "max it");
+    rc = solver_factor_batch_device(ls, g, k->Avals, 0, cand, k->n, k->n, mm, sym, nullptr, flags, zero_tol);
+    if (rc < 0) return kk_check_ls(k, rc, "batched factor");
+    ++*launches_out;
+    k->tm_factor.reset();      // the shifts are set inside the batched launches: no shift segment of its own
+    k->t_factor_ms = ls->last_factor_ms;
+    for (int j = 0; j < g; ++j) {
+      ++num_fac;
+      *num_fac_out = num_fac;
+      *delta_out = cand[j];
+      k->delta = cand[j];
+      bool chosen = flags[j] == 1;
+      int status = 1;
+      if (!chosen) {
+        static const bool scan = !(getenv("OKKT_DIAG_DOM_SCAN") && atoi(getenv("OKKT_DIAG_DOM_SCAN")) == 0);
+        if (scan) {
+          int32_t dom = -1;
+          const int rc3 = okkt_kkt_is_diag_dom(k, &dom);
+          if (rc3 < 0) return rc3;
+          if (dom == 1) ++k->diag_dom_warnings;
+        }
+        if (loop[j] && cand[j] > P.delta_max) { chosen = true; status = 0; }      // :failure: the complete factor of the last delta stays to solve with
+      }
+      if (!chosen) continue;
+      if ((rc = okkt_batch_select(ls, j)) != OKKT_OK) return kk_check_ls(k, rc, "batch select");
+      k->factored = true;
+      return status;
+    }
+  }
+}
+
 int okkt_kkt_system_rhs(okkt_kkt_handle k, const double* J_nzval_cur, const double* grad, const double* cons,
                         const double* s, const double* y, double mu, double a_norm_penalty,
                         double eta_P, double eta_D, double eta_mu, double* dual_r, double* primal_r, double* comp_r) {

@@ -48,28 +48,6 @@ __global__ void k_fold_counts(DevPlan P) {
   if (fail) atomicExch(&P.counters[4], 1ull);
 }
 
-// Right-looking LDL^T of the leading npiv columns of an LDS-resident lower-triangular front.
-// F is column-major with leading dimension ldf; wcol is scratch of length f.
-template <int TPB>
-__device__ __forceinline__ void ldl_partial_lds(double* F, double* wcol, int ldf, int f, int npiv) {
-  constexpr int G = TPB / 32;
-  const int tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
-  for (int j = 0; j < npiv; ++j) {
-    const double rd = 1.0 / F[j + j * ldf];  // one division per pivot; l = w * (1/d)
-    for (int i = j + 1 + tid; i < f; i += TPB) {
-      const double w = F[i + j * ldf];
-      wcol[i] = w;             // w_i = l_ij * d_j
-      F[i + j * ldf] = w * rd; // l_ij
-    }
-    __syncthreads();
-    for (int c = j + 1 + grp; c < f; c += G) {
-      const double wc = wcol[c];
-      for (int i = c + lane; i < f; i += 32) F[i + c * ldf] -= F[i + j * ldf] * wc;
-    }
-    __syncthreads();
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // small fronts: one workgroup, front resident in LDS
 // ------------------------------------------------------------------------------------------
@@ -96,6 +74,8 @@ __device__ __forceinline__ void flow_signal(int* flag, int value) {
   if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// (batch.hip, front_task: a copy of this kernel's loop body with FLOW = false, for the uniform batches -- a change here must be made there
+// too: tests/test_gpu_batch.py compares the two bit for bit)
 template <int TPB, bool FLOW = false>
 __global__ __launch_bounds__(TPB) void k_front_small(DevPlan P, const int* __restrict__ list, double tol, int* __restrict__ flags = nullptr, int epoch = 0, int wait_epoch = 0) {
   extern __shared__ __attribute__((aligned(16))) double sm[];

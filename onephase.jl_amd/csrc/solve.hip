@@ -307,6 +307,8 @@ __device__ __forceinline__ void flow_publish(unsigned long long* ver, int t0, in
 // ------------------------------------------------------------------------------------------------------------------
 // FLOW: the tasks of several levels in one launch (see k_front_small<.., FLOW> in numeric.hip): a task waits for the flags of its
 // children tasks, contribution vectors travel with agent-scope accesses, flags[root] = epoch when the task is done.
+// (batch.hip, fs_task / bs_task: copies of the loop bodies of k_fs_small and k_bs_small with FLOW = false, for the uniform batches -- a change
+// here must be made there too: tests/test_gpu_batch.py compares the solutions bit for bit)
 template <int TPB, int R, bool FLOW = false>
 __global__ __launch_bounds__(TPB) void k_fs_small(DevPlan P, const int* __restrict__ list, int ldw, int* __restrict__ flags = nullptr, int epoch = 0, int wait_epoch = 0) {
   extern __shared__ __attribute__((aligned(16))) double sm[];      // [R][ldw]

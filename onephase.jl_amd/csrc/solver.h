@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/okkt.h"
+#include "batch.h"
 #include "condest.h"
 #include "dense_ldlt.h"
 #include "eigs.h"
@@ -95,6 +96,9 @@ struct okkt_solver_s {
   // eigenpairs nearest zero (eigs.hip): the basis V, Op V and the block vectors of the Krylov-Schur method, allocated
   // by the first okkt_eigs after an analysis (grown for a larger basis) and released with the refinement map
   okkt::EigsWork eg;
+  // uniform batches (batch.hip): the items' slots, allocated by okkt_batch_reserve and released by okkt_batch_release
+  // and with the refinement map
+  okkt::BatchWork bt;
 };
 
 namespace okkt {
@@ -115,6 +119,9 @@ inline int schur_refuse(okkt_solver_s* h, const char* what) {
                                                    "use okkt_factor_schur / okkt_schur_condense / okkt_schur_expand, or clear the set with ns = 0)");
 }
 int solver_ensure_numeric(okkt_solver_s* h);
+// okkt_factor_batch_dev behind its pointer checks (api_batch.cpp); zero_tol as solver_factor_device's
+int solver_factor_batch_device(okkt_solver_s* h, int64_t B, const double* d_vals, int64_t val_stride, const double* shift, int64_t nshift, int64_t n, int64_t m,
+                               int sym_kind, okkt_inertia* inertia_out, int32_t* flag_out, bool zero_tol = false);
 // okkt_set_scaling behind its argument checks (api.cpp): also what okkt_kkt_set_ls_scaling forwards to
 int solver_set_scaling(okkt_solver_s* h, int mode, int32_t sweeps, const double* s_user);
 // refinement driver (api_refine.cpp): x = F \ b, then corrections from the double-double residual against d_nzval until omega <= tol,

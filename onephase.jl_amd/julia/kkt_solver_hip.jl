@@ -212,7 +212,18 @@ function ipopt_strategy!(iter::Class_iterate, k::HIP_KKT_solver, pars::Class_par
     # Lanczos bound on lambda_min(H + J' Sigma J) certifies to fail (okkt_kkt_ipopt_strategy_eig); status and delta do not change
     eig_steps = hasproperty(pars.kkt, :hip_delta_eig_steps) ? pars.kkt.hip_delta_eig_steps : 0
     eig_scaled = hasproperty(pars.kkt, :hip_delta_eig_scaled) ? pars.kkt.hip_delta_eig_scaled : 0
-    if eig_steps > 0
+    # pars.kkt.hip_delta_batch > 1 ("kkt!hip_delta_batch"): the attempts that many at a time as one uniform batch on the formed values
+    # (okkt_kkt_ipopt_strategy_batch, DESIGN.md section 8.15); a refusal (big fronts, the clever-symmetric kind, scaling) takes the serial loop
+    width = hasproperty(pars.kkt, :hip_delta_batch) ? pars.kkt.hip_delta_batch : 0
+    rc = Cint(-1)
+    if width > 1
+        launches = Ref{Int32}(0)
+        rc = ccall((:okkt_kkt_ipopt_strategy_batch, OKKT_LIB), Cint, (Ptr{Cvoid}, Float64, Ref{OkktKktPars}, Int32, Ref{Int32}, Ref{Float64}, Ref{Int32}),
+                   k.handle, get_delta(iter), p, min(width, 64), num_fac, delta, launches)
+        rc < -1 && kkt_hip_check(k, "okkt_kkt_ipopt_strategy_batch", rc)      # -1 = refused: the serial loop below
+    end
+    if rc >= 0
+    elseif eig_steps > 0
         skipped = Ref{Int32}(0); info = Ref(OkktKktEigInfo(0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0.0))
         rc = kkt_hip_check(k, "okkt_kkt_ipopt_strategy_eig", ccall((:okkt_kkt_ipopt_strategy_eig, OKKT_LIB), Cint,
             (Ptr{Cvoid}, Float64, Ref{OkktKktPars}, Int32, Int32, Ref{Int32}, Ref{Float64}, Ref{Int32}, Ref{OkktKktEigInfo}),

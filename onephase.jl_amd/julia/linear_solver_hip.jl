@@ -438,6 +438,68 @@ function sparse_reach(solver::linear_solver_HIP, b_rows::Vector{Int64}, dim::Int
     return info[], active
 end
 
+# Uniform batches (DESIGN.md section 8.15): B systems on the analysed pattern, plans of small fronts only.  Not part of the reference
+# interface.  okkt_batch_info of include/okkt.h
+struct OkktBatchInfo
+    eligible::Int32; reason::Int32
+    bytes_per_item::Int64; tasks_per_item::Int64
+    levels::Int32; max_front::Int32
+    launches_factor_level::Int32; launches_solve_level::Int32
+    launches_factor_item::Int32; launches_solve_item::Int32
+end
+
+function batch_query(solver::linear_solver_HIP; nrhs_max::Integer=1)
+    info = Ref(OkktBatchInfo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    rc = ccall((:okkt_batch_query, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Ref{OkktBatchInfo}), solver.handle, nrhs_max, info)
+    rc < 0 && okkt_error(solver, "okkt_batch_query", rc)
+    return info[]
+end
+
+# mode: 0 by the measured rule, 1 level mode, 2 item mode
+function batch_reserve(solver::linear_solver_HIP, B::Integer; nrhs_max::Integer=1, mode::Union{Nothing,Integer}=nothing)
+    if mode !== nothing
+        rc = ccall((:okkt_batch_set_mode, OKKT_LIB), Cint, (Ptr{Cvoid}, Cint), solver.handle, mode)
+        rc < 0 && okkt_error(solver, "okkt_batch_set_mode", rc)
+    end
+    rc = ccall((:okkt_batch_reserve, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Int64), solver.handle, B, nrhs_max)
+    rc < 0 && okkt_error(solver, "okkt_batch_reserve", rc)
+end
+
+function batch_release(solver::linear_solver_HIP)
+    rc = ccall((:okkt_batch_release, OKKT_LIB), Cint, (Ptr{Cvoid},), solver.handle)
+    rc < 0 && okkt_error(solver, "okkt_batch_release", rc)
+end
+
+# vals: nnz x B (one column per item), or a vector shared by all items together with shifts (length B); shifts[b] is added to the first
+# nshift (default n) diagonal entries.  Returns the items' flags and inertia counts (4 x B: pos, neg, zero, nonfinite)
+function ls_factor_batch(solver::linear_solver_HIP, vals::Union{Matrix{Float64},Vector{Float64}}, n::Int64, m::Int64;
+                         shifts::Union{Nothing,Vector{Float64}}=nothing, nshift::Int64=n)
+    B = vals isa Matrix ? size(vals, 2) : length(shifts)
+    stride = vals isa Matrix ? size(vals, 1) : 0
+    inertia = zeros(Int64, 4, B); flags = zeros(Int32, B)
+    kind = solver.sym == :definite ? 0 : 1
+    rc = ccall((:okkt_factor_batch, OKKT_LIB), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Int64, Cint, Ptr{Int64}, Ptr{Int32}),
+               solver.handle, B, vals, stride, shifts === nothing ? C_NULL : shifts, nshift, n, m, kind, inertia, flags)
+    rc < 0 && okkt_error(solver, "okkt_factor_batch", rc)
+    return flags, inertia
+end
+
+# rhs: dim x nrhs x B (or dim x B): the items' solutions in the same shape
+function ls_solve_batch(solver::linear_solver_HIP, rhs::Array{Float64})
+    B = size(rhs, ndims(rhs)); nrhs = ndims(rhs) == 3 ? size(rhs, 2) : 1
+    sol = similar(rhs)
+    rc = ccall((:okkt_solve_batch, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Int64), solver.handle, B, rhs, sol, nrhs)
+    rc < 0 && okkt_error(solver, "okkt_solve_batch", rc)
+    return sol
+end
+
+# slot b (1-based) becomes the handle's own factor
+function batch_select(solver::linear_solver_HIP, b::Integer)
+    rc = ccall((:okkt_batch_select, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64), solver.handle, b - 1)
+    rc < 0 && okkt_error(solver, "okkt_batch_select", rc)
+end
+
 # ls_solve_refine! through the Schur route: every solve is okkt_schur_solve's, the residuals are against the whole A.  Needs
 # okkt_factor_schur and okkt_schur_factor of the handle's own S.
 function schur_solve_refine!(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}, my_rhs::Array{Float64,1}, my_sol::Array{Float64,1};

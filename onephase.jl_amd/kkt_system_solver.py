@@ -124,6 +124,10 @@ class Class_kkt_solver_options:   # parameters.jl:4-46 (the entries the path rea
     # hip_delta_eig_scaled = 1: Lanczos on the Jacobi-scaled operator ("kkt!hip_delta_eig_steps", "kkt!hip_delta_eig_scaled")
     hip_delta_eig_steps: int = 0
     hip_delta_eig_scaled: int = 0
+    # ipopt_strategy! with its attempts factored hip_delta_batch (2 .. 64) at a time as one uniform batch on the formed values, the candidates
+    # as shifts (okkt_kkt_ipopt_strategy_batch): the same status, delta and factor.  For plans of small fronts only; on any other plan, for
+    # the clever-symmetric kind and with hip_ls_scaling on the serial loop runs instead.  0 = off ("kkt!hip_delta_batch")
+    hip_delta_batch: int = 0
 
 
 def okkt_opts_from_pars(kkt):
@@ -209,6 +213,9 @@ class HIP_KKT_solver:
         # the Lanczos bound of the delta loop is an argument of okkt_kkt_ipopt_strategy_eig: keywords override pars.kkt
         self.delta_eig_steps = int(opts.pop("hip_delta_eig_steps", self.pars.kkt.hip_delta_eig_steps))
         self.delta_eig_scaled = int(opts.pop("hip_delta_eig_scaled", self.pars.kkt.hip_delta_eig_scaled))
+        self.delta_batch = int(opts.pop("hip_delta_batch", self.pars.kkt.hip_delta_batch))
+        self.delta_loop = None          # "batch" | "serial": the loop the last ipopt_strategy_b took
+        self.delta_launches = None      # batched factorisations of the last ipopt_strategy_b (None: serial loop)
         self.skipped = 0
         self.delta_eig_info = None
         self._opts = opts
@@ -486,7 +493,13 @@ class HIP_KKT_solver:
         p.delta_start, p.delta_min, p.delta_max, p.delta_inc, p.delta_dec, p.delta_zero = d.start, d.min, d.max, d.inc, d.dec, d.zero
         nfac = C.c_int32()
         delta = C.c_double()
-        if self.delta_eig_steps > 0:
+        self.delta_loop, self.delta_launches = "serial", None
+        if self.delta_batch > 1 and self._delta_batch_ok():
+            launches = C.c_int32()
+            rc = self._check(self._lib.okkt_kkt_ipopt_strategy_batch(self._k, float(it.delta), C.byref(p), min(self.delta_batch, 64), C.byref(nfac),
+                                                                     C.byref(delta), C.byref(launches)), "okkt_kkt_ipopt_strategy_batch")
+            self.delta_loop, self.delta_launches = "batch", int(launches.value)
+        elif self.delta_eig_steps > 0:
             # the same loop without the attempts a Lanczos bound on lambda_min(H + J' Sigma J) certifies to fail: the same status and delta
             skipped, info = C.c_int32(), L.OkktKktEigInfo()
             rc = self._check(self._lib.okkt_kkt_ipopt_strategy_eig(self._k, float(it.delta), C.byref(p), self.delta_eig_steps, self.delta_eig_scaled,
@@ -508,6 +521,35 @@ class HIP_KKT_solver:
             for _ in range(self.diag_dom_warnings):
                 print("WARNING: Inertia calculation incorrect")
         return ("success" if rc == 1 else "failure"), int(nfac.value), float(delta.value)
+
+    def ipopt_strategy_batch(self, it, width):
+        """okkt_kkt_ipopt_strategy_batch: (status, num_fac, delta, launches); raises OkktError on a refusal (the solver stays usable)."""
+        p = L.OkktKktPars()
+        self._lib.okkt_kkt_default_pars(C.byref(p))
+        d = self.pars.delta
+        p.delta_start, p.delta_min, p.delta_max, p.delta_inc, p.delta_dec, p.delta_zero = d.start, d.min, d.max, d.inc, d.dec, d.zero
+        nfac, delta, launches = C.c_int32(), C.c_double(), C.c_int32()
+        rc = self._check(self._lib.okkt_kkt_ipopt_strategy_batch(self._k, float(it.delta), C.byref(p), int(width), C.byref(nfac), C.byref(delta),
+                                                                 C.byref(launches)), "okkt_kkt_ipopt_strategy_batch")
+        self._delta = delta.value
+        self.delta_x_vec = delta.value * np.ones(it.dim())
+        self.delta_s_vec = np.zeros(it.ncon())
+        self.ready = "factored"
+        nwarn = C.c_int32()
+        if self._lib.okkt_kkt_diag_dom_warnings(self._k, C.byref(nwarn)) == 0:
+            self.diag_dom_warnings = int(nwarn.value)
+        return ("success" if rc == 1 else "failure"), int(nfac.value), float(delta.value), int(launches.value)
+
+    def _delta_batch_ok(self):
+        """The batched delta loop applies: not the clever-symmetric kind, no linear-solver scaling, a plan of small fronts only."""
+        if self.kind == "clever_symmetric" or self.ls_scaling:
+            return False
+        from .linear_system_solvers import linear_solver_HIP
+        ls = linear_solver_HIP.of_kkt(self)
+        try:
+            return ls.batch_query()["eligible"] == 1
+        except OkktError:
+            return False
 
     def min_eig(self, max_steps=0, tol=0.0, scaled=0, with_vector=True):
         """okkt_kkt_min_eig: (info, v) -- the Lanczos estimate of lambda_min(Q(0)), Q(0) = H + J' Sigma J of the last form_system_b, as a

@@ -266,6 +266,81 @@ class linear_solver_HIP(abstract_linear_system_solver):
         self.ls_solve_b(np.asarray(my_rhs, dtype=np.float64).ravel(), sol, timer)
         return sol
 
+    # -- uniform batches: B systems on the analysed pattern (not part of the reference interface)
+    def batch_query(self, nrhs_max=1):
+        """Whether the analysed plan takes a batch, and what one costs: dict of okkt_batch_info (host only)."""
+        self._need()
+        info = L.OkktBatchInfo()
+        self._check(self._lib.okkt_batch_query(self._h, int(nrhs_max), C.byref(info)), "okkt_batch_query")
+        return info.as_dict()
+
+    def batch_reserve(self, B, nrhs_max=1, mode=None):
+        """Slots for B items with solve work for nrhs_max columns; mode: None (keep), "auto", "level" or "item"."""
+        self._need()
+        if mode is not None:
+            self._check(self._lib.okkt_batch_set_mode(self._h, L.OKKT_BATCH_MODE[mode]), "okkt_batch_set_mode")
+        self._check(self._lib.okkt_batch_reserve(self._h, int(B), int(nrhs_max)), "okkt_batch_reserve")
+
+    def batch_release(self):
+        self._need()
+        self._check(self._lib.okkt_batch_release(self._h), "okkt_batch_release")
+
+    def batch_mode_used(self):
+        return {v: k for k, v in L.OKKT_BATCH_MODE.items()}.get(self._lib.okkt_batch_mode_used(self._h))
+
+    def _batch_factor(self, fn, what, B, vals, stride, shifts, nshift, n, m):
+        sh = None if shifts is None else L.f64(shifts).ravel()
+        if sh is not None and sh.size != B:
+            raise OkktError("shifts must have one entry per item")
+        inert = (L.OkktInertia * B)()
+        flags = np.zeros(B, dtype=np.int32)
+        kind = L.OKKT_SYM_DEFINITE if self.sym == "definite" else L.OKKT_SYM_SYMMETRIC
+        self._check(fn(self._h, B, vals, stride, None if sh is None else L.p_f64(sh), int(nshift), int(n), int(m), kind, inert,
+                       flags.ctypes.data_as(C.POINTER(C.c_int32))), what)
+        self.batch_inertia = [it.as_tuple() for it in inert]
+        return flags
+
+    def ls_factor_batch(self, vals, n, m, shifts=None, nshift=None, B=None):
+        """Factor B value sets on the analysed pattern.  vals: [B, nnz] (one row per item), or [nnz] shared by all items together with
+        shifts [B] (B may then be given instead of shifts).  shifts[b] is added to the first nshift (default n) diagonal entries.
+        Returns the items' flags (1: inertia (n, m, 0)); the counts are left in self.batch_inertia."""
+        self._need()
+        v = L.f64(vals)
+        if v.ndim == 1:
+            B = int(B if B is not None else len(shifts))
+            stride = 0
+        else:
+            B, stride = v.shape[0], v.shape[1]
+        return self._batch_factor(self._lib.okkt_factor_batch, "okkt_factor_batch", B, L.p_f64(v), stride, shifts,
+                                  n if nshift is None else nshift, n, m)
+
+    def ls_factor_batch_dev(self, d_nzval, B, val_stride, n, m, shifts=None, nshift=None):
+        self._need()
+        return self._batch_factor(self._lib.okkt_factor_batch_dev, "okkt_factor_batch_dev", int(B), C.c_void_p(d_nzval), int(val_stride), shifts,
+                                  n if nshift is None else nshift, n, m)
+
+    def ls_solve_batch(self, rhs):
+        """rhs [B, dim] or [B, nrhs, dim] -> the items' solutions, same shape."""
+        self._need()
+        b = L.f64(rhs)
+        if b.ndim not in (2, 3) or b.shape[-1] != self._dim:
+            raise OkktError("rhs must be [B, dim] or [B, nrhs, dim] of the analysed dimension")
+        nrhs = 1 if b.ndim == 2 else b.shape[1]
+        out = np.empty_like(b)
+        self._check(self._lib.okkt_solve_batch(self._h, b.shape[0], L.p_f64(b), L.p_f64(out), nrhs), "okkt_solve_batch")
+        return out
+
+    def ls_solve_batch_dev(self, d_rhs, d_sol, B, nrhs=1):
+        self._need()
+        self._check(self._lib.okkt_solve_batch_dev(self._h, int(B), C.c_void_p(d_rhs), C.c_void_p(d_sol), int(nrhs)), "okkt_solve_batch_dev")
+
+    def batch_select(self, b):
+        """Slot b becomes the handle's own factor: every other call then behaves as after ls_factor of that item."""
+        self._need()
+        self._check(self._lib.okkt_batch_select(self._h, int(b)), "okkt_batch_select")
+        if getattr(self, "batch_inertia", None) and 0 <= b < len(self.batch_inertia):
+            self.inertia = self.batch_inertia[b]
+
     # -- refinement with extra-precise residuals (not part of the reference interface; DESIGN.md section 8.2)
     def _values(self, nzval_or_matrix):
         if isinstance(nzval_or_matrix, np.ndarray) and nzval_or_matrix.ndim == 1:
