@@ -743,6 +743,91 @@ int okkt_solve_batch(okkt_handle h, int64_t B, const double* rhs, double* sol, i
 int okkt_solve_batch_dev(okkt_handle h, int64_t B, const double* d_rhs, double* d_sol, int64_t nrhs);
 int okkt_batch_select(okkt_handle h, int64_t b);
 
+/* ---- Scenario batches: Schur-complement decomposition of B blocks on one pattern -------------------------
+ * The handle is in Schur mode (okkt_set_schur before okkt_analyze) and its analysed pattern [[A11 A12]; [A21 A22]] is shared by B items
+ * with values of their own.  The target is the arrowhead system
+ *     A11_b x_b + A12_b x_L = b_b   (b = 0 .. B-1),      sum_b A21_b x_b + A0 x_L = b_L,
+ * the KKT system of a two-stage stochastic programme, a scenario-tree MPC or a multi-start with shared variables: every item factors
+ * its A11 and assembles its S_b = A22_b - A21_b A11_b^-1 A12_b, the S_b are summed on the device, and one dense Bunch-Kaufman factor of
+ * sum_b S_b (+ S_add) solves the linking system.  (A0 is sum_b A22_b + S_add: give the linking block once as S_add with zero A22
+ * values in the items, or spread over the items' A22.)  No host round trip per item.
+ * Eligible: analysed, not partitioned, a Schur set, every INTERIOR front a small front (order <= small_front_max, at most 136; the
+ * Schur front itself is assembled, never factored, and exempt), ns <= 2048 (the bound of the column-in-LDS assembly).  Item b's
+ * factor, D, counts, S_b and condensed right-hand side are bit for bit what okkt_factor_schur / okkt_get_schur / okkt_schur_condense
+ * give for its values on a fresh handle.
+ * The order of the sums is part of the interface and depends neither on the device nor on ns: with G = ceil(B / OKKT_SBATCH_GROUP),
+ * P_g is the sequential sum, starting from 0.0, over the items OKKT_SBATCH_GROUP * g .. min(OKKT_SBATCH_GROUP * (g + 1), B) - 1 in
+ * item order, the sum is ((P_0 + P_1) + ... + P_{G-1}), and the caller's addend (S_add, rhs0) is added last.  The sum of the S_b is
+ * bitwise symmetric.  No atomics.
+ * Scenario batches run in LEVEL MODE ONLY (one launch per level of the interior's task tree, grid = tasks x B): the one-workgroup-
+ * per-item solve cannot be interrupted for the dense solve, and no batch size was found at which item mode pays.  okkt_batch_set_mode
+ * and OKKT_BATCH_MODE do not apply.  No workgroup waits for another inside a launch; every dependency is a launch boundary.
+ * okkt_schur_batch_query: host only, also on host_symbolic_only handles; eligible = 0 comes with the first reason that applies, in the
+ * order of the codes below.  bytes_per_item: the slot of okkt_batch_query plus the item's right-hand side of the linking system and
+ * its share of the group partials (a started group is allocated whole); bytes_shared: the sum, r2 / x2 for four columns and the
+ * batch's own dense factor.  levels / tasks_per_item / max_front: of the interior.  launches_factor: the shifts and counters, one
+ * launch per level, the Schur fronts.  launches_solve: the batch's own launches of one fused solve per group of up to four right-hand
+ * sides (gather, the levels upwards, the items' r2, the two stages of their sum, the put, the levels downwards, scatter); the launches
+ * of the dense solve between them depend on ns and are not counted.
+ * okkt_batch_query / okkt_batch_reserve keep answering OKKT_BATCH_SCHUR for such a handle.
+ * okkt_schur_batch_reserve(B in 1..65535, nrhs_max >= 1) replaces a previous reservation; a re-analysis, a partition, a changed or
+ * cleared set release it, and every call compares the plan it finds with the one reserved for (a stale reservation is released and
+ * the call refused).  The handle's own factor and its own dense factor (okkt_schur_factor) are not touched by any call but _select.
+ * okkt_factor_schur_batch(_dev): arguments as okkt_factor_batch's, n1 + m1 = dim - ns as okkt_factor_schur's; the counts and flags
+ * cover the dim - ns interior pivots of the item alone.
+ * okkt_schur_batch_get(_dev)(b): S_b for b in 0 .. B-1, the sum for b = -1; full and symmetric, rows and columns in the order of the
+ * set, column-major with leading dimension ld >= ns.
+ * okkt_schur_batch_factor(_dev): the dense factor of sum_b S_b (+ S_add: ns x ns, full symmetric, its lower triangle is read, added
+ * last; NULL: none).  inertia_total = sum_b inertia(A11_b) + inertia(S).  Returns 1 when no pivot of S is zero or non-finite, else 0
+ * (the rule of okkt_schur_factor), or a negative status.
+ * okkt_schur_batch_condense(_dev): rhs [B][nrhs][dim] -> r2_sum [nrhs][ns] = sum_b r2_b by the rule above, and r2_items [B][nrhs][ns]
+ * (or NULL).  okkt_schur_batch_expand(_dev): the same x2 [nrhs][ns] is put into every item; sol [B][nrhs][dim].
+ * okkt_schur_batch_solve(_dev): the fused solve -- one forward sweep over the interiors, r2 = (sum_b r2_b) + rhs0 (rhs0 [nrhs][ns] or
+ * NULL, added last; the entries rhs[b][.][idx] are the items' shares of b_L and are summed with them), the dense solve, the put and
+ * one backward sweep.  rhs may alias sol.  sol[b][.][idx] is x_L in every item.  Needs okkt_schur_batch_factor and the B of the
+ * last okkt_factor_schur_batch.
+ * okkt_schur_batch_select(b): slot b -> the handle's own numeric state; afterwards every entry point behaves as after
+ * okkt_factor_schur of that item.
+ * Refusals (OKKT_ERR_INVALID with the reason, the handle stays usable): no reservation, B outside 1 .. the reserved, a solve before
+ * okkt_schur_batch_factor, nrhs above the reserved nrhs_max, null pointers, ld < ns, a scaling.  OKKT_ERR_NO_DEVICE on
+ * host_symbolic_only handles.  Out of scope: refinement, GMRES, selected inversion on the batch (select an item, or use the routes
+ * of a single handle). */
+#define OKKT_SBATCH_OK 0
+#define OKKT_SBATCH_NOT_ANALYZED 1
+#define OKKT_SBATCH_PARTITIONED 2
+#define OKKT_SBATCH_NO_SET 3
+#define OKKT_SBATCH_BIG_FRONTS 4
+#define OKKT_SBATCH_SET_TOO_LARGE 5
+#define OKKT_SBATCH_GROUP 32
+typedef struct {
+  int32_t eligible, reason;
+  int64_t ns;
+  int64_t bytes_per_item, bytes_shared;
+  int64_t tasks_per_item;
+  int32_t levels, max_front;
+  int32_t launches_factor, launches_solve;
+} okkt_schur_batch_info;
+int okkt_schur_batch_query(okkt_handle h, int64_t nrhs_max, okkt_schur_batch_info* out);
+int okkt_schur_batch_reserve(okkt_handle h, int64_t B, int64_t nrhs_max);
+int okkt_schur_batch_release(okkt_handle h);
+int okkt_factor_schur_batch(okkt_handle h, int64_t B, const double* nzval, int64_t val_stride, const double* shift /* [B] or NULL */,
+                            int64_t nshift, int64_t n1, int64_t m1, int sym_kind, okkt_inertia* inertia_items /* [B] or NULL */,
+                            int32_t* flag_items /* [B] or NULL */);
+int okkt_factor_schur_batch_dev(okkt_handle h, int64_t B, const double* d_nzval, int64_t val_stride, const double* shift /* host */,
+                                int64_t nshift, int64_t n1, int64_t m1, int sym_kind, okkt_inertia* inertia_items /* host */,
+                                int32_t* flag_items /* host */);
+int okkt_schur_batch_get(okkt_handle h, int64_t b, double* S, int64_t ld);
+int okkt_schur_batch_get_dev(okkt_handle h, int64_t b, double* d_S, int64_t ld);
+int okkt_schur_batch_factor(okkt_handle h, const double* S_add, int64_t ld, okkt_inertia* inertia_S, okkt_inertia* inertia_total);
+int okkt_schur_batch_factor_dev(okkt_handle h, const double* d_S_add, int64_t ld, okkt_inertia* inertia_S, okkt_inertia* inertia_total);
+int okkt_schur_batch_condense(okkt_handle h, int64_t B, const double* rhs, double* r2_sum, double* r2_items /* or NULL */, int64_t nrhs);
+int okkt_schur_batch_condense_dev(okkt_handle h, int64_t B, const double* d_rhs, double* d_r2_sum, double* d_r2_items, int64_t nrhs);
+int okkt_schur_batch_expand(okkt_handle h, int64_t B, const double* rhs, const double* x2, double* sol, int64_t nrhs);
+int okkt_schur_batch_expand_dev(okkt_handle h, int64_t B, const double* d_rhs, const double* d_x2, double* d_sol, int64_t nrhs);
+int okkt_schur_batch_solve(okkt_handle h, int64_t B, const double* rhs, const double* rhs0 /* or NULL */, double* sol, int64_t nrhs);
+int okkt_schur_batch_solve_dev(okkt_handle h, int64_t B, const double* d_rhs, const double* d_rhs0, double* d_sol, int64_t nrhs);
+int okkt_schur_batch_select(okkt_handle h, int64_t b);
+
 
 /* ---- multi-GPU: subtree-to-GPU sharding of ONE factorisation (one process per GPU) -------------------
  * No reference counterpart (the reference is single-process).  Every rank analyses the same

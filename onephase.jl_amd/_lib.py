@@ -39,6 +39,14 @@ OKKT_BATCH_SCHUR = 3
 OKKT_BATCH_SCALING = 4
 OKKT_BATCH_BIG_FRONTS = 5
 OKKT_BATCH_MODE = {"auto": 0, "level": 1, "item": 2}
+# scenario batches: why a plan takes none (okkt_schur_batch_info.reason), and the group size of the sums over the items
+OKKT_SBATCH_OK = 0
+OKKT_SBATCH_NOT_ANALYZED = 1
+OKKT_SBATCH_PARTITIONED = 2
+OKKT_SBATCH_NO_SET = 3
+OKKT_SBATCH_BIG_FRONTS = 4
+OKKT_SBATCH_SET_TOO_LARGE = 5
+OKKT_SBATCH_GROUP = 32
 
 OKKT_OK = 0
 OKKT_ERR_INVALID = -1
@@ -283,6 +291,26 @@ class OkktBatchInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktSchurBatchInfo(C.Structure):
+    """okkt_schur_batch_info: whether the analysed plan takes a scenario batch (reason: OKKT_SBATCH_*), the order of the Schur set, the
+    HBM of one item and of what the items share, the tasks and levels of the interior, the batch's own kernel launches."""
+    _fields_ = [
+        ("eligible", C.c_int32),
+        ("reason", C.c_int32),
+        ("ns", C.c_int64),
+        ("bytes_per_item", C.c_int64),
+        ("bytes_shared", C.c_int64),
+        ("tasks_per_item", C.c_int64),
+        ("levels", C.c_int32),
+        ("max_front", C.c_int32),
+        ("launches_factor", C.c_int32),
+        ("launches_solve", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class OkktScalingInfo(C.Structure):
     """okkt_scaling_info: mode and sweeps of the current factor's scaling, the extrema of the row maxima of |S F S| over its non-zero
     rows, and the number of zero rows."""
@@ -451,6 +479,24 @@ SIGNATURES = {
     "okkt_solve_batch": (C.c_int, [_vp, C.c_int64, _f64p, _f64p, C.c_int64]),
     "okkt_solve_batch_dev": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int64]),
     "okkt_batch_select": (C.c_int, [_vp, C.c_int64]),
+    "okkt_schur_batch_query": (C.c_int, [_vp, C.c_int64, C.POINTER(OkktSchurBatchInfo)]),
+    "okkt_schur_batch_reserve": (C.c_int, [_vp, C.c_int64, C.c_int64]),
+    "okkt_schur_batch_release": (C.c_int, [_vp]),
+    "okkt_factor_schur_batch": (C.c_int, [_vp, C.c_int64, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(OkktInertia),
+                                          C.POINTER(C.c_int32)]),
+    "okkt_factor_schur_batch_dev": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(OkktInertia),
+                                              C.POINTER(C.c_int32)]),
+    "okkt_schur_batch_get": (C.c_int, [_vp, C.c_int64, _f64p, C.c_int64]),
+    "okkt_schur_batch_get_dev": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64]),
+    "okkt_schur_batch_factor": (C.c_int, [_vp, _f64p, C.c_int64, C.POINTER(OkktInertia), C.POINTER(OkktInertia)]),
+    "okkt_schur_batch_factor_dev": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(OkktInertia), C.POINTER(OkktInertia)]),
+    "okkt_schur_batch_condense": (C.c_int, [_vp, C.c_int64, _f64p, _f64p, _f64p, C.c_int64]),
+    "okkt_schur_batch_condense_dev": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
+    "okkt_schur_batch_expand": (C.c_int, [_vp, C.c_int64, _f64p, _f64p, _f64p, C.c_int64]),
+    "okkt_schur_batch_expand_dev": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
+    "okkt_schur_batch_solve": (C.c_int, [_vp, C.c_int64, _f64p, _f64p, _f64p, C.c_int64]),
+    "okkt_schur_batch_solve_dev": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
+    "okkt_schur_batch_select": (C.c_int, [_vp, C.c_int64]),
     "okkt_set_scaling": (C.c_int, [_vp, C.c_int, C.c_int32, _f64p]),
     "okkt_get_scaling": (C.c_int, [_vp, _f64p, C.POINTER(OkktScalingInfo)]),
     "okkt_get_scaling_dev": (C.c_int, [_vp, _vp]),

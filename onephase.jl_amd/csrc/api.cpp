@@ -230,6 +230,7 @@ void solver_refine_release(okkt_solver_s* h) {
   sparse_release(h->sp);
   eigs_release(h->eg);
   batch_free(h->bt);
+  schur_batch_free(h->sb);
   krylov_release(h->kr);
   dense_ldlt_release(h->dl);
   scaling_release(h->sc);
@@ -521,7 +522,7 @@ int okkt_analyze(okkt_handle h, int64_t dim, const int64_t* colptr, const int64_
     if (h->opts.ordering == 2 && (int64_t)h->user_perm.size() != dim)
       return solver_set_error(h, OKKT_ERR_INVALID, "ordering=user: okkt_set_perm must supply dim entries first");
     auto t0 = std::chrono::steady_clock::now();
-    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned || h->kr.V || h->dl.F || h->sc.ready || h->pv.planned || h->sp.copied || h->bt.s.arena)) {   // the refinement map (and Z) belong to the old pattern
+    if (h->device_ready && (h->rf.ready || h->rf_work || h->rf_om || h->cd.X || h->sl.planned || h->kr.V || h->dl.F || h->sc.ready || h->pv.planned || h->sp.copied || h->bt.s.arena || h->sb.w.s.arena)) {   // the refinement map (and Z) belong to the old pattern
       (void)hipSetDevice(h->device);
       (void)hipStreamSynchronize(h->stream);
       solver_refine_release(h);

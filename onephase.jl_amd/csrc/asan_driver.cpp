@@ -19,6 +19,7 @@
 #include "pivots.h"
 #include "solve_sparse.h"
 #include "batch.h"
+#include "batch_schur.h"
 #include "../../include/okkt.h"
 #include "sym_eig.h"
 #include "symbolic.h"
@@ -363,6 +364,27 @@ static int run(const char* name, int n, const std::set<std::pair<int, int>>& e, 
     ok = ok && batch_slot_doubles(S, S.arena_doubles, 4) - batch_slot_doubles(S, S.arena_doubles, 1) == 3 * (2 * S.n + S.sum_r) &&
          batch_arena_stride(S, S.arena_doubles) % 2 == 0 && batch_arena_stride(S, S.arena_doubles) >= S.arena_doubles + 512 + 2 * S.max_front;
     if (!ok) { fprintf(stderr, "%s (ordering %d): the grids of a batch do not hold every task once\n", name, ordering); return 1; }
+  }
+  // the grids of a scenario batch (batch_host.cpp): without a set the plan is refused for that; with the last three variables held back the
+  // Schur front is the last supernode and in no level -- with a limit that every interior front passes every interior unit is a task, one row
+  // less and the interior is refused, and a set above the bound of the assembly is refused behind the interior's fronts
+  if (n > 8) {
+    SchurBatchShape Q;
+    schur_batch_shape(S, (int)S.max_front, Q);
+    bool ok = Q.reason == OKKT_SBATCH_NO_SET && Q.tasks == 0;
+    const int64_t idx[3] = {n - 3, n - 2, n - 1};
+    Symbolic T;
+    const std::string e2 = analyze_pattern(n, cp.data(), ri.data(), 0, o, nullptr, T, idx, 3);
+    if (!e2.empty()) { fprintf(stderr, "%s (ordering %d), Schur set: %s\n", name, ordering, e2.c_str()); return 1; }
+    int maxf = 0;
+    for (int s = 0; s + 1 < T.nsuper; ++s) maxf = std::max(maxf, (int)(T.row_ptr[s + 1] - T.row_ptr[s]));
+    SchurBatchShape A, C;
+    schur_batch_shape(T, maxf, A);
+    schur_batch_shape(T, maxf - 1, C);
+    ok = ok && T.nschur == 3 && A.reason == OKKT_SBATCH_OK && A.ns == 3 && A.max_front == maxf && A.levels >= 1 && A.tasks >= A.levels && A.tasks <= T.nsuper - 1;
+    ok = ok && C.reason == OKKT_SBATCH_BIG_FRONTS && C.tasks == 0 && C.levels == 0;
+    ok = ok && schur_batch_item_doubles(3, 4) == 12 + 1 && schur_batch_shared_doubles(3) >= 2 * 9;
+    if (!ok) { fprintf(stderr, "%s (ordering %d): the grids of a scenario batch are miscounted\n", name, ordering); return 1; }
   }
   printf("%-12s ordering %d: n %d nnz(L) %lld supernodes %zu, %zu dataflow tasks\n", name, ordering, n, (long long)S.nnzL, S.sn_col0.size() - 1, ntask);
   return 0;

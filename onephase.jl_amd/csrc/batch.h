@@ -78,5 +78,11 @@ std::string batch_factor_enqueue(Numeric& N, BatchWork& W, int mode, int64_t B, 
 std::string batch_solve_enqueue(Numeric& N, BatchWork& W, int mode, int64_t B, const double* d_rhs, double* d_sol, int64_t nrhs, int64_t r0,
                                 int nr, int R);
 std::string batch_select_enqueue(Numeric& N, BatchWork& W, int64_t b);
+// the parts of a level-mode solve, for callers that put work of their own between the sweeps (batch_schur.hip): xwork <- rhs, the levels
+// upwards, the levels downwards, sol <- xwork
+std::string batch_permute_in_enqueue(Numeric& N, BatchWork& W, int64_t B, const double* d_rhs, int64_t nrhs, int64_t r0, int nr, int R);
+std::string batch_fwd_enqueue(Numeric& N, BatchWork& W, int64_t B, int R);
+std::string batch_bwd_enqueue(Numeric& N, BatchWork& W, int64_t B, int R);
+std::string batch_permute_out_enqueue(Numeric& N, BatchWork& W, int64_t B, double* d_sol, int64_t nrhs, int64_t r0, int nr, int R);
 
 }  // namespace okkt

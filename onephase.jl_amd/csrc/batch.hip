@@ -462,13 +462,78 @@ std::string batch_factor_enqueue(Numeric& N, BatchWork& W, int mode, int64_t B, 
   return "";
 }
 
+// level mode in its parts (the scenario batches of batch_schur.hip put the dense solve between the two sweeps): the gather of the
+// right-hand sides, the levels upwards, the levels downwards, the scatter of the solutions
+template <int R>
+static void permute_in_r(Numeric& N, BatchWork& W, int64_t B, const double* d_rhs, int64_t nrhs, int64_t r0, int nr) {
+  const int n = (int)W.s.n;
+  hipLaunchKernelGGL(k_batch_permute_in<R>, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, N.stream, W.s, n, N.d.perm, d_rhs, nrhs, r0, nr);
+}
+template <int R>
+static void permute_out_r(Numeric& N, BatchWork& W, int64_t B, double* d_sol, int64_t nrhs, int64_t r0, int nr) {
+  const int n = (int)W.s.n;
+  hipLaunchKernelGGL(k_batch_permute_out<R>, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, N.stream, W.s, n, N.d.perm, d_sol, nrhs, r0, nr);
+}
+template <int R>
+static void fwd_r(Numeric& N, BatchWork& W, int64_t B) {
+  const DevPlan P = N.d;
+  hipStream_t st = N.stream;
+  const std::vector<LevelRun> runs = level_runs(N);
+  for (size_t l = 0; l < runs.size(); ++l) {      // forward: the levels upwards
+    const LevelRun& r = runs[l];
+    const size_t lds = (size_t)R * r.maxf * sizeof(double);
+    if (r.maxf <= 32) hipLaunchKernelGGL((k_batch_fs<64, R>), dim3(r.cnt, (unsigned)B), dim3(64), lds, st, P, W.s, P.sched + r.off, r.maxf);
+    else hipLaunchKernelGGL((k_batch_fs<256, R>), dim3(r.cnt, (unsigned)B), dim3(256), lds, st, P, W.s, P.sched + r.off, r.maxf);
+  }
+}
+template <int R>
+static void bwd_r(Numeric& N, BatchWork& W, int64_t B) {
+  const DevPlan P = N.d;
+  hipStream_t st = N.stream;
+  const std::vector<LevelRun> runs = level_runs(N);
+  for (size_t l = runs.size(); l-- > 0;) {        // backward: downwards
+    const LevelRun& r = runs[l];
+    const size_t lds = (size_t)R * r.maxf * sizeof(double);
+    if (r.maxf <= 32) hipLaunchKernelGGL((k_batch_bs<64, R>), dim3(r.cnt, (unsigned)B), dim3(64), lds, st, P, W.s, P.sched + r.off, r.maxf);
+    else hipLaunchKernelGGL((k_batch_bs<256, R>), dim3(r.cnt, (unsigned)B), dim3(256), lds, st, P, W.s, P.sched + r.off, r.maxf);
+  }
+}
+
+#define OKKT_BATCH_BY_R(fn, ...)            \
+  do {                                      \
+    if (R == 1) fn<1>(__VA_ARGS__);         \
+    else if (R == 2) fn<2>(__VA_ARGS__);    \
+    else fn<4>(__VA_ARGS__);                \
+  } while (0)
+
+std::string batch_permute_in_enqueue(Numeric& N, BatchWork& W, int64_t B, const double* d_rhs, int64_t nrhs, int64_t r0, int nr, int R) {
+  if (W.s.n > 0) OKKT_BATCH_BY_R(permute_in_r, N, W, B, d_rhs, nrhs, r0, nr);
+  OKKT_HIP_TRY(hipGetLastError());
+  return "";
+}
+std::string batch_permute_out_enqueue(Numeric& N, BatchWork& W, int64_t B, double* d_sol, int64_t nrhs, int64_t r0, int nr, int R) {
+  if (W.s.n > 0) OKKT_BATCH_BY_R(permute_out_r, N, W, B, d_sol, nrhs, r0, nr);
+  OKKT_HIP_TRY(hipGetLastError());
+  return "";
+}
+std::string batch_fwd_enqueue(Numeric& N, BatchWork& W, int64_t B, int R) {
+  OKKT_BATCH_BY_R(fwd_r, N, W, B);
+  OKKT_HIP_TRY(hipGetLastError());
+  return "";
+}
+std::string batch_bwd_enqueue(Numeric& N, BatchWork& W, int64_t B, int R) {
+  OKKT_BATCH_BY_R(bwd_r, N, W, B);
+  OKKT_HIP_TRY(hipGetLastError());
+  return "";
+}
+
 template <int R>
 static std::string solve_enqueue_r(Numeric& N, BatchWork& W, int mode, int64_t B, const double* d_rhs, double* d_sol, int64_t nrhs, int64_t r0, int nr) {
   const DevPlan P = N.d;
   hipStream_t st = N.stream;
   const int n = (int)W.s.n;
-  const std::vector<LevelRun> runs = level_runs(N);
   if (mode == OKKT_BATCH_ITEM) {
+    const std::vector<LevelRun> runs = level_runs(N);
     int maxf = 1, ntasks = 0;
     for (const LevelRun& r : runs) { maxf = std::max(maxf, r.maxf); ntasks += r.cnt; }
     const int* list = runs.empty() ? P.sched : P.sched + runs[0].off;
@@ -476,21 +541,10 @@ static std::string solve_enqueue_r(Numeric& N, BatchWork& W, int mode, int64_t B
     if (maxf <= 32) hipLaunchKernelGGL((k_batch_item_solve<64, R>), dim3((unsigned)B), dim3(64), lds, st, P, W.s, list, ntasks, maxf, d_rhs, d_sol, nrhs, r0, nr);
     else hipLaunchKernelGGL((k_batch_item_solve<256, R>), dim3((unsigned)B), dim3(256), lds, st, P, W.s, list, ntasks, maxf, d_rhs, d_sol, nrhs, r0, nr);
   } else if (n > 0) {
-    const dim3 pg((unsigned)((n + 255) / 256), (unsigned)B);
-    hipLaunchKernelGGL(k_batch_permute_in<R>, pg, dim3(256), 0, st, W.s, n, P.perm, d_rhs, nrhs, r0, nr);
-    for (size_t l = 0; l < runs.size(); ++l) {      // forward: the levels upwards
-      const LevelRun& r = runs[l];
-      const size_t lds = (size_t)R * r.maxf * sizeof(double);
-      if (r.maxf <= 32) hipLaunchKernelGGL((k_batch_fs<64, R>), dim3(r.cnt, (unsigned)B), dim3(64), lds, st, P, W.s, P.sched + r.off, r.maxf);
-      else hipLaunchKernelGGL((k_batch_fs<256, R>), dim3(r.cnt, (unsigned)B), dim3(256), lds, st, P, W.s, P.sched + r.off, r.maxf);
-    }
-    for (size_t l = runs.size(); l-- > 0;) {        // backward: downwards
-      const LevelRun& r = runs[l];
-      const size_t lds = (size_t)R * r.maxf * sizeof(double);
-      if (r.maxf <= 32) hipLaunchKernelGGL((k_batch_bs<64, R>), dim3(r.cnt, (unsigned)B), dim3(64), lds, st, P, W.s, P.sched + r.off, r.maxf);
-      else hipLaunchKernelGGL((k_batch_bs<256, R>), dim3(r.cnt, (unsigned)B), dim3(256), lds, st, P, W.s, P.sched + r.off, r.maxf);
-    }
-    hipLaunchKernelGGL(k_batch_permute_out<R>, pg, dim3(256), 0, st, W.s, n, P.perm, d_sol, nrhs, r0, nr);
+    permute_in_r<R>(N, W, B, d_rhs, nrhs, r0, nr);
+    fwd_r<R>(N, W, B);
+    bwd_r<R>(N, W, B);
+    permute_out_r<R>(N, W, B, d_sol, nrhs, r0, nr);
   }
   OKKT_HIP_TRY(hipGetLastError());
   return "";

@@ -1,6 +1,7 @@
 // Uniform batches, host side: the grids of a batch from the analysed pattern alone -- what okkt_batch_query
 // answers, also on handles without a device, and what the sanitizer driver runs.
 #include "batch.h"
+#include "batch_schur.h"
 
 #include "../../include/okkt.h"
 #include "solve_sparse.h"
@@ -33,6 +34,33 @@ void batch_shape(const Symbolic& S, int small_max, BatchShape& out) {
 int64_t batch_slot_doubles(const Symbolic& S, int64_t arena_doubles, int R) {
   // arena, D, shift, x and z of the sweeps, contribution vectors, one line of counters
   return batch_arena_stride(S, arena_doubles) + 2 * S.n + (int64_t)R * (2 * S.n + S.sum_r) + 16;
+}
+
+// ---- scenario batches ------------------------------------------------------------------------------------
+void schur_batch_shape(const Symbolic& S, int small_max, SchurBatchShape& out) {
+  out = SchurBatchShape();
+  out.ns = S.nschur;
+  if (S.nschur <= 0) { out.reason = OKKT_SBATCH_NO_SET; return; }
+  const int ns = S.nsuper, schur_sn = ns - 1;      // the Schur front: the last supernode, a unit that no schedule holds
+  for (int s = 0; s < schur_sn; ++s) out.max_front = std::max(out.max_front, (int)(S.row_ptr[s + 1] - S.row_ptr[s]));
+  if (out.max_front > small_max) { out.reason = OKKT_SBATCH_BIG_FRONTS; return; }
+  if (S.nschur > kSchurBatchMaxSet) { out.reason = OKKT_SBATCH_SET_TOO_LARGE; return; }
+  FrontUnits U;
+  form_front_units(S, small_max, U);
+  for (int s = 0; s < schur_sn; ++s) {
+    if (U.unit_root[s] != s) continue;
+    out.levels = std::max(out.levels, U.ulevel[s] + 1);
+    ++out.tasks;
+  }
+}
+
+int64_t schur_batch_item_doubles(int64_t ns, int R) {
+  return (int64_t)R * ns + (ns * ns + 4 * ns + kSchurBatchGroup - 1) / kSchurBatchGroup;
+}
+
+int64_t schur_batch_shared_doubles(int64_t ns) {
+  // the sum, r2 / x2; the dense factor: F, the panel W, the solves' vectors X, the pivot arrays (three ints per column)
+  return ns * ns + 4 * ns + ns * ns + ns * kDlNB + 12 * ns + 2 * ns;
 }
 
 }  // namespace okkt

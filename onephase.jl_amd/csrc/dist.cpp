@@ -49,6 +49,7 @@ int okkt_dist_set_partition(okkt_handle h, int nparts, int part_id) {
     numeric_release(h->N);
     h->numeric_ready = false;
     batch_free(h->bt);      // the slots of a uniform batch were laid out for the released plan
+    schur_batch_free(h->sb);
   }
   if (nparts > 1 && h->S.max_front > kPartedMaxFront) return solver_set_error(h, OKKT_ERR_INVALID, parted_front_error(h->S.max_front));
   h->factored = false;

@@ -187,6 +187,8 @@ __device__ __forceinline__ int lower_bound_dev(const int* a, int n, int key) {
 #endif
 constexpr int kAsmBatch = OKKT_ASM_BATCH, kAsmBatchChunked = OKKT_ASM_BATCH_CHUNKED;
 constexpr int kAsmUnroll = OKKT_ASM_UNROLL;      // 64-row groups of an item whose index and value loads are in flight together (round 6: 8 instead of 4 is SLOWER -- S-metric 17.3 against 17.1 ms, S-C5 3.95 / 3.87: the registers cost waves, and waves are what hides the latency here)
+// (k_batch_schur_assemble of batch_schur.hip holds a COPY of the <true, true> form and of the LDS branch of k_big_assemble<true> below, with
+// the values, the shift and the arena of a batch item: a change to either must be made to both -- tests/test_gpu_schur_batch.py compares S bit for bit)
 template <bool LDS, bool BATCH>
 __device__ __forceinline__ void assemble_column(const DevPlan& P, int s, int pc, int f, int k, int col0, double* __restrict__ buf) {
   const int lane = threadIdx.x & 63;

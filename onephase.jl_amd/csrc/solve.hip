@@ -73,6 +73,8 @@ __device__ __forceinline__ void xblock(int k, int b, int& c0, int& kb, int& ld, 
 
 // forward right-hand-side entry of front row r (before any block of this front has been applied): the permuted rhs on the
 // pivot rows plus the children's contribution vectors through the inverted extend-add lists (fixed order)
+// (k_batch_schur_gather of batch_schur.hip holds a COPY of this body with the sweep vectors of a batch item: a change to either must be made
+// to both -- tests/test_gpu_schur_batch.py compares r2 bit for bit)
 template <int R>
 __device__ __forceinline__ void fwd_gather(const DevPlan& P, int64_t gcb, int col0, int k, int r, double (&w)[R]) {
 #pragma unroll

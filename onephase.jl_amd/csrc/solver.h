@@ -7,6 +7,7 @@
 
 #include "../../include/okkt.h"
 #include "batch.h"
+#include "batch_schur.h"
 #include "condest.h"
 #include "dense_ldlt.h"
 #include "eigs.h"
@@ -99,6 +100,9 @@ struct okkt_solver_s {
   // uniform batches (batch.hip): the items' slots, allocated by okkt_batch_reserve and released by okkt_batch_release
   // and with the refinement map
   okkt::BatchWork bt;
+  // scenario batches (batch_schur.hip): B items in Schur mode on one pattern -- their slots, the sum buffers and a
+  // dense factor of their own; allocated by okkt_schur_batch_reserve, released by okkt_schur_batch_release and with the refinement map
+  okkt::SchurBatchWork sb;
 };
 
 namespace okkt {

@@ -500,6 +500,103 @@ function batch_select(solver::linear_solver_HIP, b::Integer)
     rc < 0 && okkt_error(solver, "okkt_batch_select", rc)
 end
 
+# Scenario batches (DESIGN.md section 8.16): B items in Schur mode on the analysed pattern [[A11 A12]; [A21 A22]], their S_b summed on the
+# device in the order okkt.h states, one dense factor of the sum: the arrowhead system of B blocks.  The handle is in Schur mode
+# (okkt_set_schur before the analysis).  Not part of the reference interface.  okkt_schur_batch_info of include/okkt.h
+struct OkktSchurBatchInfo
+    eligible::Int32; reason::Int32
+    ns::Int64
+    bytes_per_item::Int64; bytes_shared::Int64
+    tasks_per_item::Int64
+    levels::Int32; max_front::Int32
+    launches_factor::Int32; launches_solve::Int32
+end
+
+function schur_batch_query(solver::linear_solver_HIP; nrhs_max::Integer=1)
+    info = Ref(OkktSchurBatchInfo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    rc = ccall((:okkt_schur_batch_query, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Ref{OkktSchurBatchInfo}), solver.handle, nrhs_max, info)
+    rc < 0 && okkt_error(solver, "okkt_schur_batch_query", rc)
+    return info[]
+end
+
+function schur_batch_reserve(solver::linear_solver_HIP, B::Integer; nrhs_max::Integer=1)
+    rc = ccall((:okkt_schur_batch_reserve, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Int64), solver.handle, B, nrhs_max)
+    rc < 0 && okkt_error(solver, "okkt_schur_batch_reserve", rc)
+end
+
+function schur_batch_release(solver::linear_solver_HIP)
+    rc = ccall((:okkt_schur_batch_release, OKKT_LIB), Cint, (Ptr{Cvoid},), solver.handle)
+    rc < 0 && okkt_error(solver, "okkt_schur_batch_release", rc)
+end
+
+# vals: nnz x B (one column per item); n1 + m1 = dim - ns; shifts[b] is added to the first nshift (default n1) diagonal entries.
+# Returns the items' flags and the inertia counts of their A11 (4 x B: pos, neg, zero, nonfinite)
+function ls_factor_schur_batch(solver::linear_solver_HIP, vals::Matrix{Float64}, n1::Int64, m1::Int64;
+                               shifts::Union{Nothing,Vector{Float64}}=nothing, nshift::Int64=n1)
+    B = size(vals, 2)
+    inertia = zeros(Int64, 4, B); flags = zeros(Int32, B)
+    kind = solver.sym == :definite ? 0 : 1
+    rc = ccall((:okkt_factor_schur_batch, OKKT_LIB), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Int64, Cint, Ptr{Int64}, Ptr{Int32}),
+               solver.handle, B, vals, size(vals, 1), shifts === nothing ? C_NULL : shifts, nshift, n1, m1, kind, inertia, flags)
+    rc < 0 && okkt_error(solver, "okkt_factor_schur_batch", rc)
+    return flags, inertia
+end
+
+# S_b of item b (1-based), or the sum of the items' S_b for b = 0: ns x ns, symmetric, in the order of the set
+function schur_batch(solver::linear_solver_HIP, b::Integer=0)
+    ns = schur_batch_query(solver).ns
+    S = zeros(Float64, ns, ns)
+    rc = ccall((:okkt_schur_batch_get, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64), solver.handle, b - 1, S, ns)
+    rc < 0 && okkt_error(solver, "okkt_schur_batch_get", rc)
+    return S
+end
+
+# dense factor of sum_b S_b (+ S_add, added last): (flag, inertia of the sum, inertia of the arrowhead matrix), counts as (pos, neg, zero, nonfinite)
+function schur_batch_factor(solver::linear_solver_HIP; S_add::Union{Nothing,Matrix{Float64}}=nothing)
+    si = zeros(Int64, 4); ti = zeros(Int64, 4)
+    rc = ccall((:okkt_schur_batch_factor, OKKT_LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}),
+               solver.handle, S_add === nothing ? C_NULL : S_add, S_add === nothing ? 0 : size(S_add, 1), si, ti)
+    rc < 0 && okkt_error(solver, "okkt_schur_batch_factor", rc)
+    return rc, si, ti
+end
+
+# rhs: dim x nrhs x B -> (the summed r2: ns x nrhs, the items' r2_b: ns x nrhs x B)
+function schur_batch_condense(solver::linear_solver_HIP, rhs::Array{Float64,3})
+    ns = schur_batch_query(solver).ns
+    nrhs = size(rhs, 2); B = size(rhs, 3)
+    r2 = zeros(Float64, ns, nrhs); items = zeros(Float64, ns, nrhs, B)
+    rc = ccall((:okkt_schur_batch_condense, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
+               solver.handle, B, rhs, r2, items, nrhs)
+    rc < 0 && okkt_error(solver, "okkt_schur_batch_condense", rc)
+    return r2, items
+end
+
+# the one x2 (ns x nrhs) put into every item: the items' solutions, dim x nrhs x B
+function schur_batch_expand(solver::linear_solver_HIP, rhs::Array{Float64,3}, x2::Matrix{Float64})
+    sol = similar(rhs)
+    rc = ccall((:okkt_schur_batch_expand, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
+               solver.handle, size(rhs, 3), rhs, x2, sol, size(rhs, 2))
+    rc < 0 && okkt_error(solver, "okkt_schur_batch_expand", rc)
+    return sol
+end
+
+# the arrowhead system: rhs dim x nrhs x B (the entries at the set are the items' shares of the linking right-hand side), rhs0 (ns x nrhs)
+# added to their sum last; the solutions in the shape of rhs, x_L at the set in every item
+function schur_batch_solve(solver::linear_solver_HIP, rhs::Array{Float64,3}; rhs0::Union{Nothing,Matrix{Float64}}=nothing)
+    sol = similar(rhs)
+    rc = ccall((:okkt_schur_batch_solve, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
+               solver.handle, size(rhs, 3), rhs, rhs0 === nothing ? C_NULL : rhs0, sol, size(rhs, 2))
+    rc < 0 && okkt_error(solver, "okkt_schur_batch_solve", rc)
+    return sol
+end
+
+# slot b (1-based) becomes the handle's own state, as after okkt_factor_schur of that item
+function schur_batch_select(solver::linear_solver_HIP, b::Integer)
+    rc = ccall((:okkt_schur_batch_select, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64), solver.handle, b - 1)
+    rc < 0 && okkt_error(solver, "okkt_schur_batch_select", rc)
+end
+
 # ls_solve_refine! through the Schur route: every solve is okkt_schur_solve's, the residuals are against the whole A.  Needs
 # okkt_factor_schur and okkt_schur_factor of the handle's own S.
 function schur_solve_refine!(solver::linear_solver_HIP, A::SparseMatrixCSC{Float64,Int64}, my_rhs::Array{Float64,1}, my_sol::Array{Float64,1};

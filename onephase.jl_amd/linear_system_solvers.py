@@ -633,6 +633,138 @@ class linear_solver_HIP(abstract_linear_system_solver):
         self._need()
         self._check(self._lib.okkt_schur_solve_dev(self._h, C.c_void_p(d_rhs), C.c_void_p(d_sol), int(nrhs)), "okkt_schur_solve_dev")
 
+    # -- scenario batches: B items in Schur mode on one pattern, their S summed on the device
+    def schur_batch_query(self, nrhs_max=1):
+        """Whether the analysed plan takes a scenario batch, and what one costs: dict of okkt_schur_batch_info (host only)."""
+        self._need()
+        info = L.OkktSchurBatchInfo()
+        self._check(self._lib.okkt_schur_batch_query(self._h, int(nrhs_max), C.byref(info)), "okkt_schur_batch_query")
+        return info.as_dict()
+
+    def schur_batch_reserve(self, B, nrhs_max=1):
+        """Slots for B items, the sum buffers and the batch's own dense factor; solve work for nrhs_max columns."""
+        self._need()
+        self._check(self._lib.okkt_schur_batch_reserve(self._h, int(B), int(nrhs_max)), "okkt_schur_batch_reserve")
+
+    def schur_batch_release(self):
+        self._need()
+        self._check(self._lib.okkt_schur_batch_release(self._h), "okkt_schur_batch_release")
+
+    def _schur_batch_factor_items(self, fn, what, B, vals, stride, shifts, nshift, n1, m1):
+        sh = None if shifts is None else L.f64(shifts).ravel()
+        if sh is not None and sh.size != B:
+            raise OkktError("shifts must have one entry per item")
+        inert = (L.OkktInertia * B)()
+        flags = np.zeros(B, dtype=np.int32)
+        self._check(fn(self._h, B, vals, stride, None if sh is None else L.p_f64(sh), int(nshift), int(n1), int(m1), self._kind(), inert,
+                       flags.ctypes.data_as(C.POINTER(C.c_int32))), what)
+        self.schur_batch_inertia = [it.as_tuple() for it in inert]
+        return flags
+
+    def ls_factor_schur_batch(self, vals, n1, m1, shifts=None, nshift=None):
+        """Factor A11 of every item and assemble its S_b.  vals: [B, nnz], one row per item, in the analysed order; n1 + m1 = dim - ns;
+        shifts[b] is added to the first nshift (default n1) diagonal entries.  Returns the items' flags (1: inertia (n1, m1, 0) of
+        A11_b); the counts are left in self.schur_batch_inertia."""
+        self._need()
+        v = L.f64(vals)
+        if v.ndim != 2:
+            raise OkktError("vals must be [B, nnz]")
+        return self._schur_batch_factor_items(self._lib.okkt_factor_schur_batch, "okkt_factor_schur_batch", v.shape[0], L.p_f64(v), v.shape[1], shifts,
+                                              n1 if nshift is None else nshift, n1, m1)
+
+    def ls_factor_schur_batch_dev(self, d_nzval, B, val_stride, n1, m1, shifts=None, nshift=None):
+        self._need()
+        return self._schur_batch_factor_items(self._lib.okkt_factor_schur_batch_dev, "okkt_factor_schur_batch_dev", int(B), C.c_void_p(d_nzval),
+                                              int(val_stride), shifts, n1 if nshift is None else nshift, n1, m1)
+
+    def schur_batch(self, b=-1):
+        """S_b of item b, or (b = -1) the sum of the items' S_b in the order the header states: dense symmetric ns x ns."""
+        self._need()
+        ns = self._ns
+        S = np.zeros((ns, ns))
+        self._check(self._lib.okkt_schur_batch_get(self._h, int(b), L.p_f64(S), ns), "okkt_schur_batch_get")
+        return S
+
+    def schur_batch_dev(self, d_S, ld, b=-1):
+        self._need()
+        self._check(self._lib.okkt_schur_batch_get_dev(self._h, int(b), C.c_void_p(d_S), int(ld)), "okkt_schur_batch_get_dev")
+
+    def schur_batch_factor(self, S_add=None):
+        """Dense factor of sum_b S_b (+ S_add, symmetric ns x ns, added last).  1 when no pivot is zero or non-finite, else 0; sets
+        schur_inertia (the sum's counts) and total_inertia (the items' A11 counts + the sum's: the arrowhead matrix's)."""
+        if S_add is None:
+            return self._schur_factor(self._lib.okkt_schur_batch_factor, "okkt_schur_batch_factor", None, self._ns)
+        A = L.f64(np.asarray(S_add, dtype=np.float64).T)
+        if A.shape != (self._ns, self._ns):
+            raise OkktError(f"S_add must be {self._ns} x {self._ns}")
+        return self._schur_factor(self._lib.okkt_schur_batch_factor, "okkt_schur_batch_factor", L.p_f64(A), self._ns)
+
+    def schur_batch_factor_dev(self, d_S_add=None, ld=None):
+        return self._schur_factor(self._lib.okkt_schur_batch_factor_dev, "okkt_schur_batch_factor_dev", None if d_S_add is None else C.c_void_p(d_S_add),
+                                  self._ns if ld is None else ld)
+
+    def _sb_rhs(self, rhs):
+        b = L.f64(rhs)
+        if b.ndim not in (2, 3) or b.shape[-1] != self._dim:
+            raise OkktError("rhs must be [B, dim] or [B, nrhs, dim] of the analysed dimension")
+        return b, (1 if b.ndim == 2 else b.shape[1])
+
+    def schur_batch_condense(self, rhs, items=False):
+        """rhs [B, dim] or [B, nrhs, dim] -> the summed r2 ([ns] or [nrhs, ns]); items: also the items' r2_b ([B, ns] or [B, nrhs, ns])."""
+        self._need()
+        b, nrhs = self._sb_rhs(rhs)
+        B, ns = b.shape[0], self._ns
+        r2 = np.zeros((nrhs, ns))
+        ri = np.zeros((B, nrhs, ns)) if items else None
+        self._check(self._lib.okkt_schur_batch_condense(self._h, B, L.p_f64(b), L.p_f64(r2), None if ri is None else L.p_f64(ri), nrhs),
+                    "okkt_schur_batch_condense")
+        if b.ndim == 2:
+            r2 = r2[0]
+            ri = None if ri is None else ri[:, 0]
+        return (r2, ri) if items else r2
+
+    def schur_batch_condense_dev(self, d_rhs, d_r2_sum, B, nrhs=1, d_r2_items=None):
+        self._need()
+        self._check(self._lib.okkt_schur_batch_condense_dev(self._h, int(B), C.c_void_p(d_rhs), C.c_void_p(d_r2_sum),
+                                                            None if d_r2_items is None else C.c_void_p(d_r2_items), int(nrhs)), "okkt_schur_batch_condense_dev")
+
+    def schur_batch_expand(self, rhs, x2):
+        """The one x2 ([ns] or [nrhs, ns]) put into every item: x_b = A11_b^-1 (b_b - A12_b x2), x[b][idx] = x2; same shape as rhs."""
+        self._need()
+        b, nrhs = self._sb_rhs(rhs)
+        X2 = L.f64(np.asarray(x2, dtype=np.float64).reshape(nrhs, self._ns))
+        out = np.empty_like(b)
+        self._check(self._lib.okkt_schur_batch_expand(self._h, b.shape[0], L.p_f64(b), L.p_f64(X2), L.p_f64(out), nrhs), "okkt_schur_batch_expand")
+        return out
+
+    def schur_batch_expand_dev(self, d_rhs, d_x2, d_sol, B, nrhs=1):
+        self._need()
+        self._check(self._lib.okkt_schur_batch_expand_dev(self._h, int(B), C.c_void_p(d_rhs), C.c_void_p(d_x2), C.c_void_p(d_sol), int(nrhs)),
+                    "okkt_schur_batch_expand_dev")
+
+    def schur_batch_solve(self, rhs, rhs0=None):
+        """The arrowhead system: rhs [B, dim] or [B, nrhs, dim] (the entries at idx are the items' shares of the linking right-hand side),
+        rhs0 ([ns] or [nrhs, ns]) added to their sum last.  Returns the solutions, same shape; [b][idx] is x_L in every item."""
+        self._need()
+        b, nrhs = self._sb_rhs(rhs)
+        r0 = None if rhs0 is None else L.f64(np.asarray(rhs0, dtype=np.float64).reshape(nrhs, self._ns))
+        out = np.empty_like(b)
+        self._check(self._lib.okkt_schur_batch_solve(self._h, b.shape[0], L.p_f64(b), None if r0 is None else L.p_f64(r0), L.p_f64(out), nrhs),
+                    "okkt_schur_batch_solve")
+        return out
+
+    def schur_batch_solve_dev(self, d_rhs, d_sol, B, nrhs=1, d_rhs0=None):
+        self._need()
+        self._check(self._lib.okkt_schur_batch_solve_dev(self._h, int(B), C.c_void_p(d_rhs), None if d_rhs0 is None else C.c_void_p(d_rhs0),
+                                                         C.c_void_p(d_sol), int(nrhs)), "okkt_schur_batch_solve_dev")
+
+    def schur_batch_select(self, b):
+        """Slot b becomes the handle's own state: every other call then behaves as after ls_factor_schur of that item."""
+        self._need()
+        self._check(self._lib.okkt_schur_batch_select(self._h, int(b)), "okkt_schur_batch_select")
+        if getattr(self, "schur_batch_inertia", None) and 0 <= b < len(self.schur_batch_inertia):
+            self.inertia = self.schur_batch_inertia[b]
+
     def schur_get_factor(self):
         """(LD, ipiv) as LAPACK's dsytrf(lower) returns them: LD[i, j] with unit L below the diagonal and D on it, ipiv 1-based with
         negative pairs for the 2 x 2 blocks."""
