@@ -981,6 +981,75 @@ int okkt_kkt_ipopt_strategy_eig(okkt_kkt_handle k, double delta_prev, const okkt
  * host_symbolic_only handles get OKKT_ERR_NO_DEVICE. */
 int okkt_kkt_ipopt_strategy_batch(okkt_kkt_handle k, double delta_prev, const okkt_kkt_pars* pars, int32_t width,
                                   int32_t* num_fac_out, double* delta_out, int32_t* launches_out);
+/* ---- KKT batches: form, delta-correct and solve B iterates on one structure ----
+ * B iterates (H_b, J_b, s_b, y_b, grad_b, cons_b) share the structure of the handle; every one gets a slot of its own in HBM (its
+ * values, Sigma, the assembled matrix, the resident rhs and direction, work vectors; index arrays are never duplicated) and a slot of
+ * the linear solver's uniform batch.  One rule for every item: its observable results -- diag_min; status, number of factorisations,
+ * delta and diagonal-dominance warnings of the delta loop; inertia and flag; the rhs triple; dx, dy, ds and the six numbers of
+ * okkt_kkt_error -- are bit for bit those of okkt_kkt_form_system, okkt_kkt_diag_min, okkt_kkt_factor / okkt_kkt_ipopt_strategy,
+ * okkt_kkt_system_rhs (J_nzval_cur = NULL) and okkt_kkt_compute_direction (resident rhs) for that iterate on a handle of its own.
+ * (okkt_kkt_ipopt_strategy_batch batches the delta CANDIDATES of one iterate; this family batches iterates.)
+ * Strides: H_stride / J_stride = 0: every item reads the same array; otherwise >= the number of entries.  s, y, grad, cons, the rhs
+ * triple and dx, dy, ds are [B][m] / [B][n], items contiguous.
+ * okkt_kkt_items_ipopt_strategy: tau_b, the first attempt and the sequence come from diag_min_b and delta_prev[b] as in
+ * okkt_kkt_ipopt_strategy; in every round each item still active makes its next attempt, and a round is ONE batched factorisation over
+ * the active items only.  An item leaves at its first success (status 1) or at its first attempt beyond delta_max (status 0) and keeps
+ * that complete factor in its slot: an item with status 0 still gives a direction, as in the reference (take_step2!).  launches_out is
+ * the number of rounds = max_b num_fac_out[b].  After every failed attempt the scan of okkt_kkt_is_diag_dom runs for the failed items
+ * as batched launches (OKKT_DIAG_DOM_SCAN=0 is honoured).  Batched factorisations are always complete.
+ * okkt_kkt_items_compute_direction: dx = dy = ds = NULL leaves the directions resident.  One host synchronisation per call.
+ * okkt_kkt_items_select(b): slot b -> the handle's own state (the iterate's device arrays, Sigma, schur_diag and the assembled values,
+ * delta, the resident rhs and direction where they exist, the linear solver's slot through okkt_batch_select): afterwards every
+ * single-iterate entry point behaves as after the serial sequence on that iterate.
+ * Scope: the symmetric kind and the Schur kind without dense rows.  okkt_kkt_items_query (host only) gives eligible = 0 with the first
+ * reason that applies, in the order of the codes; OKKT_KKT_ITEMS_PLAN + r passes on reason r of okkt_batch_query.  launches_form /
+ * launches_direction: kernel launches of one form_system / compute_direction (the Schur kind's for the default ItRefine_Num); they do
+ * not depend on B.  bytes_per_item includes the linear solver's slot and counts the values of H and J per item (an upper bound: an
+ * array given with stride 0 is held once).  Every entry point refuses a handle that is not eligible with
+ * OKKT_ERR_INVALID and a message (okkt_kkt_last_error); the handle stays usable and the single-iterate calls are untouched.  Calls out of
+ * order (a direction before a factorisation, a factorisation or a rhs before form_system, B above the reservation) get
+ * OKKT_ERR_INVALID; host_symbolic_only handles OKKT_ERR_NO_DEVICE.  okkt_kkt_items_reserve (B in 1 .. 65535) replaces a previous
+ * reservation and reserves B slots of the linear solver (okkt_batch_reserve); OKKT_ERR_ALLOC with a message when they do not fit.
+ * okkt_kkt_items_release frees the slots of both levels (the linear solver's only while they are still the ones this reservation made:
+ * another okkt_batch_reserve on that handle -- okkt_kkt_ipopt_strategy_batch makes one -- replaces them, and the items calls then ask for
+ * a new reservation).  The structure of a KKT handle is set once (a second okkt_kkt_set_structure is refused and changes nothing), so a
+ * reservation lives until it is released, replaced or the handle is destroyed. */
+#define OKKT_KKT_ITEMS_OK 0
+#define OKKT_KKT_ITEMS_NO_STRUCTURE 1
+#define OKKT_KKT_ITEMS_CLEVER 2
+#define OKKT_KKT_ITEMS_SCHUR_DIRECT 3
+#define OKKT_KKT_ITEMS_DENSE_ROWS 4
+#define OKKT_KKT_ITEMS_SCALING 5
+#define OKKT_KKT_ITEMS_LS_REFINE 6
+#define OKKT_KKT_ITEMS_PLAN 16      /* + the reason of okkt_batch_query */
+typedef struct { int32_t eligible, reason; int64_t bytes_per_item; int32_t launches_form, launches_direction; } okkt_kkt_items_info;
+int okkt_kkt_items_query(okkt_kkt_handle k, okkt_kkt_items_info* out);            /* host only */
+int okkt_kkt_items_reserve(okkt_kkt_handle k, int64_t B);                         /* 1..65535; replaces a previous reservation */
+int okkt_kkt_items_release(okkt_kkt_handle k);
+int okkt_kkt_items_form_system(okkt_kkt_handle k, int64_t B, const double* H_nzval, int64_t H_stride,
+                               const double* J_nzval, int64_t J_stride, const double* s /* [B][m] */, const double* y /* [B][m] */);
+int okkt_kkt_items_diag_min(okkt_kkt_handle k, int64_t B, double* out /* [B] */);
+int okkt_kkt_items_factor(okkt_kkt_handle k, int64_t B, const double* delta /* [B] */, okkt_inertia* inertia_out /* [B] or NULL */,
+                          int32_t* flag_out /* [B] or NULL */);
+int okkt_kkt_items_ipopt_strategy(okkt_kkt_handle k, int64_t B, const double* delta_prev /* [B] */, const okkt_kkt_pars* pars,
+                                  int32_t* status_out /* [B]: 1 success, 0 failure */, int32_t* num_fac_out /* [B] */,
+                                  double* delta_out /* [B] */, int32_t* diag_dom_warnings_out /* [B] or NULL */, int32_t* launches_out);
+int okkt_kkt_items_system_rhs(okkt_kkt_handle k, int64_t B, const double* grad /* [B][n] */, const double* cons /* [B][m] */,
+                              const double* s, const double* y, const double* mu /* [B] */, const double* a_norm_penalty /* [B] */,
+                              double eta_P, double eta_D, double eta_mu,
+                              double* dual_r, double* primal_r, double* comp_r /* [B][..] or NULL */);
+int okkt_kkt_items_compute_direction(okkt_kkt_handle k, int64_t B, int32_t ItRefine_Num,
+                                     double* dx /* [B][n] */, double* dy, double* ds /* [B][m]; three NULLs: stay resident */,
+                                     okkt_kkt_error* err_out /* [B] or NULL */);
+int okkt_kkt_items_select(okkt_kkt_handle k, int64_t b);
+/* Test hook: one batched factorisation of the reserved KKT batch over the item list items[0 .. nitems) (distinct slots below B) with the
+ * shifts delta[slot], as a round of okkt_kkt_items_ipopt_strategy runs it; flag_out [B] is written for the listed slots only. */
+int okkt_debug_kkt_items_factor_list(okkt_kkt_handle k, int64_t B, const int32_t* items, int64_t nitems, const double* delta /* [B] */,
+                                     int32_t* flag_out /* [B] */);
+/* Test hook, host only (no device, no handle): the attempt sequence and the round bookkeeping of okkt_kkt_items_ipopt_strategy
+ * (csrc/kkt_items_seq.h) for B items whose attempt with delta succeeds exactly when delta >= need[b]; outputs as the loop's. */
+int okkt_debug_items_loop_model(int64_t B, const double* diag_min, const double* delta_prev, const double* need, const okkt_kkt_pars* pars,
+                                int32_t* status_out, int32_t* num_fac_out, double* delta_out, int32_t* launches_out);
 /* Test hook, host only (no device, no handle): the tridiagonal solver of okkt_kkt_min_eig (csrc/lanczos_tridiag.h) on
  * T = tridiag(beta[0 .. k-2]; alpha[0 .. k-1]), 1 <= k <= 64.  beta holds k entries: beta[k-1] is the residual coefficient beta_k of
  * the Lanczos recurrence.  Returns theta_min, theta_max, the unit eigenvector s_out [k] of theta_min (largest entry positive) and

@@ -39,6 +39,14 @@ OKKT_BATCH_SCHUR = 3
 OKKT_BATCH_SCALING = 4
 OKKT_BATCH_BIG_FRONTS = 5
 OKKT_BATCH_MODE = {"auto": 0, "level": 1, "item": 2}
+OKKT_KKT_ITEMS_OK = 0
+OKKT_KKT_ITEMS_NO_STRUCTURE = 1
+OKKT_KKT_ITEMS_CLEVER = 2
+OKKT_KKT_ITEMS_SCHUR_DIRECT = 3
+OKKT_KKT_ITEMS_DENSE_ROWS = 4
+OKKT_KKT_ITEMS_SCALING = 5
+OKKT_KKT_ITEMS_LS_REFINE = 6
+OKKT_KKT_ITEMS_PLAN = 16
 # scenario batches: why a plan takes none (okkt_schur_batch_info.reason), and the group size of the sums over the items
 OKKT_SBATCH_OK = 0
 OKKT_SBATCH_NOT_ANALYZED = 1
@@ -285,6 +293,21 @@ class OkktBatchInfo(C.Structure):
         ("launches_solve_level", C.c_int32),
         ("launches_factor_item", C.c_int32),
         ("launches_solve_item", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class OkktKktItemsInfo(C.Structure):
+    """okkt_kkt_items_info: whether the KKT handle takes a batch of iterates (reason: OKKT_KKT_ITEMS_*), the HBM of one item's slot (the
+    linear solver's included), the kernel launches of one batched form_system / compute_direction."""
+    _fields_ = [
+        ("eligible", C.c_int32),
+        ("reason", C.c_int32),
+        ("bytes_per_item", C.c_int64),
+        ("launches_form", C.c_int32),
+        ("launches_direction", C.c_int32),
     ]
 
     def as_dict(self):
@@ -547,6 +570,21 @@ SIGNATURES = {
                                                  C.POINTER(C.c_int32)]),
     "okkt_kkt_ipopt_strategy_eig": (C.c_int, [_vp, C.c_double, C.POINTER(OkktKktPars), C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p,
                                               C.POINTER(C.c_int32), C.POINTER(OkktKktEigInfo)]),
+    "okkt_kkt_items_query": (C.c_int, [_vp, C.POINTER(OkktKktItemsInfo)]),
+    "okkt_kkt_items_reserve": (C.c_int, [_vp, C.c_int64]),
+    "okkt_kkt_items_release": (C.c_int, [_vp]),
+    "okkt_kkt_items_form_system": (C.c_int, [_vp, C.c_int64, _f64p, C.c_int64, _f64p, C.c_int64, _f64p, _f64p]),
+    "okkt_kkt_items_diag_min": (C.c_int, [_vp, C.c_int64, _f64p]),
+    "okkt_kkt_items_factor": (C.c_int, [_vp, C.c_int64, _f64p, C.POINTER(OkktInertia), C.POINTER(C.c_int32)]),
+    "okkt_kkt_items_ipopt_strategy": (C.c_int, [_vp, C.c_int64, _f64p, C.POINTER(OkktKktPars), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f64p,
+                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "okkt_kkt_items_system_rhs": (C.c_int, [_vp, C.c_int64, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, C.c_double, C.c_double, C.c_double,
+                                             _f64p, _f64p, _f64p]),
+    "okkt_kkt_items_compute_direction": (C.c_int, [_vp, C.c_int64, C.c_int32, _f64p, _f64p, _f64p, C.POINTER(OkktKktError)]),
+    "okkt_kkt_items_select": (C.c_int, [_vp, C.c_int64]),
+    "okkt_debug_kkt_items_factor_list": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _f64p, C.POINTER(C.c_int32)]),
+    "okkt_debug_items_loop_model": (C.c_int, [C.c_int64, _f64p, _f64p, _f64p, C.POINTER(OkktKktPars), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                               _f64p, C.POINTER(C.c_int32)]),
     "okkt_debug_tridiag_eig": (C.c_int, [C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]),
     "okkt_kkt_compute_directions": (C.c_int, [_vp, C.c_int32, _f64p, C.c_int32, _f64p, _f64p, _f64p, C.POINTER(OkktKktError)]),
     "okkt_kkt_is_diag_dom": (C.c_int, [_vp, C.POINTER(C.c_int32)]),

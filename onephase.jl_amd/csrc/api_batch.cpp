@@ -73,10 +73,20 @@ int solve_batch_device(okkt_solver_s* h, int64_t B, const double* d_rhs, double*
 namespace okkt {
 
 int solver_factor_batch_device(okkt_solver_s* h, int64_t B, const double* d_vals, int64_t val_stride, const double* shift, int64_t nshift, int64_t n, int64_t m,
-                               int sym_kind, okkt_inertia* inertia_out, int32_t* flag_out, bool zero_tol) {
-  int rc = batch_ready(h, "okkt_factor_batch", B);
+                               int sym_kind, okkt_inertia* inertia_out, int32_t* flag_out, bool zero_tol, const int32_t* items, int64_t nslots) {
+  int rc = batch_ready(h, "okkt_factor_batch", items ? std::max<int64_t>(nslots, 1) : B);
   if (rc != OKKT_OK) return rc;
   BatchWork& W = h->bt;
+  if (items) {
+    // an item list: B distinct slots below nslots; values, shift and the outputs are indexed by slot, the other slots are not touched
+    if (B < 1 || B > nslots) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_factor_batch: the item list must hold 1 .. nslots slots");
+    std::vector<char> seen((size_t)nslots, 0);
+    for (int64_t j = 0; j < B; ++j) {
+      if (items[j] < 0 || items[j] >= nslots || seen[(size_t)items[j]]) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_factor_batch: the item list names a slot twice or one outside the batch");
+      seen[(size_t)items[j]] = 1;
+    }
+  }
+  const int64_t nout = items ? nslots : B;      // entries of shift and of the outputs
   if (h->sc.mode != OKKT_SCALE_NONE) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_factor_batch: a scaling is set (okkt_set_scaling with OKKT_SCALE_NONE first)");
   if (val_stride != 0 && val_stride < h->S.nnz_in) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_factor_batch: val_stride must be 0 or at least the number of entries");
   if (n < 0 || m < 0 || n + m != h->S.n) return solver_set_error(h, OKKT_ERR_INVALID, "n + m does not match the analysed dimension");
@@ -84,21 +94,34 @@ int solver_factor_batch_device(okkt_solver_s* h, int64_t B, const double* d_vals
   if (sym_kind == OKKT_SYM_DEFINITE && m != 0) return solver_set_error(h, OKKT_ERR_INVALID, ":definite requires m == 0 (julia.jl:30)");
   if (nshift < 0 || nshift > h->S.n) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_factor_batch: nshift outside 0 .. dim");
   const double tol = (sym_kind == OKKT_SYM_DEFINITE || zero_tol) ? 0.0 : h->opts.inertia_tol;
-  const int mode = batch_pick_mode(W, h->N, B);
+  // an item list is a level-mode launch (the grid's second coordinate is looked up); a list after a factorisation in item mode would mix
+  // the two, so the list's first use must cover a batch factored in level mode or none
+  const int mode = items ? OKKT_BATCH_LEVEL : batch_pick_mode(W, h->N, B);
+  const int64_t kept_B = items && W.mode_used == OKKT_BATCH_LEVEL && (int64_t)W.flags.size() >= nslots ? W.factored_B : 0;
+  if (items && B < nslots && kept_B < nslots)
+    return solver_set_error(h, OKKT_ERR_INVALID, "okkt_factor_batch: an item list that leaves slots out needs a level-mode factorisation of all of them before it "
+                                                 "(the slots it does not name would hold no factor)");
   W.factored_B = 0;
-  if (shift && (rc = stage_upload(h, W.shift, shift, B, "okkt_factor_batch: shift upload")) != OKKT_OK) return rc;
+  if (shift && (rc = stage_upload(h, W.shift, shift, nout, "okkt_factor_batch: shift upload")) != OKKT_OK) return rc;
+  if (items) {
+    static_assert(sizeof(int) == sizeof(int32_t), "the device list holds int");
+    if ((rc = hip_check(h, hipMemcpyAsync(W.items, items, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream), "okkt_factor_batch: item list upload")) != OKKT_OK) return rc;
+  }
   (void)hipEventRecord(h->ev0, h->stream);
-  std::string e = batch_factor_enqueue(h->N, W, mode, B, d_vals, val_stride, shift != nullptr, nshift, tol);
+  std::string e = batch_factor_enqueue(h->N, W, mode, B, d_vals, val_stride, shift != nullptr, nshift, tol, items ? W.items : nullptr);
   if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
   (void)hipEventRecord(h->ev1, h->stream);
-  W.raw.resize((size_t)B * kCountStride);
+  W.raw.resize((size_t)nout * kCountStride);
   if ((rc = stream_read(h, W.raw.data(), W.s.counters, W.raw.size() * sizeof(unsigned long long), "okkt_factor_batch failed")) != OKKT_OK) return rc;
   float ms = 0;
   if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->last_factor_ms = ms;
   W.mode_used = mode;
-  W.inertia.assign((size_t)B * 4, 0);
-  W.flags.assign((size_t)B, 0);
-  for (int64_t b = 0; b < B; ++b) {
+  if (!items || kept_B == 0) {
+    W.inertia.assign((size_t)nout * 4, 0);
+    W.flags.assign((size_t)nout, 0);
+  }
+  for (int64_t j = 0; j < B; ++j) {
+    const int64_t b = items ? items[j] : j;
     const unsigned long long* c = W.raw.data() + (size_t)b * kCountStride;
     int64_t* in = W.inertia.data() + (size_t)b * 4;
     for (int q = 0; q < 4; ++q) in[q] = (int64_t)c[q];
@@ -111,7 +134,9 @@ int solver_factor_batch_device(okkt_solver_s* h, int64_t B, const double* d_vals
     if (inertia_out) { inertia_out[b].pos = in[0]; inertia_out[b].neg = in[1]; inertia_out[b].zero = in[2]; inertia_out[b].nonfinite = in[3]; }
     if (flag_out) flag_out[b] = flag;
   }
-  W.factored_B = B;
+  // with a list: the slots it does not name keep the factor, the counts and the flag an earlier factorisation left them
+  // (a list that leaves slots out is accepted only behind a factorisation of all nslots, above: every slot below factored_B holds a factor)
+  W.factored_B = items ? std::max(kept_B, nslots) : B;
   return OKKT_OK;
 }
 

@@ -6,6 +6,8 @@
 // (lanczos_tridiag.h), and the dense symmetric eigen-solver of okkt_eigs (sym_eig.h), and the sets of the sparse right-hand sides
 // (solve_sparse_host.cpp), and the grids of the uniform batches (batch_host.cpp).  No device code, no HIP call.  SURVEY.md section 5 (host-side
 // sanitizer build); GPU sanitizers are not available on this pool.
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -20,6 +22,7 @@
 #include "solve_sparse.h"
 #include "batch.h"
 #include "batch_schur.h"
+#include "kkt_items_seq.h"
 #include "../../include/okkt.h"
 #include "sym_eig.h"
 #include "symbolic.h"
@@ -73,6 +76,75 @@ static int check_tridiag() {
     if (tridiag_extreme(0, a, a, &t0, &t1, s) != 1 || tridiag_extreme(65, a, a, &t0, &t1, s) != 1) { fprintf(stderr, "tridiag: order 0 / 65 not refused\n"); ++bad; }
   }
   if (!bad) printf("tridiag      orders 1 .. 64, split, scaled and refused cases clean\n");
+  return bad;
+}
+
+// The attempt sequencing of the delta loop over the items of a KKT batch (kkt_items_seq.h): items that pass at delta = 0, after three
+// attempts, beyond delta_max (status 0) and with a previous delta, stepped as okkt_kkt_items_ipopt_strategy steps
+// them (an attempt succeeds when delta >= need).  Checks the counts against a serial walk of the same sequence per item, that the number
+// of rounds is the largest count, and that an item leaves the active list exactly once.
+static int check_items_loop() {
+  int bad = 0;
+  okkt_kkt_pars P;
+  P.delta_start = 1e-6; P.delta_min = 1e-12; P.delta_max = 1e3; P.delta_inc = 8.0; P.delta_dec = 1.0 / 3.0; P.delta_zero = 0.0;
+  P.ItRefine_Num = 3; P.max_it = 500;
+  // item 6 starts from a large previous delta: it passes delta_max at its third attempt and leaves with status 0 while items 1 and 4
+  // are still making attempts (item 1 succeeds at its fourth)
+  const double dmin[] = {0.5, 0.5, -2.0, -2.0, 0.5, 0.25, 0.5};
+  const double prev[] = {0.0, 0.0, 0.0, 0.3, 0.0, 7.0, 900.0};
+  const double need[] = {0.0, 1e-5, 4.0, 0.01, 1e9, 1.0, 1e9};
+  const int B = 7;
+  {   // a NaN diag_min: every attempt is NaN, none ends the loop, and the sequence is used up after max_it attempts (error("max it"))
+    DeltaSeq s;
+    s.start(NAN, 0.0, P);
+    double d = 0.0;
+    bool lp = false;
+    int cnt = 0;
+    while (s.next(P, &d, &lp)) { ++cnt; if (d == d || !lp) { ++bad; break; } }
+    if (cnt != P.max_it) { fprintf(stderr, "items loop: the NaN sequence gave %d attempts\n", cnt); ++bad; }
+  }
+  std::vector<DeltaSeq> seq(B);
+  std::vector<double> cand(B, 0.0), delta(B, 0.0);
+  std::vector<char> in_loop(B, 0);
+  std::vector<int32_t> flags(B, 0), status(B, -1), nfac(B, 0), left(B, 0);
+  for (int b = 0; b < B; ++b) seq[b].start(dmin[b], prev[b], P);
+  ItemsLoop L;
+  L.start(B);
+  int rounds = 0;
+  while (!L.active.empty() && rounds < 1000) {
+    const std::vector<int32_t> before = L.active;
+    for (const int32_t b : L.active) {
+      bool lp = false;
+      if (!seq[b].next(P, &cand[b], &lp)) { ++bad; break; }
+      in_loop[b] = lp;
+      flags[b] = cand[b] >= need[b] ? 1 : 0;
+    }
+    ++rounds;
+    L.close_round(cand.data(), in_loop.data(), flags.data(), P.delta_max, status.data(), nfac.data(), delta.data());
+    for (const int32_t b : before)
+      if (std::find(L.active.begin(), L.active.end(), b) == L.active.end()) ++left[b];
+  }
+  int max_fac = 0;
+  for (int b = 0; b < B; ++b) {
+    // the serial walk of one item
+    DeltaSeq s;
+    s.start(dmin[b], prev[b], P);
+    int nf = 0, st = -1;
+    double d = 0.0;
+    bool lp = false;
+    while (s.next(P, &d, &lp)) {
+      ++nf;
+      if (d >= need[b]) { st = 1; break; }
+      if (lp && d > P.delta_max) { st = 0; break; }
+    }
+    if (nf != nfac[b] || st != status[b] || d != delta[b] || left[b] != 1) {
+      fprintf(stderr, "items loop: item %d: %d attempts (serial %d), status %d (%d), left %d times\n", b, nfac[b], nf, status[b], st, left[b]);
+      ++bad;
+    }
+    max_fac = std::max(max_fac, nf);
+  }
+  if (status[6] != 0 || nfac[6] != 3 || status[1] != 1 || nfac[1] != 4 || rounds <= nfac[6]) { fprintf(stderr, "items loop: the early failure: status %d after %d attempts\n", status[6], nfac[6]); ++bad; }
+  if (rounds != max_fac || status[4] != 0 || status[0] != 1 || nfac[0] != 1) { fprintf(stderr, "items loop: %d rounds, largest count %d\n", rounds, max_fac); ++bad; }
   return bad;
 }
 
@@ -451,6 +523,7 @@ int main() {
   }
   bad += check_tridiag();
   bad += check_sym_eig();
+  bad += check_items_loop();
   if (bad) { fprintf(stderr, "%d case(s) failed\n", bad); return 1; }
   printf("asan driver: all cases clean\n");
   return 0;

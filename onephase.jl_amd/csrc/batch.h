@@ -48,10 +48,12 @@ struct BatchSlots {
 struct BatchWork {
   BatchSlots s;
   int64_t B = 0, nrhs_max = 0;
+  int64_t generation = 0;        // counts the reservations made and released: what holds state of its own per slot (kkt_batch.hip) compares it
   int64_t arena_len = 0;         // doubles of the handle's own arena (the copy of okkt_batch_select)
   int64_t factored_B = 0;        // items of the last okkt_factor_batch (0: none)
   int mode = 0, env_mode = 0, mode_used = 0;   // mode forced by okkt_batch_set_mode (0 = none), by OKKT_BATCH_MODE at the reservation, mode of the last factorisation
   double* shift = nullptr;       // [B] the items' shifts on the device
+  int* items = nullptr;          // [B] the slots of a factorisation over an item list (solver_factor_batch_device with items)
   std::vector<int64_t> inertia;  // [factored_B][4]
   std::vector<int> flags;
   std::vector<unsigned long long> raw;
@@ -71,9 +73,10 @@ void batch_free(BatchWork& W);
 // whose levels run as one epoch)
 bool batch_item_mode_ok(const Numeric& N);
 int batch_pick_mode(const BatchWork& W, const Numeric& N, int64_t B);
-// all on N.stream, no synchronisation.  d_shift: W.shift filled by the caller (NULL: zero shift)
+// all on N.stream, no synchronisation.  d_shift: W.shift filled by the caller (NULL: zero shift).  d_items (level mode only): B slots;
+// grid item j works on slot d_items[j] -- its values at d_vals + slot * val_stride, its shift W.shift[slot]; NULL: slot j
 std::string batch_factor_enqueue(Numeric& N, BatchWork& W, int mode, int64_t B, const double* d_vals, int64_t val_stride, bool shifted,
-                                 int64_t nshift, double tol);
+                                 int64_t nshift, double tol, const int* d_items = nullptr);
 // right-hand sides r0 .. r0 + nr of every item (R = 1, 2 or 4 columns carried); rhs / sol [B][nrhs][n]
 std::string batch_solve_enqueue(Numeric& N, BatchWork& W, int mode, int64_t B, const double* d_rhs, double* d_sol, int64_t nrhs, int64_t r0,
                                 int nr, int R);

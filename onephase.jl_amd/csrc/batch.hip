@@ -111,11 +111,13 @@ __device__ __forceinline__ void front_task(const DevPlan& P, int s_root, double 
   }
 }
 
-// level mode: blockIdx.x = task of the level, blockIdx.y = item
+// level mode: blockIdx.x = task of the level, blockIdx.y = item, or with an item list (the delta loop over the items of a KKT batch,
+// DESIGN.md section 8.17, factors the still active items only) the slot items[blockIdx.y]; items = NULL is the identity
 template <int TPB>
-__global__ __launch_bounds__(TPB) void k_batch_front(DevPlan P0, BatchSlots S, const int* __restrict__ list, double tol, const double* __restrict__ vals, int64_t val_stride) {
+__global__ __launch_bounds__(TPB) void k_batch_front(DevPlan P0, BatchSlots S, const int* __restrict__ list, double tol, const double* __restrict__ vals, int64_t val_stride,
+                                                     const int* __restrict__ items) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  const int b = blockIdx.y;
+  const int b = items ? items[blockIdx.y] : (int)blockIdx.y;
   DevPlan P = item_plan(P0, S, b);
   P.vals = vals + (size_t)b * val_stride;
   unsigned pos = 0, neg = 0, zer = 0, bad = 0;
@@ -124,8 +126,9 @@ __global__ __launch_bounds__(TPB) void k_batch_front(DevPlan P0, BatchSlots S, c
 }
 
 // level mode: the items' shifts and counters before the first level (diagadd[b][i] = shift[b] where the original index is below nshift)
-__global__ __launch_bounds__(256) void k_batch_prepare(BatchSlots S, int n, const int* __restrict__ perm, const double* __restrict__ shift, int nshift) {
-  const int b = blockIdx.y;
+__global__ __launch_bounds__(256) void k_batch_prepare(BatchSlots S, int n, const int* __restrict__ perm, const double* __restrict__ shift, int nshift,
+                                                       const int* __restrict__ items) {
+  const int b = items ? items[blockIdx.y] : (int)blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) S.diagadd[(size_t)b * n + i] = (shift && perm[i] < nshift) ? shift[b] : 0.0;
   if (blockIdx.x == 0 && threadIdx.x < kCountStride) S.counters[(size_t)b * kCountStride + threadIdx.x] = 0ull;
@@ -389,7 +392,7 @@ std::string batch_alloc(BatchWork& W, const Symbolic& S, int64_t arena_doubles, 
   const size_t b = (size_t)B;
   const bool ok = dev_alloc(&s.arena, b * (size_t)s.arena_stride) && dev_alloc(&s.dvals, b * (size_t)S.n) && dev_alloc(&s.diagadd, b * (size_t)S.n) &&
                   dev_alloc(&s.xwork, b * R * (size_t)S.n) && dev_alloc(&s.zwork, b * R * (size_t)S.n) && dev_alloc(&s.cv, b * R * (size_t)S.sum_r) &&
-                  dev_alloc(&s.counters, b * kCountStride) && dev_alloc(&W.shift, b);
+                  dev_alloc(&s.counters, b * kCountStride) && dev_alloc(&W.shift, b) && dev_alloc(&W.items, b);
   if (!ok) {
     (void)hipGetLastError();
     batch_free(W);
@@ -414,10 +417,12 @@ std::string batch_alloc(BatchWork& W, const Symbolic& S, int64_t arena_doubles, 
 
 void batch_free(BatchWork& W) {
   BatchSlots& s = W.s;
-  for (void* p : {(void*)s.arena, (void*)s.dvals, (void*)s.diagadd, (void*)s.xwork, (void*)s.zwork, (void*)s.cv, (void*)s.counters, (void*)W.shift})
+  for (void* p : {(void*)s.arena, (void*)s.dvals, (void*)s.diagadd, (void*)s.xwork, (void*)s.zwork, (void*)s.cv, (void*)s.counters, (void*)W.shift, (void*)W.items})
     if (p) (void)hipFree(p);
   s = BatchSlots();
   W.shift = nullptr;
+  W.items = nullptr;
+  ++W.generation;
   W.B = W.nrhs_max = W.factored_B = 0;
   W.mode_used = 0;
   W.inertia.clear();
@@ -440,7 +445,8 @@ int batch_pick_mode(const BatchWork& W, const Numeric& N, int64_t B) {
 // workgroups are dispatched is undefined by contract, so a consumer could hold the slot its producer needs.  Dependencies are ordered
 // by launch boundaries (level mode: children's levels are earlier launches on the stream) and by program order inside the one
 // workgroup of an item (item mode: the schedule lists children's tasks before their parents'), and by nothing else.
-std::string batch_factor_enqueue(Numeric& N, BatchWork& W, int mode, int64_t B, const double* d_vals, int64_t val_stride, bool shifted, int64_t nshift, double tol) {
+std::string batch_factor_enqueue(Numeric& N, BatchWork& W, int mode, int64_t B, const double* d_vals, int64_t val_stride, bool shifted, int64_t nshift, double tol,
+                                 const int* d_items) {
   const DevPlan P = N.d;
   hipStream_t st = N.stream;
   const double* d_shift = shifted ? W.shift : nullptr;
@@ -452,10 +458,10 @@ std::string batch_factor_enqueue(Numeric& N, BatchWork& W, int mode, int64_t B, 
     if (maxf <= 32) hipLaunchKernelGGL(k_batch_item_factor<64>, dim3((unsigned)B), dim3(64), lds_front(maxf), st, P, W.s, list, ntasks, tol, d_vals, val_stride, d_shift, (int)nshift);
     else hipLaunchKernelGGL(k_batch_item_factor<256>, dim3((unsigned)B), dim3(256), lds_front(maxf), st, P, W.s, list, ntasks, tol, d_vals, val_stride, d_shift, (int)nshift);
   } else {
-    hipLaunchKernelGGL(k_batch_prepare, dim3((unsigned)std::max<int64_t>((W.s.n + 255) / 256, 1), (unsigned)B), dim3(256), 0, st, W.s, (int)W.s.n, P.perm, d_shift, (int)nshift);
+    hipLaunchKernelGGL(k_batch_prepare, dim3((unsigned)std::max<int64_t>((W.s.n + 255) / 256, 1), (unsigned)B), dim3(256), 0, st, W.s, (int)W.s.n, P.perm, d_shift, (int)nshift, d_items);
     for (const LevelRun& r : runs) {
-      if (r.maxf <= 32) hipLaunchKernelGGL(k_batch_front<64>, dim3(r.cnt, (unsigned)B), dim3(64), lds_front(r.maxf), st, P, W.s, P.sched + r.off, tol, d_vals, val_stride);
-      else hipLaunchKernelGGL(k_batch_front<256>, dim3(r.cnt, (unsigned)B), dim3(256), lds_front(r.maxf), st, P, W.s, P.sched + r.off, tol, d_vals, val_stride);
+      if (r.maxf <= 32) hipLaunchKernelGGL(k_batch_front<64>, dim3(r.cnt, (unsigned)B), dim3(64), lds_front(r.maxf), st, P, W.s, P.sched + r.off, tol, d_vals, val_stride, d_items);
+      else hipLaunchKernelGGL(k_batch_front<256>, dim3(r.cnt, (unsigned)B), dim3(256), lds_front(r.maxf), st, P, W.s, P.sched + r.off, tol, d_vals, val_stride, d_items);
     }
   }
   OKKT_HIP_TRY(hipGetLastError());

@@ -3,13 +3,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
 
 #include "solver.h"
 
-namespace okkt { struct LanczosWork; }
+namespace okkt { struct LanczosWork; struct KktItems; }
 
 struct okkt_kkt_s {
   okkt_handle ls = nullptr;
@@ -129,6 +130,8 @@ struct okkt_kkt_s {
   // operator nests (rows and columns of J, rows of the symmetric H), from okkt_kkt_set_structure
   okkt::LanczosWork* lz = nullptr;
   int64_t eig_maxlen = 0;
+  // KKT batches (kkt_batch.hip): the slots of okkt_kkt_items_reserve, released by okkt_kkt_items_release and with the handle
+  okkt::KktItems* items = nullptr;
 };
 
 #define KK_TRY(k, expr)                                                                      \
@@ -143,4 +146,8 @@ void kk_spmv_J(okkt_kkt_s* k, const double* x, double* y);
 void kk_spmv_JT(okkt_kkt_s* k, const double* Jx, const double* v, double* y);
 void kk_spmv_H(okkt_kkt_s* k, const double* x, double* y);
 inline hipStream_t kk_stream(okkt_kkt_s* k) { return k->ls->stream; }
+// the grid of a segmented row kernel: lpr lanes per row, workgroups of 256
+inline dim3 seg_grid(int64_t rows, int lpr) { return dim3((unsigned)std::max<int64_t>(1, (rows * lpr + 255) / 256)); }
+// the slots of the KKT batch and the synchronisation before them (kkt_batch.hip); okkt_kkt_destroy calls it
+void kkt_items_free(okkt_kkt_s* k);
 }  // namespace okkt

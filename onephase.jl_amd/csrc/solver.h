@@ -123,9 +123,12 @@ inline int schur_refuse(okkt_solver_s* h, const char* what) {
                                                    "use okkt_factor_schur / okkt_schur_condense / okkt_schur_expand, or clear the set with ns = 0)");
 }
 int solver_ensure_numeric(okkt_solver_s* h);
-// okkt_factor_batch_dev behind its pointer checks (api_batch.cpp); zero_tol as solver_factor_device's
+// okkt_factor_batch_dev behind its pointer checks (api_batch.cpp); zero_tol as solver_factor_device's.
+// items (host, or NULL: slots 0 .. B-1): B distinct slots below nslots, factored in level mode; d_vals, shift, inertia_out and flag_out
+// are then indexed by slot (nslots entries), and the slots not named keep their factor, counts and flag
 int solver_factor_batch_device(okkt_solver_s* h, int64_t B, const double* d_vals, int64_t val_stride, const double* shift, int64_t nshift, int64_t n, int64_t m,
-                               int sym_kind, okkt_inertia* inertia_out, int32_t* flag_out, bool zero_tol = false);
+                               int sym_kind, okkt_inertia* inertia_out, int32_t* flag_out, bool zero_tol = false, const int32_t* items = nullptr,
+                               int64_t nslots = 0);
 // okkt_set_scaling behind its argument checks (api.cpp): also what okkt_kkt_set_ls_scaling forwards to
 int solver_set_scaling(okkt_solver_s* h, int mode, int32_t sweeps, const double* s_user);
 // refinement driver (api_refine.cpp): x = F \ b, then corrections from the double-double residual against d_nzval until omega <= tol,

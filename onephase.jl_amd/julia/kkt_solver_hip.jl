@@ -325,6 +325,119 @@ function compute_directions!(k::HIP_KKT_solver, etas::Vector{Class_reduction_fac
     return out
 end
 
+# ---- KKT batches (okkt_kkt_items_*, DESIGN.md section 8.17): B iterates on the structure of one HIP_KKT_solver (:schur without dense
+# rows, or :symmetric).  Plain ccalls, UNTESTED like the rest of this file.  A multi-start or sweep driver calls these instead of looping
+# over solvers: item b's results are bit for bit those of form_system!, ipopt_strategy!, kkt_associate_rhs! and compute_direction! for
+# that iterate on a solver of its own.  Matrices are column-major in Julia: values go in as nnz x B (one column per item), vectors as
+# n x B / m x B, which is the [B][..] layout of the C ABI.
+struct OkktKktItemsInfo     # okkt_kkt_items_info of include/okkt.h
+    eligible::Int32
+    reason::Int32
+    bytes_per_item::Int64
+    launches_form::Int32
+    launches_direction::Int32
+end
+
+function items_query(k::HIP_KKT_solver)
+    info = Ref(OkktKktItemsInfo(0, 0, 0, 0, 0))
+    kkt_hip_check(k, "okkt_kkt_items_query", ccall((:okkt_kkt_items_query, OKKT_LIB), Cint, (Ptr{Cvoid}, Ref{OkktKktItemsInfo}), k.handle, info))
+    return info[]
+end
+items_reserve!(k::HIP_KKT_solver, B::Integer) =
+    kkt_hip_check(k, "okkt_kkt_items_reserve", ccall((:okkt_kkt_items_reserve, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64), k.handle, B))
+items_release!(k::HIP_KKT_solver) =
+    kkt_hip_check(k, "okkt_kkt_items_release", ccall((:okkt_kkt_items_release, OKKT_LIB), Cint, (Ptr{Cvoid},), k.handle))
+
+# its: iterates on the structure the solver was given (form_system! of the first one sets it).  A value array that is the same object
+# for every item goes in once, with stride 0
+function form_system_items!(k::HIP_KKT_solver, its::Vector{Class_iterate})
+    B = length(its)
+    Hs = [get_lag_hess(it) for it in its]; Js = [get_jac(it) for it in its]
+    sameH = all(H -> H.nzval === Hs[1].nzval, Hs); sameJ = all(J -> J.nzval === Js[1].nzval, Js)
+    Hx = sameH ? Hs[1].nzval : hcat([H.nzval for H in Hs]...); Jx = sameJ ? Js[1].nzval : hcat([J.nzval for J in Js]...)
+    s = hcat([get_s(it) for it in its]...); y = hcat([get_y(it) for it in its]...)
+    kkt_hip_check(k, "okkt_kkt_items_form_system", ccall((:okkt_kkt_items_form_system, OKKT_LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+        k.handle, B, Hx, sameH ? 0 : length(Hs[1].nzval), Jx, sameJ ? 0 : length(Js[1].nzval), s, y))
+    k.ready = :system_formed
+end
+
+function diag_min_items(k::HIP_KKT_solver, B::Integer)
+    out = zeros(B)
+    kkt_hip_check(k, "okkt_kkt_items_diag_min", ccall((:okkt_kkt_items_diag_min, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), k.handle, B, out))
+    return out
+end
+
+# factor!(kkt_solver, deltas[b]) for every item: (flags, inertias)
+function factor_items!(k::HIP_KKT_solver, deltas::Vector{Float64})
+    B = length(deltas)
+    inertia = Vector{OkktInertiaCounts}(undef, B); flags = zeros(Int32, B)
+    kkt_hip_check(k, "okkt_kkt_items_factor", ccall((:okkt_kkt_items_factor, OKKT_LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{OkktInertiaCounts}, Ptr{Int32}), k.handle, B, deltas, inertia, flags))
+    k.ready = :factored
+    return flags, inertia
+end
+
+# ipopt_strategy! for every item, a round of attempts being ONE batched factorisation over the items still active:
+# ([(status, num_fac, delta)], launches)
+function ipopt_strategy_items!(its::Vector{Class_iterate}, k::HIP_KKT_solver, pars::Class_parameters)
+    B = length(its)
+    p = OkktKktPars(pars.delta.start, pars.delta.min, pars.delta.max, pars.delta.inc, pars.delta.dec, pars.delta.zero,
+                    Int32(pars.kkt.ItRefine_Num), Int32(500))
+    prev = [get_delta(it) for it in its]
+    status = zeros(Int32, B); nfac = zeros(Int32, B); warn = zeros(Int32, B); delta = zeros(B); launches = Ref{Int32}(0)
+    kkt_hip_check(k, "okkt_kkt_items_ipopt_strategy", ccall((:okkt_kkt_items_ipopt_strategy, OKKT_LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{OkktKktPars}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ref{Int32}),
+        k.handle, B, prev, Ref(p), status, nfac, delta, warn, launches))
+    for b in 1:B, _ in 1:warn[b]          # delta_strategy.jl:94-98, counted per item by the library
+        println("WARNING: Inertia calculation incorrect")
+        @warn("Inertia calculation incorrect")
+    end
+    k.ready = :factored
+    # the caller calls set_delta(its[b], delta_b) itself, as after ipopt_strategy! (one_phase.jl:203-206)
+    return [(status[b] == 1 ? :success : :failure, Int(nfac[b]), delta[b]) for b in 1:B], Int(launches[])
+end
+
+# kkt_associate_rhs! for every item at the iterate it was formed at: [System_rhs]
+function kkt_associate_rhs_items!(k::HIP_KKT_solver, its::Vector{Class_iterate}, reduct_factors::Class_reduction_factors)
+    B = length(its); n = dim(its[1]); m = ncon(its[1])
+    grad = hcat([get_grad(it) for it in its]...); cons = hcat([get_cons(it) for it in its]...)
+    s = hcat([get_s(it) for it in its]...); y = hcat([get_y(it) for it in its]...)
+    mu = [get_mu(it) for it in its]; pen = [it.a_norm_penalty_par for it in its]
+    rD = zeros(n, B); rP = zeros(m, B); rC = zeros(m, B)
+    kkt_hip_check(k, "okkt_kkt_items_system_rhs", ccall((:okkt_kkt_items_system_rhs, OKKT_LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Float64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        k.handle, B, grad, cons, s, y, mu, pen, reduct_factors.P, reduct_factors.D, reduct_factors.mu, rD, rP, rC))
+    return [System_rhs(rD[:, b], rP[:, b], rC[:, b]) for b in 1:B]
+end
+
+# compute_direction! for every item: ([Class_point], [Class_kkt_error])
+function compute_direction_items!(k::HIP_KKT_solver, its::Vector{Class_iterate}, reduct_factors::Class_reduction_factors)
+    B = length(its); n = dim(its[1]); m = ncon(its[1])
+    dx = zeros(n, B); dy = zeros(m, B); ds = zeros(m, B); err = zeros(6, B)
+    kkt_hip_check(k, "okkt_kkt_items_compute_direction", ccall((:okkt_kkt_items_compute_direction, OKKT_LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        k.handle, B, Int32(k.pars.kkt.ItRefine_Num), dx, dy, ds, err))
+    dirs = Vector{Class_point}(); errs = Vector{Class_kkt_error}()
+    for b in 1:B
+        d = Class_point(); d.x = dx[:, b]; d.y = dy[:, b]; d.s = ds[:, b]
+        d.mu = -(1.0 - reduct_factors.mu) * get_mu(its[b])
+        d.primal_scale = -(1.0 - reduct_factors.P) * its[b].point.primal_scale
+        push!(dirs, d)
+        push!(errs, Class_kkt_error(err[1, b], err[2, b], err[3, b], err[4, b], err[5, b], err[6, b]))
+    end
+    return dirs, errs
+end
+
+# slot b (0-based, as in the C ABI) -> the solver's own state: afterwards every single-iterate method behaves as after the serial
+# sequence on that iterate
+function items_select!(k::HIP_KKT_solver, b::Integer, it::Class_iterate)
+    kkt_hip_check(k, "okkt_kkt_items_select", ccall((:okkt_kkt_items_select, OKKT_LIB), Cint, (Ptr{Cvoid}, Int64), k.handle, b))
+    k.factor_it = it
+    k.resident_rhs = nothing
+end
+
 # ---- the dense factor of the Schur complement (DESIGN.md section 8.7) on a linear_solver_HIP in Schur mode (okkt_set_schur before the
 # analysis, okkt_factor_schur before these).  UNTESTED like the rest of this file.  Inertias come back as (pos, neg, zero, nonfinite).
 struct OkktInertiaCounts    # okkt_inertia of include/okkt.h

@@ -232,6 +232,13 @@ class HIP_KKT_solver:
         self.inertia = None
         self._pattern = None
         self._resident_rhs = None
+        # KKT batches: items of the last form_system_items, their iterates, the (iterates, eta, [System_rhs]) of the last
+        # kkt_associate_rhs_items, the deltas of the last factor_items / ipopt_strategy_items
+        self._items_B = 0
+        self._items_its = None
+        self._items_cur = None
+        self._items_delta = None
+        self.items_diag_dom_warnings = None
 
     # ---- initialize! (kkt_system_solver.jl:21-25)
     def initialize_b(self, intial_it):
@@ -550,6 +557,177 @@ class HIP_KKT_solver:
             return ls.batch_query()["eligible"] == 1
         except OkktError:
             return False
+
+    # ---- KKT batches (okkt_kkt_items_*): B iterates on the structure of this solver.  Item b's results are bit for
+    # bit those of form_system_b, diag_min, factor_b / ipopt_strategy_b, kkt_associate_rhs_b and compute_direction_b for that iterate on a
+    # solver of its own; a multi-start or sweep driver calls these instead of looping over solvers
+    def items_query(self):
+        """okkt_kkt_items_query as a dict (host only): eligible, reason (OKKT_KKT_ITEMS_*), bytes_per_item, launches_form, launches_direction."""
+        if self._k is None:
+            raise OkktError("initialize_b has not been called")
+        info = L.OkktKktItemsInfo()
+        self._check(self._lib.okkt_kkt_items_query(self._k, C.byref(info)), "okkt_kkt_items_query")
+        return info.as_dict()
+
+    def items_reserve(self, B):
+        if self._k is None:
+            raise OkktError("initialize_b has not been called")
+        self._check(self._lib.okkt_kkt_items_reserve(self._k, int(B)), "okkt_kkt_items_reserve")
+        self._items_B, self._items_its, self._items_cur, self._items_delta = 0, None, None, None
+
+    def items_release(self):
+        if self._k is None:
+            raise OkktError("initialize_b has not been called")
+        self._check(self._lib.okkt_kkt_items_release(self._k), "okkt_kkt_items_release")
+        self._items_B, self._items_its, self._items_cur, self._items_delta = 0, None, None, None
+
+    def form_system_items(self, its):
+        """form_system! for the iterates `its` (one structure: their index arrays are checked against the stored ones).  Value arrays that
+        are the same object for all items go in once, with stride 0."""
+        if self._k is None:
+            raise OkktError("initialize_b has not been called")
+        if len(its) == 0:
+            raise OkktError("form_system_items: no iterates")
+        mats = [self._set_structure(it) for it in its]
+        n, m = mats[0][2], mats[0][3]
+        B = len(its)
+
+        def pack(arrs):
+            if all(a is arrs[0] for a in arrs):
+                return L.f64(arrs[0]), 0
+            return L.f64(np.stack([np.asarray(a, dtype=float) for a in arrs])), len(arrs[0])
+
+        Hx, hs = pack([t[0].data for t in mats])
+        Jx, js = pack([t[1].data for t in mats])
+        s = L.f64(np.stack([it.s for it in its])) if m else np.zeros(1)
+        y = L.f64(np.stack([it.y for it in its])) if m else np.zeros(1)
+        self._check(self._lib.okkt_kkt_items_form_system(self._k, B, L.p_f64(Hx), hs, L.p_f64(Jx), js, L.p_f64(s), L.p_f64(y)),
+                    "okkt_kkt_items_form_system")
+        self._items_B = B
+        self._items_its = list(its)
+        self._items_cur = None
+        self.ready = "system_formed"
+
+    def _items_formed(self, what):
+        if self._k is None:
+            raise OkktError("initialize_b has not been called")
+        if not self._items_B:
+            raise OkktError(f"{what}: form_system_items has not been called")
+        return self._items_B
+
+    def diag_min_items(self):
+        self._items_formed("diag_min_items")
+        out = np.zeros(self._items_B)
+        self._check(self._lib.okkt_kkt_items_diag_min(self._k, self._items_B, L.p_f64(out)), "okkt_kkt_items_diag_min")
+        return out
+
+    def factor_items(self, deltas):
+        """factor!(kkt_solver, deltas[b]) for every item -> (flags, inertias): the flag and (pos, neg, zero, nonfinite) of okkt_kkt_factor."""
+        B = self._items_formed("factor_items")
+        d = L.f64(np.asarray(deltas, dtype=float))
+        if d.shape != (B,):
+            raise OkktError("factor_items: one delta per item of the last form_system_items")
+        inert = (L.OkktInertia * max(B, 1))()
+        flags = np.zeros(max(B, 1), dtype=np.int32)
+        self._check(self._lib.okkt_kkt_items_factor(self._k, B, L.p_f64(d), inert, flags.ctypes.data_as(C.POINTER(C.c_int32))),
+                    "okkt_kkt_items_factor")
+        self._items_delta = [float(v) for v in d]
+        self.ready = "factored"
+        return [int(f) for f in flags[:B]], [inert[b].as_tuple() for b in range(B)]
+
+    def ipopt_strategy_items(self, its):
+        """ipopt_strategy! for every item, a round of attempts being ONE batched factorisation over the items still active ->
+        ([(status, num_fac, delta)], launches).  Sets it.delta as ipopt_strategy_b's caller does (delta_strategy.jl:46,62)."""
+        B = self._items_formed("ipopt_strategy_items")
+        if len(its) != B:
+            raise OkktError("ipopt_strategy_items: the iterates of the last form_system_items")
+        p = L.OkktKktPars()
+        self._lib.okkt_kkt_default_pars(C.byref(p))
+        d = self.pars.delta
+        p.delta_start, p.delta_min, p.delta_max, p.delta_inc, p.delta_dec, p.delta_zero = d.start, d.min, d.max, d.inc, d.dec, d.zero
+        prev = L.f64(np.array([float(it.delta) for it in its]))
+        status, nfac, warn = (np.zeros(B, dtype=np.int32) for _ in range(3))
+        delta = np.zeros(B)
+        launches = C.c_int32()
+        i32 = C.POINTER(C.c_int32)
+        self._check(self._lib.okkt_kkt_items_ipopt_strategy(self._k, B, L.p_f64(prev), C.byref(p), status.ctypes.data_as(i32), nfac.ctypes.data_as(i32),
+                                                            L.p_f64(delta), warn.ctypes.data_as(i32), C.byref(launches)),
+                    "okkt_kkt_items_ipopt_strategy")
+        self.items_diag_dom_warnings = [int(w) for w in warn]
+        for it, dl in zip(its, delta):
+            it.delta = float(dl)
+        self._items_delta = [float(v) for v in delta]
+        self.ready = "factored"
+        return [("success" if status[b] == 1 else "failure", int(nfac[b]), float(delta[b])) for b in range(B)], int(launches.value)
+
+    def kkt_associate_rhs_items(self, its, eta):
+        """kkt_associate_rhs! for every item at the iterate it was formed at -> [System_rhs]."""
+        B = self._items_formed("kkt_associate_rhs_items")
+        if len(its) != B:
+            raise OkktError("kkt_associate_rhs_items: the iterates of the last form_system_items")
+        n, m = its[0].dim(), its[0].ncon()
+        grad = L.f64(np.stack([it.grad for it in its]))
+        cons, s, y = (L.f64(np.stack([getattr(it, a) for it in its])) for a in ("cons", "s", "y"))
+        mu = L.f64(np.array([float(it.mu) for it in its]))
+        pen = L.f64(np.array([float(it.a_norm_penalty_par) for it in its]))
+        rD, rP, rC = np.zeros((B, n)), np.zeros((B, m)), np.zeros((B, m))
+        self._check(self._lib.okkt_kkt_items_system_rhs(self._k, B, L.p_f64(grad), L.p_f64(cons), L.p_f64(s), L.p_f64(y), L.p_f64(mu), L.p_f64(pen),
+                                                        eta.P, eta.D, eta.mu, L.p_f64(rD), L.p_f64(rP), L.p_f64(rC)), "okkt_kkt_items_system_rhs")
+        rhs = [System_rhs(rD[b].copy(), rP[b].copy(), rC[b].copy()) for b in range(B)]
+        self._items_cur = (list(its), eta, rhs)
+        return rhs
+
+    def compute_direction_items(self, resident=False, check_nan=True):
+        """compute_direction! for every item -> ([Class_point], [Class_kkt_error]); resident=True leaves the directions on the device
+        (items_select(b) + okkt_kkt_get_direction bring one back) and returns ([], errors).  Like compute_direction_b, a returned
+        direction goes through check_for_nan (IPM_tools.jl:32-49): a non-finite entry raises OkktError naming the first such item.
+        check_nan=False returns every item's direction as the device computed it (a caller that drops bad items itself); resident
+        directions are not looked at."""
+        if self.ready != "factored":
+            raise OkktError("kkt solver not ready to compute direction!")
+        B = self._items_formed("compute_direction_items")
+        its, eta = self._items_cur[:2] if self._items_cur is not None else (self._items_its, None)
+        n, m = its[0].dim(), its[0].ncon()
+        dx, dy, ds = np.zeros((B, n)), np.zeros((B, m)), np.zeros((B, m))
+        err = (L.OkktKktError * max(B, 1))()
+        a = (None, None, None) if resident else (L.p_f64(dx), L.p_f64(dy), L.p_f64(ds))
+        self._check(self._lib.okkt_kkt_items_compute_direction(self._k, B, self.pars.kkt.ItRefine_Num, a[0], a[1], a[2], err),
+                    "okkt_kkt_items_compute_direction")
+        errs = [Class_kkt_error(e.error_D, e.error_P, e.error_mu, e.overall, e.rhs_norm, e.ratio) for e in err[:B]]
+        dirs = []
+        for b in range(B if not resident else 0):
+            d = Class_point(x=dx[b].copy(), y=dy[b].copy(), s=ds[b].copy())
+            if eta is not None:
+                d.mu = -(1.0 - eta.mu) * its[b].mu
+                d.primal_scale = -(1.0 - eta.P) * its[b].primal_scale
+            dirs.append(d)
+        if check_nan:
+            for b, d in enumerate(dirs):
+                for name, v in (("x", d.x), ("y", d.y), ("s", d.s)):
+                    if not np.all(np.isfinite(v)):
+                        raise OkktError(f"NaN in {name} (item {b})")
+        return dirs, errs
+
+    def items_select(self, b):
+        """Slot b -> this solver's own state: afterwards every single-iterate method behaves as after the serial sequence on that iterate."""
+        self._items_formed("items_select")
+        self._check(self._lib.okkt_kkt_items_select(self._k, int(b)), "okkt_kkt_items_select")
+        it = self._items_its[b]
+        sd = np.zeros(it.dim())
+        self._check(self._lib.okkt_kkt_get_schur_diag(self._k, L.p_f64(sd)), "okkt_kkt_get_schur_diag")
+        self.schur_diag = sd
+        self.factor_it = it
+        if self.ready == "factored":
+            self._delta = self._items_delta[b]
+            self.delta_x_vec = self._delta * np.ones(it.dim())
+            self.delta_s_vec = np.zeros(it.ncon())
+        if self._items_cur is not None:
+            self.current_it = self._items_cur[0][b]
+            self.reduct_factors = self._items_cur[1]
+            # the item's triple is resident on the device; the host copy is the one kkt_associate_rhs_items downloaded
+            self._resident_rhs = self.rhs = self._items_cur[2][b]
+        else:
+            self._resident_rhs = self.rhs = None
 
     def min_eig(self, max_steps=0, tol=0.0, scaled=0, with_vector=True):
         """okkt_kkt_min_eig: (info, v) -- the Lanczos estimate of lambda_min(Q(0)), Q(0) = H + J' Sigma J of the last form_system_b, as a
