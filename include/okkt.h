@@ -1042,6 +1042,49 @@ int okkt_kkt_items_compute_direction(okkt_kkt_handle k, int64_t B, int32_t ItRef
                                      double* dx /* [B][n] */, double* dy, double* ds /* [B][m]; three NULLs: stay resident */,
                                      okkt_kkt_error* err_out /* [B] or NULL */);
 int okkt_kkt_items_select(okkt_kkt_handle k, int64_t b);
+/* ---- Line-search batches: step sizes and predicted reductions for the items of a KKT batch ----
+ * The step-side functions (okkt_kkt_max_step_primal, okkt_kkt_s_bound_ok, okkt_kkt_dual_step_range, okkt_kkt_predicted_reduction,
+ * okkt_kkt_dual_step) for B items of a reservation at once, against each item's formed iterate and resident direction in its slot: the
+ * direction okkt_kkt_items_compute_direction left, or the triples of okkt_kkt_items_set_direction (which covers B items as
+ * okkt_kkt_set_direction covers one; okkt_kkt_items_select(b) afterwards leaves the handle as okkt_kkt_set_direction would).  One rule:
+ * every output for item b is bit for bit what the matching single-iterate call returns for that iterate and direction on a KKT handle of
+ * its own -- NaN propagation, the reset semantics of dual_bounds and the non-finite fallback (0, -1) included.
+ * Per-item scalars are arrays [B], per-item vectors [B][m] or [B][n], items contiguous.  items / nitems is the optional item list:
+ * items == NULL means every slot 0 .. B-1; otherwise items[0 .. nitems) are distinct slots below B, inputs and outputs stay indexed by
+ * slot, only listed slots are read and only their outputs written (a backtracking loop keeps calling with the items still in it);
+ * nitems == 0 is OKKT_OK and writes nothing.  frac_stride = 0: one fraction vector for every item, else m.  okkt_kkt_items_dual_step:
+ * J_nzval_cand = NULL reads each item's formed J, J_stride = 0 one candidate array for every item, else >= the number of entries; for
+ * dual_ls other than 1 or 3 step_size_D[b] = ub[b] and nothing is launched.  okkt_kkt_items_dual_step_range runs a second pass over
+ * the items in which an entry with dy == 0 reset the interval.  One host synchronisation per pass, one more when norm(dx_b, Inf) of the
+ * directions is not cached yet (once per direction).  The line-search slots (okkt_kkt_items_ls_info.extra_bytes_per_item) are
+ * allocated by the first of these calls after a reservation -- OKKT_ERR_ALLOC with a message when they do not fit -- and freed with it.
+ * Refusals: those of the family (an ineligible handle, a missing or replaced reservation: OKKT_ERR_INVALID; host_symbolic_only:
+ * OKKT_ERR_NO_DEVICE), and OKKT_ERR_INVALID with a message, the handle staying usable, for B above the items of the last
+ * okkt_kkt_items_form_system, a direction call before it, a step call with B above the items that hold a direction ("no direction:
+ * ..."), a NULL required array, a slot in items out of range or listed twice, frac_stride other than 0 or m.
+ * okkt_kkt_items_ls_query (host only): eligible / reason as okkt_kkt_items_query, the extra HBM of one item, and the kernel launches of
+ * the norm pass and of each of the five calls (they do not depend on B; launches_dual_range counts one pass). */
+typedef struct {
+  int32_t eligible, reason;
+  int64_t extra_bytes_per_item;
+  int32_t launches_dx_norm, launches_max_step, launches_s_bound, launches_dual_range, launches_predicted_reduction, launches_dual_step;
+} okkt_kkt_items_ls_info;
+int okkt_kkt_items_set_direction(okkt_kkt_handle k, int64_t B, const double* dx /* [B][n] */, const double* dy, const double* ds /* [B][m] */);
+int okkt_kkt_items_max_step_primal(okkt_kkt_handle k, int64_t B, const int32_t* items, int64_t nitems, const double* frac_bd_predict,
+                                   int64_t frac_stride /* 0 or m */, double ex, double* step_size_P /* [B] */, double* dx_norm_inf /* [B] or NULL */);
+int okkt_kkt_items_s_bound_ok(okkt_kkt_handle k, int64_t B, const int32_t* items, int64_t nitems, const double* s_new /* [B][m] */,
+                              const double* frac_bd, int64_t frac_stride, double ex, int32_t* ok /* [B] */);
+int okkt_kkt_items_dual_step_range(okkt_kkt_handle k, int64_t B, const int32_t* items, int64_t nitems, const double* s_cand, const double* y_cand /* [B][m] */,
+                                   const double* mu_cand /* [B] */, double comp_feas, const double* frac_bd, int64_t frac_stride,
+                                   double* lb /* [B] */, double* ub /* [B] */);
+int okkt_kkt_items_predicted_reduction(okkt_kkt_handle k, int64_t B, const int32_t* items, int64_t nitems, const double* grad /* [B][n] */,
+                                       const double* mu, const double* dmu, const double* a_norm_penalty, const double* step_size /* [B] each */,
+                                       double* out /* [B][4] */);
+int okkt_kkt_items_dual_step(okkt_kkt_handle k, int64_t B, const int32_t* items, int64_t nitems, const double* J_nzval_cand /* or NULL */,
+                             int64_t J_stride /* 0: shared */, const double* grad_cand /* [B][n] */, const double* s_cand, const double* y_cand /* [B][m] */,
+                             const double* mu_cand, const double* a_norm_penalty, const double* step_size_P, const double* lb, const double* ub,
+                             const double* scale_D, const double* scale_mu /* [B] each */, int dual_ls, double* step_size_D /* [B] */);
+int okkt_kkt_items_ls_query(okkt_kkt_handle k, okkt_kkt_items_ls_info* out);      /* host only */
 /* Test hook: one batched factorisation of the reserved KKT batch over the item list items[0 .. nitems) (distinct slots below B) with the
  * shifts delta[slot], as a round of okkt_kkt_items_ipopt_strategy runs it; flag_out [B] is written for the listed slots only. */
 int okkt_debug_kkt_items_factor_list(okkt_kkt_handle k, int64_t B, const int32_t* items, int64_t nitems, const double* delta /* [B] */,

@@ -314,6 +314,25 @@ class OkktKktItemsInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OkktKktItemsLsInfo(C.Structure):
+    """okkt_kkt_items_ls_info: eligible / reason as okkt_kkt_items_info, the HBM of one item's line-search slots, the kernel launches of the
+    norm pass and of each batched step-side call (launches_dual_range: one pass)."""
+    _fields_ = [
+        ("eligible", C.c_int32),
+        ("reason", C.c_int32),
+        ("extra_bytes_per_item", C.c_int64),
+        ("launches_dx_norm", C.c_int32),
+        ("launches_max_step", C.c_int32),
+        ("launches_s_bound", C.c_int32),
+        ("launches_dual_range", C.c_int32),
+        ("launches_predicted_reduction", C.c_int32),
+        ("launches_dual_step", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class OkktSchurBatchInfo(C.Structure):
     """okkt_schur_batch_info: whether the analysed plan takes a scenario batch (reason: OKKT_SBATCH_*), the order of the Schur set, the
     HBM of one item and of what the items share, the tasks and levels of the interior, the batch's own kernel launches."""
@@ -582,6 +601,15 @@ SIGNATURES = {
                                              _f64p, _f64p, _f64p]),
     "okkt_kkt_items_compute_direction": (C.c_int, [_vp, C.c_int64, C.c_int32, _f64p, _f64p, _f64p, C.POINTER(OkktKktError)]),
     "okkt_kkt_items_select": (C.c_int, [_vp, C.c_int64]),
+    "okkt_kkt_items_set_direction": (C.c_int, [_vp, C.c_int64, _f64p, _f64p, _f64p]),
+    "okkt_kkt_items_max_step_primal": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _f64p, C.c_int64, C.c_double, _f64p, _f64p]),
+    "okkt_kkt_items_s_bound_ok": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _f64p, _f64p, C.c_int64, C.c_double, C.POINTER(C.c_int32)]),
+    "okkt_kkt_items_dual_step_range": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _f64p, _f64p, _f64p, C.c_double, _f64p, C.c_int64,
+                                                 _f64p, _f64p]),
+    "okkt_kkt_items_predicted_reduction": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]),
+    "okkt_kkt_items_dual_step": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _f64p, C.c_int64, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p,
+                                           _f64p, _f64p, _f64p, _f64p, C.c_int, _f64p]),
+    "okkt_kkt_items_ls_query": (C.c_int, [_vp, C.POINTER(OkktKktItemsLsInfo)]),
     "okkt_debug_kkt_items_factor_list": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _f64p, C.POINTER(C.c_int32)]),
     "okkt_debug_items_loop_model": (C.c_int, [C.c_int64, _f64p, _f64p, _f64p, C.POINTER(OkktKktPars), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                _f64p, C.POINTER(C.c_int32)]),

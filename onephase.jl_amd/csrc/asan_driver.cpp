@@ -4,7 +4,8 @@
 // of them and on a front tall enough for several chunks per column, and the flat records of the staged big-front assembly
 // (asm_pieces.h) on each of them and under a front of three chunks, and the tridiagonal solver of the Lanczos estimate
 // (lanczos_tridiag.h), and the dense symmetric eigen-solver of okkt_eigs (sym_eig.h), and the sets of the sparse right-hand sides
-// (solve_sparse_host.cpp), and the grids of the uniform batches (batch_host.cpp).  No device code, no HIP call.  SURVEY.md section 5 (host-side
+// (solve_sparse_host.cpp), and the grids of the uniform batches (batch_host.cpp), and the host arithmetic behind the reductions of the
+// step-side functions (ls_finish.h).  No device code, no HIP call.  SURVEY.md section 5 (host-side
 // sanitizer build); GPU sanitizers are not available on this pool.
 #include <algorithm>
 #include <cmath>
@@ -23,6 +24,7 @@
 #include "batch.h"
 #include "batch_schur.h"
 #include "kkt_items_seq.h"
+#include "ls_finish.h"
 #include "../../include/okkt.h"
 #include "sym_eig.h"
 #include "symbolic.h"
@@ -462,6 +464,42 @@ static int run(const char* name, int n, const std::set<std::pair<int, int>>& e, 
   return 0;
 }
 
+// The host arithmetic behind the reductions of the step-side functions (ls_finish.h), stepped once on what a launch can return: ordinary
+// numbers, NaN in either argument of Julia's min / max, a zero norm under a fractional exponent, the non-finite bounds that fall back to
+// (0, -1), a reset interval whose ub stays at -1, no constraints (m = 0: no complementarity penalty) and a NaN least-squares step.
+static int check_ls_finish() {
+  int bad = 0;
+  auto fail = [&](const char* what) { fprintf(stderr, "ls_finish: %s\n", what); ++bad; };
+  if (jl_min(1.0, 2.0) != 1.0 || jl_max(1.0, 2.0) != 2.0 || !std::isnan(jl_min(NAN, 1.0)) || !std::isnan(jl_min(1.0, NAN)) || !std::isnan(jl_max(NAN, 1.0)) ||
+      !std::isnan(jl_max(1.0, NAN)) || jl_min(-INFINITY, 1.0) != -INFINITY)
+    fail("jl_min / jl_max");
+  if (thres_scalar(4.0, 0.5) != 8.0 || thres_scalar(0.0, 0.5) != 0.0 || !std::isnan(thres_scalar(NAN, 0.5)) || thres_scalar(INFINITY, 0.5) != INFINITY) fail("thres_scalar");
+  if (step_from_ratio(4.0) != 0.25 || step_from_ratio(INFINITY) != 0.0 || !std::isnan(step_from_ratio(NAN))) fail("step_from_ratio");
+  double lb = 0.0, ub = 0.0;
+  { const double r[4] = {0.25, 0.75, -1.0, 2.0}; dual_range_finish(r, &lb, &ub); if (lb != 0.25 || ub != 0.5) fail("dual range, ordinary"); }
+  { const double r[4] = {0.25, 0.75, -1.0, 1.0}; dual_range_finish(r, &lb, &ub); if (lb != 0.25 || ub != 0.75) fail("dual range, ratio 1"); }
+  { const double r[4] = {INFINITY, 0.75, -1.0, 2.0}; dual_range_finish(r, &lb, &ub); if (lb != 0.0 || ub != -1.0) fail("dual range, lb = Inf"); }
+  { const double r[4] = {0.25, NAN, -1.0, 2.0}; dual_range_finish(r, &lb, &ub); if (lb != 0.0 || ub != -1.0) fail("dual range, ub = NaN"); }
+  { const double r[4] = {0.0, -1.0, 16.0, 1.0}; dual_range_finish(r, &lb, &ub); if (lb != 0.0 || ub != -1.0) fail("dual range, behind a reset"); }
+  { const double r[4] = {0.25, 0.75, -1.0, NAN}; dual_range_finish(r, &lb, &ub); if (lb != 0.25 || !std::isnan(ub)) fail("dual range, NaN ratio"); }
+  double out[4];
+  { const double rm[3] = {2.0, 3.0, 4.0}, rn[2] = {-1.0, 6.0};
+    predicted_reduction_finish(5, rm, rn, 0.5, 0.5, out);
+    if (out[0] != 0.5 * -1.0 + 0.25 * 0.5 * 8.0 || out[1] != 3.0 || out[2] != 4.0 || out[3] != out[0] + (64.0 - 27.0) / 0.25) fail("predicted reduction");
+    predicted_reduction_finish(0, rm, rn, 0.0, 0.5, out);
+    if (out[3] != out[0]) fail("predicted reduction, m = 0"); }
+  { const double rm[3] = {2.0, 3.0, NAN}, rn[2] = {-1.0, 6.0};
+    predicted_reduction_finish(5, rm, rn, 0.5, 1.0, out);
+    if (out[1] != 3.0 || !std::isnan(out[2]) || !std::isnan(out[3]) || out[0] != -1.0 + 0.5 * 8.0) fail("predicted reduction, NaN"); }
+  if (dual_small_step(0.25, 0.75, 0.5) != 0.5 || dual_small_step(0.25, 0.75, 2.0) != 0.75 || dual_small_step(0.25, 0.1, 2.0) != 0.25) fail("dual_small_step");
+  { const double rn[2] = {1.0, 2.0}, rm[2] = {2.0, 2.0};
+    if (dual_step_finish(rn, rm, 1.0, 0.1) != 0.75 || dual_step_finish(rn, rm, 0.5, 0.1) != 0.5 || dual_step_finish(rn, rm, 1.0, 0.9) != 0.9) fail("dual_step_finish"); }
+  { const double rn[2] = {0.0, 0.0}, rm[2] = {0.0, 0.0};
+    if (!std::isnan(dual_step_finish(rn, rm, 1.0, 0.1))) fail("dual_step_finish, 0 / 0"); }
+  if (!bad) printf("ls_finish    min / max, threshold, dual range, predicted reduction and dual step clean\n");
+  return bad;
+}
+
 int main() {
   int bad = 0;
   std::mt19937 rng(5);
@@ -524,6 +562,7 @@ int main() {
   bad += check_tridiag();
   bad += check_sym_eig();
   bad += check_items_loop();
+  bad += check_ls_finish();
   if (bad) { fprintf(stderr, "%d case(s) failed\n", bad); return 1; }
   printf("asan driver: all cases clean\n");
   return 0;

@@ -280,12 +280,7 @@ template <int LPR>
 __global__ __launch_bounds__(256) void k_seg_hess(int64_t n, const int64_t* __restrict__ Hrp, const int* __restrict__ Hrj, const double* __restrict__ Hcsr,
                                                   const int64_t* __restrict__ Hp, const int* __restrict__ Hi, const double* __restrict__ Hx,
                                                   const double* __restrict__ Hdiag, const double* __restrict__ x, double* __restrict__ y) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = t / LPR;
-  const int sub = (int)(t % LPR);
-  const int64_t i = row < n ? row : n - 1;
-  const double h = seg_hess<LPR>(Hrp, Hrj, Hcsr, Hp, Hi, Hx, Hdiag, x, i, sub);
-  if (sub == 0 && row < n) y[i] = h;
+  kd_seg_hess<LPR>(n, Hrp, Hrj, Hcsr, Hp, Hi, Hx, Hdiag, x, y);
 }
 // res = rhs - (J' v + (H dx + delta dx)) with v = Sigma .* (J dx) (schur.jl:166-170)
 template <int LPR>

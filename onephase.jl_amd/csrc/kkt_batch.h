@@ -31,8 +31,29 @@ struct KktItemSlots {
   double *delta = nullptr, *mu_pen = nullptr, *mu_target = nullptr, *rmin = nullptr;
 };
 
+// Line-search slots (ls_batch.hip): what the batched step-side calls stage and reduce through, allocated at
+// the first of them after a reservation and freed with it (they sit in KktItems::allocs)
+struct KktLsSlots {
+  bool ready = false;
+  double *sm[4] = {nullptr, nullptr, nullptr, nullptr};   // [B][m] staging: frac, s_cand / s_new / J dx, y_cand / w, y - mu pen
+  double *sn[2] = {nullptr, nullptr};                     // [B][n] staging: grad, J'w
+  double *part = nullptr, *out = nullptr;                 // partials [B][256 * 8], results [B][8]
+  double* scal = nullptr;                                 // the per-item scalars the maps read: [kLsScalars][B]
+  int* list = nullptr;                                    // [B] the item list of a launch
+  double* Jcand = nullptr;                                // [B or 1][nnzJ] Jacobian values of the candidates (okkt_kkt_items_dual_step)
+  int64_t Jcand_cap = 0;                                  // arrays Jcand has room for
+};
+// rows of KktLsSlots::scal
+enum { kLsThr = 0, kLsNxMin, kLsMu, kLsMuNew, kLsStep, kLsScaleD, kLsScaleMu, kLsAfter, kLsUbInit, kLsAxA, kLsAxB, kLsScalars };
+
 struct KktItems {
   KktItemSlots S;
+  KktLsSlots LS;
+  // items whose direction is the solve's of the last okkt_kkt_items_compute_direction (okkt_kkt_items_set_direction leaves it: dir_B
+  // counts the items that hold a direction of either origin), and the cached norm(dx, Inf) of the items 0 .. dir_B-1
+  int64_t solved_B = 0;
+  bool dxnorm_ok = false;
+  std::vector<double> dxnorm;
   int64_t B = 0;                 // reserved slots
   std::vector<void*> allocs;
   int64_t Hx_cap = 0, Jx_cap = 0;   // arrays S.Hx / S.Jx have room for (0: not allocated yet; 1: a shared array; else B)

@@ -81,6 +81,14 @@ __global__ __launch_bounds__(256) void kb_seg_spmv(int64_t nrows, const int64_t*
   kd_seg_spmv<LPR, false>(nrows, ptr, idx, vals + b * vals_stride, x + b * x_stride, scale ? scale + b * scale_stride : nullptr,
                           addv ? addv + b * addv_stride : nullptr, beta, y + b * y_stride, nullptr, nullptr);
 }
+// k_seg_hess with the item's H: y_b = hess_product(x_b)
+template <int LPR>
+__global__ __launch_bounds__(256) void kb_seg_hess(KktItemSlots S, const int64_t* __restrict__ Hrp, const int* __restrict__ Hrj, const int64_t* __restrict__ Hp,
+                                                   const int* __restrict__ Hi, const double* __restrict__ x, int64_t x_stride, double* __restrict__ y,
+                                                   int64_t y_stride, const int* __restrict__ items) {
+  const int64_t b = item_of(items);
+  kd_seg_hess<LPR>(S.n, Hrp, Hrj, S.Hcsr + b * S.nnzH, Hp, Hi, S.Hx + b * S.Hx_stride, S.Hdiag + b * S.n, x + b * x_stride, y + b * y_stride);
+}
 // hcol = vn1, hrow = vn2, jsj = vn3 (schur) of the item, its delta from the array; margins into big1
 __global__ void kb_diag_dom_margin(KktItemSlots S, int with_jsj, const double* __restrict__ qdiag, const int* __restrict__ items) {
   const int64_t b = item_of(items);
@@ -291,7 +299,7 @@ int factor_round(okkt_kkt_s* k, int64_t B, const std::vector<int32_t>& list, con
   return OKKT_OK;
 }
 
-void items_state_reset(KktItems* I) { I->formed_B = I->factored_B = I->rhs_B = I->dir_B = 0; }
+void items_state_reset(KktItems* I) { I->formed_B = I->factored_B = I->rhs_B = I->dir_B = I->solved_B = 0; I->dxnorm_ok = false; }
 
 }  // namespace
 
@@ -303,6 +311,14 @@ void kkt_items_free(okkt_kkt_s* k) {
   for (void* p : I->allocs) (void)hipFree(p);
   delete I;
   k->items = nullptr;
+}
+int kkt_items_gate(okkt_kkt_s* k, const char* what, int64_t B) { return items_gate(k, what, B, true); }
+void kkt_items_spmv(okkt_kkt_s* k, int lpr, int64_t rows, int64_t nl, const int64_t* ptr, const int* idx, const double* vals, int64_t vals_stride,
+                    const double* x, int64_t x_stride, double* y, int64_t y_stride, const int* d_list) {
+  SEGB_LAUNCH(kb_seg_spmv, lpr, rows, nl, kk_stream(k), rows, ptr, idx, vals, vals_stride, x, x_stride, kNoVec, (int64_t)0, kNoVec, (int64_t)0, 0.0, y, y_stride, d_list);
+}
+void kkt_items_hess(okkt_kkt_s* k, int64_t nl, const double* x, int64_t x_stride, double* y, int64_t y_stride, const int* d_list) {
+  SEGB_LAUNCH(kb_seg_hess, k->lprH, k->n, nl, kk_stream(k), k->items->S, k->Hrp, k->Hrj, k->Hp, k->Hi, x, x_stride, y, y_stride, d_list);
 }
 }  // namespace okkt
 
@@ -477,7 +493,7 @@ int okkt_kkt_items_factor(okkt_kkt_handle k, int64_t B, const double* delta, okk
   KktItems* I = k->items;
   if (I->formed_B < B) return ki_fail(k, OKKT_ERR_INVALID, "kkt solver not ready to factor: form_system has not been called");
   try {
-    I->factored_B = I->dir_B = 0;
+    I->factored_B = I->dir_B = I->solved_B = 0;
     k->t_factor_ms = 0.0;
     k->tm_factor.reset();
     ItemsLoop L;
@@ -507,7 +523,7 @@ int okkt_kkt_items_ipopt_strategy(okkt_kkt_handle k, int64_t B, const double* de
     if (pars) P = *pars;
     static const bool scan = !(getenv("OKKT_DIAG_DOM_SCAN") && atoi(getenv("OKKT_DIAG_DOM_SCAN")) == 0);
     hipStream_t st = kk_stream(k);
-    I->factored_B = I->dir_B = 0;
+    I->factored_B = I->dir_B = I->solved_B = 0;
     k->t_factor_ms = 0.0;
     k->tm_factor.reset();
     const size_t nb = (size_t)B;
@@ -616,7 +632,7 @@ int okkt_kkt_items_system_rhs(okkt_kkt_handle k, int64_t B, const double* grad, 
   KktItemSlots& S = I->S;
   hipStream_t st = kk_stream(k);
   const int64_t n = k->n, m = k->m;
-  I->rhs_B = I->dir_B = 0;
+  I->rhs_B = I->dir_B = I->solved_B = 0;
   for (int64_t b = 0; b < B; ++b) {
     I->mu[(size_t)b] = mu[b];
     I->pen[(size_t)b] = a_norm_penalty[b];
@@ -664,7 +680,8 @@ int okkt_kkt_items_compute_direction(okkt_kkt_handle k, int64_t B, int32_t ItRef
     okkt_solver_s* ls = k->ls;
     hipStream_t st = kk_stream(k);
     const int64_t n = k->n, m = k->m;
-    I->dir_B = 0;
+    I->dir_B = I->solved_B = 0;
+    I->dxnorm_ok = false;
     okkt_kkt_s::Timer& T = k->tm_dir;
     T.reset();
     k->n_solves = 0;
@@ -728,7 +745,7 @@ int okkt_kkt_items_compute_direction(okkt_kkt_handle k, int64_t B, int32_t ItRef
       E.ratio = E.overall / E.rhs_norm;
       err_out[b] = E;
     }
-    I->dir_B = B;
+    I->dir_B = I->solved_B = B;
     return OKKT_OK;
   } catch (const std::bad_alloc&) {
     return ki_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_kkt_items_compute_direction");
@@ -772,7 +789,7 @@ int okkt_kkt_items_select(okkt_kkt_handle k, int64_t b) {
   k->factored = false;
   k->have_dir = has_dir;
   k->have_dxnorm = false;
-  k->sym_dir_ok = has_dir && has_rhs && k->kind == OKKT_KKT_SYMMETRIC;
+  k->sym_dir_ok = b < I->solved_B && has_rhs && k->kind == OKKT_KKT_SYMMETRIC;      // a direction of okkt_kkt_items_set_direction is no solve
   k->clever_vecs_ok = false;
   k->have_rhs = k->have_cur = has_rhs;
   k->cur_Jx = k->Jx;

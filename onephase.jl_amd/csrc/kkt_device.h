@@ -165,6 +165,18 @@ __device__ __forceinline__ double seg_hess(const int64_t* __restrict__ Hrp, cons
   const double v2 = seg_dot<LPR>(Hp, Hi, Hx, x, i, sub);
   return (v1 + v2) - Hdiag[i] * x[i];
 }
+// y = hess_product(x): one group of LPR lanes per row
+template <int LPR>
+__device__ __forceinline__ void kd_seg_hess(int64_t n, const int64_t* __restrict__ Hrp, const int* __restrict__ Hrj, const double* __restrict__ Hcsr,
+                                            const int64_t* __restrict__ Hp, const int* __restrict__ Hi, const double* __restrict__ Hx,
+                                            const double* __restrict__ Hdiag, const double* __restrict__ x, double* __restrict__ y) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = t / LPR;
+  const int sub = (int)(t % LPR);
+  const int64_t i = row < n ? row : n - 1;
+  const double h = seg_hess<LPR>(Hrp, Hrj, Hcsr, Hp, Hi, Hx, Hdiag, x, i, sub);
+  if (sub == 0 && row < n) y[i] = h;
+}
 __device__ __forceinline__ double nan_max(double a, double b) { return (a != a || b != b) ? NAN : fmax(a, b); }
 // per-workgroup maxima of NV values per thread (NaN propagates like Julia's norm(., Inf)); slot v of workgroup b -> part[b * 8 + v]
 template <int NV>

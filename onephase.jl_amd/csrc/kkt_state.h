@@ -150,4 +150,11 @@ inline hipStream_t kk_stream(okkt_kkt_s* k) { return k->ls->stream; }
 inline dim3 seg_grid(int64_t rows, int lpr) { return dim3((unsigned)std::max<int64_t>(1, (rows * lpr + 255) / 256)); }
 // the slots of the KKT batch and the synchronisation before them (kkt_batch.hip); okkt_kkt_destroy calls it
 void kkt_items_free(okkt_kkt_s* k);
+// what ls_batch.hip shares with kkt_batch.hip: the gate of the family (eligible handle, a standing reservation of at least B), and the
+// batched products on the items' values -- y_b = A_b x_b over the rows of (ptr, idx) with lpr lanes per row, and y_b = hess_product(x_b)
+// with the item's H -- for the nl listed slots (d_list NULL: slots 0 .. nl-1), enqueued on the handle's stream
+int kkt_items_gate(okkt_kkt_s* k, const char* what, int64_t B);
+void kkt_items_spmv(okkt_kkt_s* k, int lpr, int64_t rows, int64_t nl, const int64_t* ptr, const int* idx, const double* vals, int64_t vals_stride,
+                    const double* x, int64_t x_stride, double* y, int64_t y_stride, const int* d_list);
+void kkt_items_hess(okkt_kkt_s* k, int64_t nl, const double* x, int64_t x_stride, double* y, int64_t y_stride, const int* d_list);
 }  // namespace okkt

@@ -21,150 +21,27 @@
 #include <string>
 
 #include "kkt_state.h"
+#include "ls_device.h"
+#include "ls_finish.h"
 
 using namespace okkt;
 
 namespace {
 
-enum { kSum = 0, kNanMax = 1, kNanMin = 2 };
-constexpr int kMaxBlocks = 256;
+constexpr int kMaxBlocks = kLsMaxBlocks;
 
-template <int NCH>
-struct Channels { int op[NCH]; double init[NCH]; };
-
-__device__ __forceinline__ double combine(int op, double a, double b) {
-  if (op == kSum) return a + b;
-  if (a != a || b != b) return NAN;
-  return op == kNanMax ? fmax(a, b) : fmin(a, b);
-}
-__device__ __forceinline__ double nan_min(double a, double b) { return (a != a || b != b) ? NAN : fmin(a, b); }
-
-template <int NCH>
-__device__ void block_reduce(double (&v)[NCH], const Channels<NCH>& ch, double* out) {
-  __shared__ double sh[NCH][256];
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) sh[c][t] = v[c];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) {
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) sh[c][t] = combine(ch.op[c], sh[c][t], sh[c][t + o]);
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) out[c] = sh[c][0];
-  }
-}
-
+// the bodies, the maps and the reduction: ls_device.h (shared with the batched kernels of ls_batch.hip)
 // partials: part[block * NCH + c]
 template <int NCH, typename F>
 __global__ __launch_bounds__(256) void k_map_reduce(int64_t n, F f, Channels<NCH> ch, double* __restrict__ part) {
-  double acc[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) acc[c] = ch.op[c] == kSum ? 0.0 : ch.init[c];
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-    double v[NCH];
-    f(i, v);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) acc[c] = combine(ch.op[c], acc[c], v[c]);
-  }
-  block_reduce<NCH>(acc, ch, part + (size_t)blockIdx.x * NCH);
+  ld_map_reduce<NCH>(n, f, ch, part);
 }
 template <int NCH>
 __global__ __launch_bounds__(256) void k_reduce_final(int nb, Channels<NCH> ch, const double* __restrict__ part, double* __restrict__ out) {
-  double acc[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) acc[c] = ch.op[c] == kSum ? 0.0 : ch.init[c];
-  for (int b = threadIdx.x; b < nb; b += 256) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) acc[c] = combine(ch.op[c], acc[c], part[(size_t)b * NCH + c]);
-  }
-  block_reduce<NCH>(acc, ch, out);
+  ld_reduce_final<NCH>(nb, ch, part, out);
 }
-
-// ---- the maps ------------------------------------------------------------------------------------------------
-struct MapAbs {   // norm(v, Inf)
-  const double* v;
-  __device__ void operator()(int64_t i, double (&o)[1]) const { o[0] = fabs(v[i]); }
-};
-// -dir ./ (val - frac .* min.(s, thr)): simple_max_step with lb = frac .* lb_s_thres (frac_boundary.jl:3-15,31-35)
-struct MapRatioS {
-  const double *val, *dir, *frac, *s;
-  double thr;
-  __device__ void operator()(int64_t i, double (&o)[1]) const {
-    const double lb = frac[i] * nan_min(s[i], thr);
-    o[0] = -dir[i] / (val[i] - lb);
-  }
-};
-// s_new .>= frac .* min.(s, thr) (move.jl:15; frac_boundary.jl:22-28): 1 / 0, reduced with min
-struct MapSBound {
-  const double *s_new, *frac, *s;
-  double thr;
-  __device__ void operator()(int64_t i, double (&o)[1]) const { o[0] = s_new[i] >= frac[i] * nan_min(s[i], thr) ? 1.0 : 0.0; }
-};
-// dual_bounds (move.jl:28-80) entry i as (candidate for lb, candidate for ub, index if it resets the interval),
-// counted only behind the last reset `after`; and -dy ./ (y_cand - frac .* y * min(1, |dx|_inf)) (line_search.jl:85-86)
-struct MapDualBounds {
-  const double *s_c, *y_c, *dy, *frac, *y;
-  double mu, comp_feas, nxmin;
-  int64_t after;
-  __device__ void operator()(int64_t i, double (&o)[4]) const {
-    const double s = s_c[i], d = dy[i], yc = y_c[i];
-    const double safety_factor = 1.001, safety_add = 0.0;
-    const double ub_dyi = mu / (comp_feas * s * d) - yc / d;
-    const double lb_dyi = mu * comp_feas / (s * d) - yc / d;
-    double a = -INFINITY, b = INFINITY, r = -1.0;
-    if (d > 0.0) { a = lb_dyi * safety_factor + safety_add; b = ub_dyi / safety_factor - safety_add; }
-    else if (d < 0.0) { a = ub_dyi * safety_factor + safety_add; b = lb_dyi / safety_factor - safety_add; }
-    else if (lb_dyi >= 0.0 || ub_dyi <= 0.0) r = (double)i;
-    if (i <= after) { a = -INFINITY; b = INFINITY; }
-    o[0] = a; o[1] = b; o[2] = r;
-    o[3] = -d / (yc - frac[i] * y[i] * nxmin);
-  }
-};
-// m-part of the predicted reductions (eval.jl:236-273): (J dx).^2 . (y ./ s), |comp|, |comp_predicted|
-struct MapPredM {
-  const double *v, *s, *y, *dy, *ds;
-  double mu, mu_new, step;
-  __device__ void operator()(int64_t i, double (&o)[3]) const {
-    const double si = s[i], yi = y[i];
-    o[0] = v[i] * v[i] * (yi / si);
-    o[1] = fabs(si * yi - mu);
-    o[2] = fabs(si * yi + dy[i] * si * step + ds[i] * yi * step - mu_new);
-  }
-};
-// n-part: dx . (grad - J'w) and dx . (H dx)
-struct MapPredN {
-  const double *dx, *grad, *jtw, *h;
-  __device__ void operator()(int64_t i, double (&o)[2]) const {
-    o[0] = dx[i] * (grad[i] - jtw[i]);
-    o[1] = dx[i] * h[i];
-  }
-};
-// move_dual (move.jl:100-112): res . q and q . q, first n entries / last m entries
-struct MapDualStepN {
-  const double *grad, *jtw, *jtdy;
-  double scale_D;
-  __device__ void operator()(int64_t i, double (&o)[2]) const {
-    const double q = scale_D * jtdy[i], res = scale_D * (grad[i] - jtw[i]);
-    o[0] = res * q; o[1] = q * q;
-  }
-};
-struct MapDualStepM {
-  const double *s_c, *y_c, *dy;
-  double scale_mu, mu;
-  __device__ void operator()(int64_t i, double (&o)[2]) const {
-    const double q = scale_mu * s_c[i] * dy[i], res = -scale_mu * (s_c[i] * y_c[i] - mu);
-    o[0] = res * q; o[1] = q * q;
-  }
-};
 __global__ void k_axpb(int64_t n, double a, const double* __restrict__ x, double b, double* __restrict__ o, int recip) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) o[i] = (recip ? a / x[i] : a * x[i]) + b;   // recip: a ./ x + b
+  ld_axpb(n, a, x, b, o, recip);
 }
 
 int ls_fail(okkt_kkt_s* k, int code, const char* msg) { k->err = msg; return code; }
@@ -213,7 +90,7 @@ int map_reduce(okkt_kkt_s* k, int64_t n, const F& f, const Channels<NCH>& ch, do
   return OKKT_OK;
 }
 
-// norm(dir.x, Inf) and lb_s_thres's scalar  norm * norm^ex  (frac_boundary.jl:3-10); pow on the host (one libm for all)
+// norm(dir.x, Inf), once per direction (the scalar steps behind the reductions: ls_finish.h)
 int dx_norm(okkt_kkt_s* k, double* nx) {
   if (k->have_dxnorm) { *nx = k->dxnorm; return OKKT_OK; }     // once per direction
   Channels<1> ch{{kNanMax}, {0.0}};
@@ -221,9 +98,6 @@ int dx_norm(okkt_kkt_s* k, double* nx) {
   if (rc == OKKT_OK) { k->dxnorm = *nx; k->have_dxnorm = true; }
   return rc;
 }
-double thres_scalar(double nx, double ex) { return nx * std::pow(nx, ex); }
-double jl_min(double a, double b) { return (a != a || b != b) ? NAN : std::min(a, b); }
-double jl_max(double a, double b) { return (a != a || b != b) ? NAN : std::max(a, b); }
 
 }  // namespace
 
@@ -250,7 +124,7 @@ int okkt_kkt_max_step_primal(okkt_kkt_handle k, const double* frac_bd_predict, d
   double ratio = 1.0;
   Channels<1> ch{{kNanMax}, {1.0}};
   if ((rc = map_reduce<1>(k, k->m, MapRatioS{k->s, k->ds, k->ls_m[0], k->s, thres_scalar(nx, ex)}, ch, &ratio)) != OKKT_OK) return rc;
-  *step_size_P = 1.0 / ratio;
+  *step_size_P = step_from_ratio(ratio);
   if (dx_norm_inf) *dx_norm_inf = nx;
   return OKKT_OK;
 }
@@ -292,10 +166,7 @@ int okkt_kkt_dual_step_range(okkt_kkt_handle k, const double* s_cand, const doub
     if ((rc = map_reduce<4>(k, k->m, f, ch, r)) != OKKT_OK) return rc;
     r[3] = ratio_y;
   }
-  double lb = r[0], ub = r[1];
-  if (!std::isfinite(lb) || !std::isfinite(ub)) { lb = 0.0; ub = -1.0; }   // isbad(lb) || isbad(ub), move.jl:74-76
-  ub = jl_min(ub, 1.0 / r[3]);
-  *lb_out = lb; *ub_out = ub;
+  dual_range_finish(r, lb_out, ub_out);
   return OKKT_OK;
 }
 
@@ -322,10 +193,7 @@ int okkt_kkt_predicted_reduction(okkt_kkt_handle k, const double* grad, double m
     Channels<2> ch{{kSum, kSum}, {0.0, 0.0}};
     if ((rc = map_reduce<2>(k, n, MapPredN{k->dx, k->ls_n[0], k->ls_n[1], k->vn1}, ch, rn)) != OKKT_OK) return rc;
   }
-  const double phi_red = step_size * rn[0] + step_size * step_size * 0.5 * (rn[1] + rm[0]);
-  const double C_k = rm[1], P_k = rm[2];
-  const double comp_penalty = m > 0 ? (P_k * P_k * P_k - C_k * C_k * C_k) / (mu * mu) : 0.0;
-  out[0] = phi_red; out[1] = C_k; out[2] = P_k; out[3] = phi_red + comp_penalty;
+  predicted_reduction_finish(m, rm, rn, mu, step_size, out);
   return OKKT_OK;
 }
 
@@ -335,7 +203,7 @@ int okkt_kkt_dual_step(okkt_kkt_handle k, const double* J_nzval_cand, const doub
   int rc = ls_ready(k, true);
   if (rc != OKKT_OK) return rc;
   if (!step_size_D) return OKKT_ERR_INVALID;
-  const double small_step = std::max(lb, std::min(ub, step_size_P));
+  const double small_step = dual_small_step(lb, ub, step_size_P);
   if (dual_ls != 1 && dual_ls != 3) { *step_size_D = ub; return OKKT_OK; }
   const int64_t n = k->n, m = k->m;
   if ((n > 0 && !grad_cand) || (m > 0 && (!s_cand || !y_cand))) return OKKT_ERR_INVALID;
@@ -369,10 +237,7 @@ int okkt_kkt_dual_step(okkt_kkt_handle k, const double* J_nzval_cand, const doub
     if ((rc = map_reduce<2>(k, n, MapDualStepN{k->ls_n[0], k->ls_n[1], k->vn1, scale_D}, ch, rn)) != OKKT_OK) return rc;
   }
   if (m && (rc = map_reduce<2>(k, m, MapDualStepM{k->ls_m[1], k->ls_m[2], k->dy, scale_mu, mu_cand}, ch, rm)) != OKKT_OK) return rc;
-  double sd = (rn[0] + rm[0]) / (rn[1] + rm[1]);
-  sd = jl_min(sd, ub);
-  sd = jl_max(sd, small_step);
-  *step_size_D = sd;
+  *step_size_D = dual_step_finish(rn, rm, ub, small_step);
   return OKKT_OK;
 }
 

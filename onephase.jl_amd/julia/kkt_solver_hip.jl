@@ -438,6 +438,91 @@ function items_select!(k::HIP_KKT_solver, b::Integer, it::Class_iterate)
     k.resident_rhs = nothing
 end
 
+# ---- line-search batches (okkt_kkt_items_max_step_primal ..., DESIGN.md section 8.18): the step-side functions of line_search_hip.jl
+# for the items of a KKT batch, against the iterates of form_system_items! and the directions compute_direction_items! left resident
+# (or set_direction_items!).  Plain ccalls, UNTESTED like the rest of this file.  Per-item vectors are matrices with one COLUMN per
+# item (the [B][m] / [B][n] of the C ABI), per-item scalars vectors of length B; items: nothing for every item, else 0-based slots --
+# inputs and outputs stay indexed by slot, and only the listed slots' outputs are written (a backtracking loop passes the items still
+# in it).  Item b's numbers are bit for bit those of the single-iterate functions on a solver of its own.
+items_arg(items) = items === nothing ? (Ptr{Int32}(C_NULL), Int64(0)) : (pointer(items), Int64(length(items)))
+frac_arg(frac, m) = ndims(frac) == 1 ? Int64(0) : Int64(m)          # one fraction vector for every item, or one column per item
+
+function set_direction_items!(k::HIP_KKT_solver, dx::Matrix{Float64}, dy::Matrix{Float64}, ds::Matrix{Float64})
+    kkt_hip_check(k, "okkt_kkt_items_set_direction", ccall((:okkt_kkt_items_set_direction, OKKT_LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), k.handle, size(dx, 2), dx, dy, ds))
+end
+
+# (step_size_P, norm(dir_b.x, Inf)), vectors of length B
+function max_step_primal_items(k::HIP_KKT_solver, B::Integer, frac_bd_predict::Array{Float64}, ex::Float64; items::Union{Nothing,Vector{Int32}}=nothing)
+    step = fill(NaN, B); nx = fill(NaN, B)
+    GC.@preserve items begin
+        ip, ni = items_arg(items)
+        kkt_hip_check(k, "okkt_kkt_items_max_step_primal", ccall((:okkt_kkt_items_max_step_primal, OKKT_LIB), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int32}, Int64, Ptr{Float64}, Int64, Float64, Ptr{Float64}, Ptr{Float64}),
+            k.handle, B, ip, ni, frac_bd_predict, frac_arg(frac_bd_predict, size(frac_bd_predict, 1)), ex, step, nx))
+    end
+    return step, nx
+end
+
+function s_bound_ok_items(k::HIP_KKT_solver, s_new::Matrix{Float64}, frac_bd::Array{Float64}, ex::Float64; items::Union{Nothing,Vector{Int32}}=nothing)
+    m, B = size(s_new)
+    ok = fill(Int32(-1), B)
+    GC.@preserve items begin
+        ip, ni = items_arg(items)
+        kkt_hip_check(k, "okkt_kkt_items_s_bound_ok", ccall((:okkt_kkt_items_s_bound_ok, OKKT_LIB), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int32}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Ptr{Int32}),
+            k.handle, B, ip, ni, s_new, frac_bd, frac_arg(frac_bd, m), ex, ok))
+    end
+    return ok
+end
+
+# (lb, ub), vectors of length B
+function dual_step_range_items(k::HIP_KKT_solver, s_cand::Matrix{Float64}, y_cand::Matrix{Float64}, mu_cand::Vector{Float64}, comp_feas::Float64,
+                               frac_bd::Array{Float64}; items::Union{Nothing,Vector{Int32}}=nothing)
+    m, B = size(s_cand)
+    lb = fill(NaN, B); ub = fill(NaN, B)
+    GC.@preserve items begin
+        ip, ni = items_arg(items)
+        kkt_hip_check(k, "okkt_kkt_items_dual_step_range", ccall((:okkt_kkt_items_dual_step_range, OKKT_LIB), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int32}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+            k.handle, B, ip, ni, s_cand, y_cand, mu_cand, comp_feas, frac_bd, frac_arg(frac_bd, m), lb, ub))
+    end
+    return lb, ub
+end
+
+# 4 x B: (phi_predicted_reduction_primal_dual, |comp|_inf, |comp_predicted|_inf, merit_function_predicted_reduction) per column
+function predicted_reduction_items(k::HIP_KKT_solver, grad::Matrix{Float64}, mu::Vector{Float64}, dmu::Vector{Float64}, a_norm_penalty::Vector{Float64},
+                                   step_size::Vector{Float64}; items::Union{Nothing,Vector{Int32}}=nothing)
+    B = size(grad, 2)
+    out = fill(NaN, 4, B)
+    GC.@preserve items begin
+        ip, ni = items_arg(items)
+        kkt_hip_check(k, "okkt_kkt_items_predicted_reduction", ccall((:okkt_kkt_items_predicted_reduction, OKKT_LIB), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int32}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            k.handle, B, ip, ni, grad, mu, dmu, a_norm_penalty, step_size, out))
+    end
+    return out
+end
+
+# step_size_D of move_dual per item; J_nzval_cand: nothing (each item's formed J), a vector (one array for every item) or nnz x B
+function dual_step_items(k::HIP_KKT_solver, J_nzval_cand::Union{Nothing,Array{Float64}}, grad_cand::Matrix{Float64}, s_cand::Matrix{Float64},
+                         y_cand::Matrix{Float64}, mu_cand::Vector{Float64}, a_norm_penalty::Vector{Float64}, step_size_P::Vector{Float64},
+                         lb::Vector{Float64}, ub::Vector{Float64}, scale_D::Vector{Float64}, scale_mu::Vector{Float64}, dual_ls::Integer;
+                         items::Union{Nothing,Vector{Int32}}=nothing)
+    B = size(s_cand, 2)
+    out = fill(NaN, B)
+    Jp = J_nzval_cand === nothing ? Ptr{Float64}(C_NULL) : pointer(J_nzval_cand)
+    Js = (J_nzval_cand === nothing || ndims(J_nzval_cand) == 1) ? Int64(0) : Int64(size(J_nzval_cand, 1))
+    GC.@preserve items J_nzval_cand begin
+        ip, ni = items_arg(items)
+        kkt_hip_check(k, "okkt_kkt_items_dual_step", ccall((:okkt_kkt_items_dual_step, OKKT_LIB), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int32}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}),
+            k.handle, B, ip, ni, Jp, Js, grad_cand, s_cand, y_cand, mu_cand, a_norm_penalty, step_size_P, lb, ub, scale_D, scale_mu, dual_ls, out))
+    end
+    return out
+end
+
 # ---- the dense factor of the Schur complement (DESIGN.md section 8.7) on a linear_solver_HIP in Schur mode (okkt_set_schur before the
 # analysis, okkt_factor_schur before these).  UNTESTED like the rest of this file.  Inertias come back as (pos, neg, zero, nonfinite).
 struct OkktInertiaCounts    # okkt_inertia of include/okkt.h

@@ -239,6 +239,11 @@ class HIP_KKT_solver:
         self._items_cur = None
         self._items_delta = None
         self.items_diag_dom_warnings = None
+        # the items that hold a resident direction (compute_direction_items, line_search.set_direction_items), the host copies where
+        # there are any, and d.mu of every item: what the batched step-side functions of line_search.py read
+        self._items_dir_B = 0
+        self._items_dirs = None
+        self._items_dir_mu = None
 
     # ---- initialize! (kkt_system_solver.jl:21-25)
     def initialize_b(self, intial_it):
@@ -606,6 +611,7 @@ class HIP_KKT_solver:
         self._items_B = B
         self._items_its = list(its)
         self._items_cur = None
+        self._items_dir_B, self._items_dirs, self._items_dir_mu = 0, None, None
         self.ready = "system_formed"
 
     def _items_formed(self, what):
@@ -701,6 +707,9 @@ class HIP_KKT_solver:
                 d.mu = -(1.0 - eta.mu) * its[b].mu
                 d.primal_scale = -(1.0 - eta.P) * its[b].primal_scale
             dirs.append(d)
+        self._items_dir_B = B
+        self._items_dirs = None if resident else dirs
+        self._items_dir_mu = [-(1.0 - eta.mu) * its[b].mu if eta is not None else 0.0 for b in range(B)]
         if check_nan:
             for b, d in enumerate(dirs):
                 for name, v in (("x", d.x), ("y", d.y), ("s", d.s)):
@@ -728,6 +737,8 @@ class HIP_KKT_solver:
             self._resident_rhs = self.rhs = self._items_cur[2][b]
         else:
             self._resident_rhs = self.rhs = None
+        if self._items_dirs is not None and b < self._items_dir_B:
+            self.dir = self._items_dirs[b]
 
     def min_eig(self, max_steps=0, tol=0.0, scaled=0, with_vector=True):
         """okkt_kkt_min_eig: (info, v) -- the Lanczos estimate of lambda_min(Q(0)), Q(0) = H + J' Sigma J of the last form_system_b, as a
