@@ -11,8 +11,6 @@ using namespace okkt;
 
 namespace {
 
-int small_max_of(const okkt_solver_s* h) { return std::max(32, std::min(h->sopts.small_front_max, 136)); }
-
 // the first reason that applies, in the order of the codes; shape filled when the plan is eligible
 int batch_reason(okkt_solver_s* h, BatchShape& shape, std::string* why) {
   shape = BatchShape();
@@ -72,6 +70,40 @@ int solve_batch_device(okkt_solver_s* h, int64_t B, const double* d_rhs, double*
 
 namespace okkt {
 
+int batch_counts_to_flags(okkt_solver_s* h, BatchWork& W, const char* name, const char* order_words, int64_t B, const int32_t* items, int64_t order, int64_t n, int64_t m,
+                          int sym_kind, okkt_inertia* inertia_out, int32_t* flag_out) {
+  for (int64_t j = 0; j < B; ++j) {
+    const int64_t b = items ? items[j] : j;
+    const unsigned long long* c = W.raw.data() + (size_t)b * kCountStride;
+    int64_t* in = W.inertia.data() + (size_t)b * 4;
+    for (int q = 0; q < 4; ++q) in[q] = (int64_t)c[q];
+    if (in[0] + in[1] + in[2] + in[3] != order)
+      return solver_set_error(h, OKKT_ERR_INTERNAL, std::string(name) + ": the pivot counts of item " + std::to_string(b) + " do not add up to " + order_words);
+    int flag = 0;
+    if (in[3] == 0) flag = sym_kind == OKKT_SYM_DEFINITE ? (in[0] == n ? 1 : 0) : ((in[0] == n && in[1] == m) ? 1 : 0);
+    W.flags[(size_t)b] = flag;
+    if (inertia_out) { inertia_out[b].pos = in[0]; inertia_out[b].neg = in[1]; inertia_out[b].zero = in[2]; inertia_out[b].nonfinite = in[3]; }
+    if (flag_out) flag_out[b] = flag;
+  }
+  return OKKT_OK;
+}
+
+int batch_select_slot(okkt_solver_s* h, BatchWork& W, const char* name, int64_t b) {
+  h->factored = false;
+  ++h->factor_seq;      // the handle's own dense factor, a selected inverse, a pivot report of the previous factor are stale from here on
+  h->sc.valid = false;
+  std::string e = batch_select_enqueue(h->N, W, b);      // (a scenario batch: the arena holds the item's Schur front where the handle's own plan has it)
+  if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
+  int rc = stream_sync(h, name);
+  if (rc != OKKT_OK) return rc;
+  const int64_t* in = W.inertia.data() + (size_t)b * 4;
+  h->a11_inertia.pos = in[0]; h->a11_inertia.neg = in[1]; h->a11_inertia.zero = in[2]; h->a11_inertia.nonfinite = in[3];
+  h->N.early_exited = false;
+  h->last_failed = W.flags[(size_t)b] == 0;
+  h->factored = true;
+  return OKKT_OK;
+}
+
 int solver_factor_batch_device(okkt_solver_s* h, int64_t B, const double* d_vals, int64_t val_stride, const double* shift, int64_t nshift, int64_t n, int64_t m,
                                int sym_kind, okkt_inertia* inertia_out, int32_t* flag_out, bool zero_tol, const int32_t* items, int64_t nslots) {
   int rc = batch_ready(h, "okkt_factor_batch", items ? std::max<int64_t>(nslots, 1) : B);
@@ -120,20 +152,7 @@ int solver_factor_batch_device(okkt_solver_s* h, int64_t B, const double* d_vals
     W.inertia.assign((size_t)nout * 4, 0);
     W.flags.assign((size_t)nout, 0);
   }
-  for (int64_t j = 0; j < B; ++j) {
-    const int64_t b = items ? items[j] : j;
-    const unsigned long long* c = W.raw.data() + (size_t)b * kCountStride;
-    int64_t* in = W.inertia.data() + (size_t)b * 4;
-    for (int q = 0; q < 4; ++q) in[q] = (int64_t)c[q];
-    if (in[0] + in[1] + in[2] + in[3] != h->S.n)
-      return solver_set_error(h, OKKT_ERR_INTERNAL, "okkt_factor_batch: the pivot counts of item " + std::to_string(b) + " do not add up to the matrix order");
-    // the flag of okkt_factor (solver_factor_device): no non-finite pivot, then the inertia
-    int flag = 0;
-    if (in[3] == 0) flag = sym_kind == OKKT_SYM_DEFINITE ? (in[0] == n ? 1 : 0) : ((in[0] == n && in[1] == m) ? 1 : 0);
-    W.flags[(size_t)b] = flag;
-    if (inertia_out) { inertia_out[b].pos = in[0]; inertia_out[b].neg = in[1]; inertia_out[b].zero = in[2]; inertia_out[b].nonfinite = in[3]; }
-    if (flag_out) flag_out[b] = flag;
-  }
+  if ((rc = batch_counts_to_flags(h, W, "okkt_factor_batch", "the matrix order", B, items, h->S.n, n, m, sym_kind, inertia_out, flag_out)) != OKKT_OK) return rc;
   // with a list: the slots it does not name keep the factor, the counts and the flag an earlier factorisation left them
   // (a list that leaves slots out is accepted only behind a factorisation of all nslots, above: every slot below factored_B holds a factor)
   W.factored_B = items ? std::max(kept_B, nslots) : B;
@@ -227,19 +246,9 @@ int okkt_factor_batch(okkt_handle h, int64_t B, const double* nzval, int64_t val
   return fence(h, "okkt_factor_batch", [&]() -> int {
     int rc = batch_ready(h, "okkt_factor_batch", B);
     if (rc != OKKT_OK) return rc;
-    const int64_t nnz = h->S.nnz_in;
-    if (val_stride != 0 && val_stride < nnz) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_factor_batch: val_stride must be 0 or at least the number of entries");
-    const int64_t copies = val_stride == 0 ? 1 : B;
-    DevTemp vals;
-    if (!vals.alloc(std::max<int64_t>(copies * nnz, 1))) return solver_set_error(h, OKKT_ERR_ALLOC, "okkt_factor_batch: the device copy of the values does not fit");
-    if (nnz > 0) {
-      const hipError_t he = hipMemcpy2DAsync(vals.p, (size_t)nnz * sizeof(double), nzval, (size_t)std::max(val_stride, nnz) * sizeof(double), (size_t)nnz * sizeof(double),
-                                             (size_t)copies, hipMemcpyHostToDevice, h->stream);
-      if ((rc = hip_check(h, he, "okkt_factor_batch: nzval upload")) != OKKT_OK) return rc;
-    }
-    rc = solver_factor_batch_device(h, B, vals.p, val_stride == 0 ? 0 : nnz, shift, nshift, n, m, sym_kind, inertia_out, flag_out);
-    (void)hipStreamSynchronize(h->stream);      // the copy of the values is freed behind everything that reads it
-    return rc;
+    return batch_factor_host_values(h, "okkt_factor_batch", B, nzval, val_stride, [&](const double* d_vals, int64_t stride) {
+      return solver_factor_batch_device(h, B, d_vals, stride, shift, nshift, n, m, sym_kind, inertia_out, flag_out);
+    });
   }, true);
 }
 
@@ -270,18 +279,7 @@ int okkt_batch_select(okkt_handle h, int64_t b) {
     if (rc != OKKT_OK) return rc;
     BatchWork& W = h->bt;
     if (b < 0 || b >= W.factored_B) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_batch_select: b outside the items of the last okkt_factor_batch");
-    h->factored = false;
-    ++h->factor_seq;      // a selected inverse, a pivot report of the previous factor are stale from here on
-    h->sc.valid = false;
-    std::string e = batch_select_enqueue(h->N, W, b);
-    if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
-    if ((rc = stream_sync(h, "okkt_batch_select")) != OKKT_OK) return rc;
-    const int64_t* in = W.inertia.data() + (size_t)b * 4;
-    h->a11_inertia.pos = in[0]; h->a11_inertia.neg = in[1]; h->a11_inertia.zero = in[2]; h->a11_inertia.nonfinite = in[3];
-    h->N.early_exited = false;
-    h->last_failed = W.flags[(size_t)b] == 0;
-    h->factored = true;
-    return OKKT_OK;
+    return batch_select_slot(h, W, "okkt_batch_select", b);
   });
 }
 

@@ -12,8 +12,6 @@ using namespace okkt;
 
 namespace {
 
-int small_max_of(const okkt_solver_s* h) { return std::max(32, std::min(h->sopts.small_front_max, 136)); }
-
 // the first reason that applies, in the order of the codes; shape filled when the plan is eligible
 int sbatch_reason(okkt_solver_s* h, SchurBatchShape& shape, std::string* why) {
   shape = SchurBatchShape();
@@ -83,19 +81,7 @@ int factor_device(okkt_solver_s* h, int64_t B, const double* d_vals, int64_t val
   W.w.mode_used = OKKT_BATCH_LEVEL;
   W.w.inertia.assign((size_t)B * 4, 0);
   W.w.flags.assign((size_t)B, 0);
-  for (int64_t b = 0; b < B; ++b) {
-    const unsigned long long* c = W.w.raw.data() + (size_t)b * kCountStride;
-    int64_t* in = W.w.inertia.data() + (size_t)b * 4;
-    for (int q = 0; q < 4; ++q) in[q] = (int64_t)c[q];
-    if (in[0] + in[1] + in[2] + in[3] != order)
-      return solver_set_error(h, OKKT_ERR_INTERNAL, std::string(what) + ": the pivot counts of item " + std::to_string(b) + " do not add up to dim - ns");
-    // the flag of okkt_factor_schur (solver_factor_device): no non-finite pivot, then the inertia of A11
-    int flag = 0;
-    if (in[3] == 0) flag = sym_kind == OKKT_SYM_DEFINITE ? (in[0] == n1 ? 1 : 0) : ((in[0] == n1 && in[1] == m1) ? 1 : 0);
-    W.w.flags[(size_t)b] = flag;
-    if (inertia_out) { inertia_out[b].pos = in[0]; inertia_out[b].neg = in[1]; inertia_out[b].zero = in[2]; inertia_out[b].nonfinite = in[3]; }
-    if (flag_out) flag_out[b] = flag;
-  }
+  if ((rc = batch_counts_to_flags(h, W.w, what, "dim - ns", B, nullptr, order, n1, m1, sym_kind, inertia_out, flag_out)) != OKKT_OK) return rc;
   W.w.factored_B = B;
   return OKKT_OK;
 }
@@ -297,19 +283,9 @@ int okkt_factor_schur_batch(okkt_handle h, int64_t B, const double* nzval, int64
   return fence(h, "okkt_factor_schur_batch", [&]() -> int {
     int rc = sbatch_ready(h, "okkt_factor_schur_batch", B);
     if (rc != OKKT_OK) return rc;
-    const int64_t nnz = h->S.nnz_in;
-    if (val_stride != 0 && val_stride < nnz) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_factor_schur_batch: val_stride must be 0 or at least the number of entries");
-    const int64_t copies = val_stride == 0 ? 1 : B;
-    DevTemp vals;
-    if (!vals.alloc(std::max<int64_t>(copies * nnz, 1))) return solver_set_error(h, OKKT_ERR_ALLOC, "okkt_factor_schur_batch: the device copy of the values does not fit");
-    if (nnz > 0) {
-      const hipError_t he = hipMemcpy2DAsync(vals.p, (size_t)nnz * sizeof(double), nzval, (size_t)std::max(val_stride, nnz) * sizeof(double), (size_t)nnz * sizeof(double),
-                                             (size_t)copies, hipMemcpyHostToDevice, h->stream);
-      if ((rc = hip_check(h, he, "okkt_factor_schur_batch: nzval upload")) != OKKT_OK) return rc;
-    }
-    rc = factor_device(h, B, vals.p, val_stride == 0 ? 0 : nnz, shift, nshift, n1, m1, sym_kind, inertia_items, flag_items);
-    (void)hipStreamSynchronize(h->stream);      // the copy of the values is freed behind everything that reads it
-    return rc;
+    return batch_factor_host_values(h, "okkt_factor_schur_batch", B, nzval, val_stride, [&](const double* d_vals, int64_t stride) {
+      return factor_device(h, B, d_vals, stride, shift, nshift, n1, m1, sym_kind, inertia_items, flag_items);
+    });
   }, true);
 }
 
@@ -365,18 +341,7 @@ int okkt_schur_batch_select(okkt_handle h, int64_t b) {
     if (rc != OKKT_OK) return rc;
     SchurBatchWork& W = h->sb;
     if (b < 0 || b >= W.w.factored_B) return solver_set_error(h, OKKT_ERR_INVALID, "okkt_schur_batch_select: b outside the items of the last okkt_factor_schur_batch");
-    h->factored = false;
-    ++h->factor_seq;      // the handle's own dense factor, a selected inverse, a pivot report of the previous factor are stale from here on
-    h->sc.valid = false;
-    std::string e = batch_select_enqueue(h->N, W.w, b);      // the arena holds the item's Schur front where the handle's own plan has it
-    if (!e.empty()) return solver_set_error(h, OKKT_ERR_HIP, e);
-    if ((rc = stream_sync(h, "okkt_schur_batch_select")) != OKKT_OK) return rc;
-    const int64_t* in = W.w.inertia.data() + (size_t)b * 4;
-    h->a11_inertia.pos = in[0]; h->a11_inertia.neg = in[1]; h->a11_inertia.zero = in[2]; h->a11_inertia.nonfinite = in[3];
-    h->N.early_exited = false;
-    h->last_failed = W.w.flags[(size_t)b] == 0;
-    h->factored = true;
-    return OKKT_OK;
+    return batch_select_slot(h, W.w, "okkt_schur_batch_select", b);
   });
 }
 

@@ -1,5 +1,6 @@
-// What the files of the C ABI layer (api.cpp, api_refine.cpp, api_condest.cpp, api_schur.cpp, api_selinv.cpp) share: the exception
-// fence, the staging of host-side arguments, the gates, the batching of right-hand sides.  Defined in api.cpp unless noted.
+// What the files of the C ABI layer (api.cpp, api_refine.cpp, api_condest.cpp, api_schur.cpp, api_selinv.cpp, api_batch.cpp,
+// api_batch_schur.cpp) share: the exception fence, the staging of host-side arguments, the gates, the batching of right-hand sides, the
+// host side of a batched factorisation.  Defined in api.cpp unless noted.
 #pragma once
 #include <algorithm>
 #include <new>
@@ -64,6 +65,38 @@ inline int for_rhs_batches(okkt_solver_s* h, int64_t nrhs, F&& body) {
   }
   return OKKT_OK;
 }
+
+// ---- what the uniform and the scenario batches share (api_batch.cpp defines, api_batch_schur.cpp uses) -------------------------------
+// small_front_max as numeric_setup clamps it
+inline int small_max_of(const okkt_solver_s* h) { return std::max(32, std::min(h->sopts.small_front_max, 136)); }
+// The host-values form of a batched factorisation, behind the entry's own ready check: the val_stride check, B (or with val_stride 0 one)
+// sets of values to the device, device_factor(d_vals, device stride), and the wait that keeps the copy alive for everything that reads it.
+// name: the entry's, the prefix of every message
+template <class F>
+inline int batch_factor_host_values(okkt_solver_s* h, const char* name, int64_t B, const double* nzval, int64_t val_stride, F&& device_factor) {
+  const std::string what = name;
+  const int64_t nnz = h->S.nnz_in;
+  if (val_stride != 0 && val_stride < nnz) return solver_set_error(h, OKKT_ERR_INVALID, what + ": val_stride must be 0 or at least the number of entries");
+  const int64_t copies = val_stride == 0 ? 1 : B;
+  DevTemp vals;
+  if (!vals.alloc(std::max<int64_t>(copies * nnz, 1))) return solver_set_error(h, OKKT_ERR_ALLOC, what + ": the device copy of the values does not fit");
+  int rc;
+  if (nnz > 0) {
+    const hipError_t he = hipMemcpy2DAsync(vals.p, (size_t)nnz * sizeof(double), nzval, (size_t)std::max(val_stride, nnz) * sizeof(double), (size_t)nnz * sizeof(double),
+                                           (size_t)copies, hipMemcpyHostToDevice, h->stream);
+    if ((rc = hip_check(h, he, (what + ": nzval upload").c_str())) != OKKT_OK) return rc;
+  }
+  rc = device_factor(vals.p, val_stride == 0 ? 0 : nnz);
+  (void)hipStreamSynchronize(h->stream);      // the copy of the values is freed behind everything that reads it
+  return rc;
+}
+// W.raw (the counters of the slots) -> W.inertia and W.flags of the B items (items: the slots of an item list, NULL: 0 .. B - 1), and
+// the caller's outputs where given.  The flag is okkt_factor's (solver_factor_device): no non-finite pivot, then the inertia (n, m).
+// OKKT_ERR_INTERNAL "<name>: the pivot counts of item <b> do not add up to <order_words>" when the counts do not sum to order
+int batch_counts_to_flags(okkt_solver_s* h, BatchWork& W, const char* name, const char* order_words, int64_t B, const int32_t* items, int64_t order, int64_t n, int64_t m,
+                          int sym_kind, okkt_inertia* inertia_out, int32_t* flag_out);
+// slot b of a factored batch into the handle's own arena, D and shift: the handle is then factored with the item's inertia and flag
+int batch_select_slot(okkt_solver_s* h, BatchWork& W, const char* name, int64_t b);
 
 // ---- residuals and refinement (api_refine.cpp) ----------------------------------------------------------------------------------
 // device, analysis, no partition (need_factor: not Schur mode, a complete factorisation); the row map

@@ -1,8 +1,9 @@
 // Uniform batches: B systems that share one analysed pattern, every front a small front (gfx950).
 //
-// The per-front code is that of the single-system kernels -- k_front_small (numeric.hip), k_fs_small and k_bs_small (solve.hip) in
-// their forms without in-launch hand-offs -- with one more grid coordinate: the item, whose values, shift, arena, D, counters and
-// sweep vectors are reached through a DevPlan whose numeric pointers are moved to the item's slot.  All index arrays are the plan's.
+// The per-front code IS that of the single-system kernels: front_small_body, fs_small_body and bs_small_body of front_bodies.h, which
+// k_front_small (numeric.hip), k_fs_small and k_bs_small (solve.hip) instantiate too, here in their forms without in-launch hand-offs
+// (FLOW = false).  The kernels of this file add one grid coordinate: the item, whose values, shift, arena, D, counters and sweep vectors
+// are reached through a DevPlan whose numeric pointers are moved to the item's slot (item_plan).  All index arrays are the plan's.
 // The arithmetic of a small front does not depend on the block size (one update per element and pivot, children added one at a time
 // in their fixed order, the duplicate path serial; the sweeps sum a row's terms in one thread, or in one wave in lane order), so item b
 // is bit for bit what okkt_factor / okkt_solve compute for its values on a handle of their own, in both modes.
@@ -15,7 +16,7 @@
 #include <cstdlib>
 
 #include "../../include/okkt.h"
-#include "front_device.h"
+#include "front_bodies.h"
 #include "numeric.h"
 
 namespace okkt {
@@ -27,90 +28,9 @@ namespace okkt {
       return std::string(#expr) + ": " + hipGetErrorString(e__);                   \
   } while (0)
 
-// the plan as item b sees it: numeric state in the item's slot, no limits on the counts (a batch has no early exit)
-__device__ __forceinline__ DevPlan item_plan(DevPlan P, const BatchSlots& S, int b) {
-  P.arena = S.arena + (size_t)b * S.arena_stride;
-  P.dvals = S.dvals + (size_t)b * S.n;
-  P.diagadd = S.diagadd + (size_t)b * S.n;
-  P.xwork = S.xwork + (size_t)b * S.R * S.n;
-  P.zwork = S.zwork + (size_t)b * S.R * S.n;
-  P.cv = S.cv + (size_t)b * S.R * S.sum_r;
-  P.counters = S.counters + (size_t)b * kCountStride;
-  P.want_pos = P.want_neg = -1;
-  return P;
-}
-
 // ------------------------------------------------------------------------------------------
-// factorisation: the fronts task_lo[root] .. root of one task.  A COPY of the loop body of k_front_small<TPB, false> (numeric.hip): a change
-// to either must be made to both, or item b stops being bit for bit okkt_factor's (tests/test_gpu_batch.py compares them)
+// factorisation: front_small_body<TPB, false> on the item's plan, one call per task
 // ------------------------------------------------------------------------------------------
-template <int TPB>
-__device__ __forceinline__ void front_task(const DevPlan& P, int s_root, double tol, double* sm, unsigned& pos, unsigned& neg, unsigned& zer, unsigned& bad) {
-  constexpr int G = TPB / 32;
-  const int tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
-  const int t_lo = P.task_lo[s_root];
-  for (int s = t_lo; s <= s_root; ++s) {
-    const int col0 = P.sn_col0[s];
-    const int k = P.sn_col0[s + 1] - col0;
-    const int f = (int)(P.row_ptr[s + 1] - P.row_ptr[s]);
-    const int ldf = f | 1;
-    double* F = sm;
-    double* wcol = sm + (size_t)ldf * f;
-    double* front = P.arena + P.front_pos[s];
-
-    for (int i = tid; i < ldf * f; i += TPB) F[i] = 0.0;
-    __syncthreads();
-    // original matrix entries of this supernode's columns
-    {
-      const int64_t e0 = P.aent_ptr[s], e1 = P.aent_ptr[s + 1];
-      if (!P.has_dup) {
-        for (int64_t e = e0 + tid; e < e1; e += TPB) {
-          const int dst = (int)P.aent_dst[e];
-          const int lc = dst / f, lr = dst - lc * f;
-          F[lr + lc * ldf] = P.vals[P.aent_src[e]];
-        }
-      } else if (tid == 0) {
-        for (int64_t e = e0; e < e1; ++e) {
-          const int dst = (int)P.aent_dst[e];
-          const int lc = dst / f, lr = dst - lc * f;
-          F[lr + lc * ldf] += P.vals[P.aent_src[e]];
-        }
-      }
-    }
-    __syncthreads();
-    for (int j = tid; j < k; j += TPB) F[j + j * ldf] += P.diagadd[col0 + j];
-    __syncthreads();
-    // extend-add of the children's contribution blocks, one child at a time (fixed order)
-    for (int64_t q = P.child_ptr[s]; q < P.child_ptr[s + 1]; ++q) {
-      const int c = P.children[q];
-      const int kc = P.sn_col0[c + 1] - P.sn_col0[c];
-      const int fc = (int)(P.row_ptr[c + 1] - P.row_ptr[c]);
-      const int rc = fc - kc;
-      const double* C = P.arena + P.front_pos[c] + P.cb_shift[c];
-      const int* rl = P.rel + P.rel_ptr[c];
-      for (int jj = grp; jj < rc; jj += G) {
-        const int pj = rl[jj];
-        const double* Ccol = C + (size_t)(kc + jj) * fc + kc;
-        for (int ii = jj + lane; ii < rc; ii += 32) F[rl[ii] + pj * ldf] += Ccol[ii];
-      }
-      __syncthreads();
-    }
-    ldl_partial_lds<TPB>(F, wcol, ldf, f, k);
-    // write back: L panel (rows >= col), contribution block (lower), D, inertia counts
-    for (int c = grp; c < f; c += G) {
-      double* dst = front + (size_t)c * f + cb_off(P, s, c, k);
-      for (int i = c + lane; i < f; i += 32) dst[i] = F[i + c * ldf];
-    }
-    for (int j = tid; j < k; j += TPB) {
-      const double d = F[j + j * ldf];
-      P.dvals[col0 + j] = d;
-      classify_pivot(d, tol, pos, neg, zer, bad);
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-}
-
 // level mode: blockIdx.x = task of the level, blockIdx.y = item, or with an item list (the delta loop over the items of a KKT batch,
 // DESIGN.md section 8.17, factors the still active items only) the slot items[blockIdx.y]; items = NULL is the identity
 template <int TPB>
@@ -121,7 +41,7 @@ __global__ __launch_bounds__(TPB) void k_batch_front(DevPlan P0, BatchSlots S, c
   DevPlan P = item_plan(P0, S, b);
   P.vals = vals + (size_t)b * val_stride;
   unsigned pos = 0, neg = 0, zer = 0, bad = 0;
-  front_task<TPB>(P, list[blockIdx.x], tol, sm, pos, neg, zer, bad);
+  front_small_body<TPB, false>(P, list[blockIdx.x], tol, sm, nullptr, 0, pos, neg, zer, bad);
   flush_counts(P, 0, pos, neg, zer, bad);
 }
 
@@ -148,138 +68,24 @@ __global__ __launch_bounds__(TPB) void k_batch_item_factor(DevPlan P0, BatchSlot
   __threadfence_block();
   __syncthreads();
   unsigned pos = 0, neg = 0, zer = 0, bad = 0;
-  for (int t = 0; t < ntasks; ++t) front_task<TPB>(P, list[t], tol, sm, pos, neg, zer, bad);
+  for (int t = 0; t < ntasks; ++t) front_small_body<TPB, false>(P, list[t], tol, sm, nullptr, 0, pos, neg, zer, bad);
   flush_counts(P, 0, pos, neg, zer, bad);
 }
 
 // ------------------------------------------------------------------------------------------
-// solves, R right-hand sides.  fs_task / bs_task are COPIES of the loop bodies of k_fs_small<TPB, R, false> / k_bs_small<TPB, R, false>
-// (solve.hip): a change to either must be made to both (tests/test_gpu_batch.py compares the solutions bit for bit)
+// solves, R right-hand sides: fs_small_body / bs_small_body<TPB, R, false> on the item's plan
 // ------------------------------------------------------------------------------------------
-template <int TPB, int R>
-__device__ __forceinline__ void fs_task(const DevPlan& P, int s_root, int ldw, double* sm) {
-  const int tid = threadIdx.x;
-  const int t_lo = P.task_lo[s_root];
-  for (int s = t_lo; s <= s_root; ++s) {      // the task's fronts, children first
-    const int col0 = P.sn_col0[s];
-    const int k = P.sn_col0[s + 1] - col0;
-    const int f = (int)(P.row_ptr[s + 1] - P.row_ptr[s]);
-    const double* L = P.arena + P.front_pos[s];
-    for (int i = tid; i < f; i += TPB)
-#pragma unroll
-      for (int q = 0; q < R; ++q) sm[q * ldw + i] = i < k ? P.xwork[(size_t)q * P.xw_stride + col0 + i] : 0.0;
-    __syncthreads();
-    for (int64_t c = P.child_ptr[s]; c < P.child_ptr[s + 1]; ++c) {
-      const int ch = P.children[c];
-      const int rc = (int)(P.rel_ptr[ch + 1] - P.rel_ptr[ch]);
-      const int* rl = P.rel + P.rel_ptr[ch];
-      const double* cvc = P.cv + P.cv_pos[ch];
-      for (int ii = tid; ii < rc; ii += TPB) {
-        const int d = rl[ii];
-#pragma unroll
-        for (int q = 0; q < R; ++q) sm[q * ldw + d] += cvc[(size_t)q * P.cv_stride + ii];
-      }
-      __syncthreads();
-    }
-    // unit lower triangular k x k
-    for (int j = 0; j < k; ++j) {
-      const double* col = L + (size_t)j * f;
-      for (int i = j + 1 + tid; i < k; i += TPB) {
-        const double l = col[i];
-#pragma unroll
-        for (int q = 0; q < R; ++q) sm[q * ldw + i] -= l * sm[q * ldw + j];
-      }
-      __syncthreads();
-    }
-    // rows below the pivot block: contribution vector for the parent
-    double* cvs = P.cv + P.cv_pos[s];
-    for (int i = k + tid; i < f; i += TPB) {
-      double acc[R];
-#pragma unroll
-      for (int q = 0; q < R; ++q) acc[q] = sm[q * ldw + i];
-      for (int j = 0; j < k; ++j) {
-        const double l = L[(size_t)j * f + i];
-#pragma unroll
-        for (int q = 0; q < R; ++q) acc[q] -= l * sm[q * ldw + j];
-      }
-#pragma unroll
-      for (int q = 0; q < R; ++q) cvs[(size_t)q * P.cv_stride + i - k] = acc[q];
-    }
-    // z = D^-1 y
-    for (int j = tid; j < k; j += TPB) {
-      const double d = P.dvals[col0 + j];
-#pragma unroll
-      for (int q = 0; q < R; ++q) P.zwork[(size_t)q * P.xw_stride + col0 + j] = sm[q * ldw + j] / d;
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-}
-
-template <int TPB, int R>
-__device__ __forceinline__ void bs_task(const DevPlan& P, int s_root, int ldw, double* sm) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  constexpr int NW = TPB / 64;
-  for (int s = s_root; s >= P.task_lo[s_root]; --s) {      // the task's fronts, parents first
-    const int col0 = P.sn_col0[s];
-    const int k = P.sn_col0[s + 1] - col0;
-    const int f = (int)(P.row_ptr[s + 1] - P.row_ptr[s]);
-    const double* L = P.arena + P.front_pos[s];
-    const int* rows = P.rows + P.row_ptr[s];
-    for (int i = tid; i < f; i += TPB) {
-      const int g = rows[i];     // rows[i] = col0 + i for i < k: this front's z; beyond: the ancestors' solution
-      const double* src = i < k ? P.zwork : P.xwork;
-#pragma unroll
-      for (int q = 0; q < R; ++q) sm[q * ldw + i] = src[(size_t)q * P.xw_stride + g];
-    }
-    __syncthreads();
-    // rhs_j = z_j - sum_{i >= k} L[i, j] * x_i
-    for (int j = wv; j < k; j += NW) {
-      const double* col = L + (size_t)j * f;
-      double acc[R];
-#pragma unroll
-      for (int q = 0; q < R; ++q) acc[q] = 0.0;
-      for (int i = k + lane; i < f; i += 64) {
-        const double l = col[i];
-#pragma unroll
-        for (int q = 0; q < R; ++q) acc[q] += l * sm[q * ldw + i];
-      }
-#pragma unroll
-      for (int q = 0; q < R; ++q) {
-        double a = acc[q];
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
-        if (lane == 0) sm[q * ldw + j] -= a;
-      }
-    }
-    __syncthreads();
-    // unit upper triangular (L11^T) k x k, column oriented
-    for (int j = k - 1; j >= 0; --j) {
-      for (int i = tid; i < j; i += TPB) {
-        const double l = L[(size_t)i * f + j];
-#pragma unroll
-        for (int q = 0; q < R; ++q) sm[q * ldw + i] -= l * sm[q * ldw + j];
-      }
-      __syncthreads();
-    }
-    for (int j = tid; j < k; j += TPB)
-#pragma unroll
-      for (int q = 0; q < R; ++q) P.xwork[(size_t)q * P.xw_stride + col0 + j] = sm[q * ldw + j];
-    __threadfence_block();
-    __syncthreads();
-  }
-}
-
 template <int TPB, int R>
 __global__ __launch_bounds__(TPB) void k_batch_fs(DevPlan P0, BatchSlots S, const int* __restrict__ list, int ldw) {
   extern __shared__ __attribute__((aligned(16))) double sm[];      // [R][ldw]
   const DevPlan P = item_plan(P0, S, blockIdx.y);
-  fs_task<TPB, R>(P, list[blockIdx.x], ldw, sm);
+  fs_small_body<TPB, R, false>(P, list[blockIdx.x], ldw, sm, nullptr, 0);
 }
 template <int TPB, int R>
 __global__ __launch_bounds__(TPB) void k_batch_bs(DevPlan P0, BatchSlots S, const int* __restrict__ list, int ldw) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const DevPlan P = item_plan(P0, S, blockIdx.y);
-  bs_task<TPB, R>(P, list[blockIdx.x], ldw, sm);
+  bs_small_body<TPB, R, false>(P, list[blockIdx.x], ldw, sm);
 }
 
 // level mode: xwork[b][q][i] = rhs[b][r0 + q][perm[i]] for q < nr (zero for nr <= q < R)  /  sol[b][r0 + q][perm[i]] = xwork[b][q][i]
@@ -326,8 +132,8 @@ __global__ __launch_bounds__(TPB) void k_batch_item_solve(DevPlan P0, BatchSlots
   }
   __threadfence_block();
   __syncthreads();
-  for (int t = 0; t < ntasks; ++t) fs_task<TPB, R>(P, list[t], ldw, sm);
-  for (int t = ntasks - 1; t >= 0; --t) bs_task<TPB, R>(P, list[t], ldw, sm);
+  for (int t = 0; t < ntasks; ++t) fs_small_body<TPB, R, false>(P, list[t], ldw, sm, nullptr, 0);
+  for (int t = ntasks - 1; t >= 0; --t) bs_small_body<TPB, R, false>(P, list[t], ldw, sm);
   {
     double* dst = sol + ((size_t)b * nrhs + r0) * n;
     for (int i = threadIdx.x; i < n; i += TPB) {

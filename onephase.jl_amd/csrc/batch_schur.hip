@@ -1,6 +1,7 @@
 // Scenario batches: B items in Schur mode on one analysed pattern (gfx950).  The interiors are the level mode
 // of the uniform batches (batch.hip); this file is the item coordinate on the Schur front -- its assembly, the gather and the put of the
-// sweeps -- and the two sums over the items.
+// sweeps -- and the two sums over the items.  The assembly of a column is the single-system body itself (assemble_column of
+// front_bodies.h) on a DevPlan pointed at the item's slot (item_plan), not code of this file; the gather of a row still repeats fwd_gather.
 //
 // No workgroup waits for another inside a launch: no flags, no spins.  Every dependency -- the interiors before the Schur fronts, the
 // fronts before the group partials, the partials before the sum, the sum before the dense factor -- is a launch boundary on the handle's
@@ -14,7 +15,7 @@
 #include <cstdlib>
 
 #include "../../include/okkt.h"
-#include "front_device.h"
+#include "front_bodies.h"
 #include "numeric.h"
 
 namespace okkt {
@@ -29,20 +30,16 @@ static_assert(kSchurBatchGroup == OKKT_SBATCH_GROUP, "the group size of the sums
   } while (0)
 
 // ------------------------------------------------------------------------------------------
-// k_batch_schur_assemble: grid (ceil(ns / 4), B), one wave per (column of the Schur front, item), the column in LDS and written once.
-// From here to the end of the kernel: a COPY of assemble_column<true, true> and of the LDS branch of k_big_assemble<true> (numeric.hip),
-// with the values, the shift and the arena of the item.  A change to either must be made to both, or item b's S_b stops being bit for
-// bit okkt_factor_schur's (tests/test_gpu_schur_batch.py compares them)
+// k_batch_schur_assemble: grid (ceil(ns / 4), B), one wave per (column of the Schur front, item), the column in LDS and written once:
+// the LDS branch of k_big_assemble<true> (numeric.hip) on the item's plan -- assemble_column<true, true> of front_bodies.h, so item b's S_b
+// is bit for bit okkt_factor_schur's
 // ------------------------------------------------------------------------------------------
-constexpr int kSbAsmBatch = 4, kSbAsmUnroll = 4;      // kAsmBatch, kAsmUnroll of numeric.hip
-
-__global__ __launch_bounds__(256) void k_batch_schur_assemble(DevPlan P, BatchSlots S, int s, int lcol, const double* __restrict__ vals, int64_t val_stride) {
+__global__ __launch_bounds__(256) void k_batch_schur_assemble(DevPlan P0, BatchSlots S, int s, int lcol, const double* __restrict__ vals, int64_t val_stride) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int b = blockIdx.y;
-  const double* __restrict__ ivals = vals + (size_t)b * val_stride;
-  const double* arena = S.arena + (size_t)b * S.arena_stride;      // (the front written below lies in it too: no __restrict__)
-  const double* __restrict__ diagadd = S.diagadd + (size_t)b * S.n;
+  DevPlan P = item_plan(P0, S, b);
+  P.vals = vals + (size_t)b * val_stride;
   const int col0 = P.sn_col0[s];
   const int k = P.sn_col0[s + 1] - col0;
   const int f = (int)(P.row_ptr[s + 1] - P.row_ptr[s]);
@@ -50,71 +47,11 @@ __global__ __launch_bounds__(256) void k_batch_schur_assemble(DevPlan P, BatchSl
   if (pc >= f) return;
   const int nrow = f - pc;
   if (nrow > lcol) return;      // (never: lcol >= ns; a column that does not fit is not written rather than written out of bounds)
-  double* col = S.arena + (size_t)b * S.arena_stride + P.front_pos[s] + (size_t)pc * f + pc + cb_off(P, s, pc, k);
+  double* col = P.arena + P.front_pos[s] + (size_t)pc * f + pc + cb_off(P, s, pc, k);
   double* buf = sm + (size_t)wv * lcol;
-  for (int i = lane; i < nrow; i += 64) buf[i] = 0.0;
-  __threadfence_block();
-  if (pc < k) {
-    const int64_t e0 = P.aent_ptr[s];
-    const int ne = (int)(P.aent_ptr[s + 1] - e0);
-    const int64_t* dstv = P.aent_dst + e0;
-    const int64_t gcol = P.bigcol_base[s] + pc;
-    const int lo = (int)(P.acol_lo[gcol] - e0);
-    const int hi = pc + 1 < f ? (int)(P.acol_lo[gcol + 1] - e0) : ne;
-    const int64_t base = (int64_t)pc * f + pc;
-    if (!P.has_dup) {
-      for (int e = lo + lane; e < hi; e += 64) buf[(int)(dstv[e] - base)] = ivals[P.aent_src[e0 + e]];
-    } else if (lane == 0) {
-      for (int e = lo; e < hi; ++e) buf[(int)(dstv[e] - base)] += ivals[P.aent_src[e0 + e]];
-    }
-    __threadfence_block();
-    if (lane == 0) buf[0] += diagadd[col0 + pc];
-    __threadfence_block();
-  }
-  const int64_t gc = P.bigcol_base[s] + pc;
-  const int64_t q0 = P.ea_ptr[gc], q1 = P.ea_ptr[gc + 1];
-  constexpr int NB4 = kSbAsmBatch;
-  for (int64_t q = q0; q < q1; q += NB4) {
-    int64_t src[NB4], rel[NB4];
-    int rc[NB4], jj[NB4];
-#pragma unroll
-    for (int u = 0; u < NB4; ++u) {
-      const EaRec r = P.ea_rec[min(q + u, q1 - 1)];
-      src[u] = r.src; rel[u] = r.rel; rc[u] = r.rc; jj[u] = r.jj;
-    }
-    int d[NB4];
-    double v[NB4];
-#pragma unroll
-    for (int u = 0; u < NB4; ++u) {
-      const int ii = min(jj[u] + lane, rc[u] - 1);
-      d[u] = P.rel[rel[u] + ii] - pc;
-      v[u] = arena[src[u] + ii];
-    }
-#pragma unroll
-    for (int u = 0; u < NB4; ++u) {
-      if (q + u < q1) {       // wave-uniform
-        if (jj[u] + lane < rc[u]) buf[d[u]] += v[u];
-        const int* rl = P.rel + rel[u];
-        const double* Ccol = arena + src[u];
-        int ii = jj[u] + 64 + lane;
-        for (; ii + 64 * (kSbAsmUnroll - 1) < rc[u]; ii += 64 * kSbAsmUnroll) {
-          int dd[kSbAsmUnroll];
-          double vv[kSbAsmUnroll], oo[kSbAsmUnroll];
-#pragma unroll
-          for (int w = 0; w < kSbAsmUnroll; ++w) dd[w] = rl[ii + 64 * w] - pc;
-#pragma unroll
-          for (int w = 0; w < kSbAsmUnroll; ++w) { vv[w] = Ccol[ii + 64 * w]; oo[w] = buf[dd[w]]; }
-#pragma unroll
-          for (int w = 0; w < kSbAsmUnroll; ++w) buf[dd[w]] = oo[w] + vv[w];
-        }
-        for (; ii < rc[u]; ii += 64) buf[rl[ii] - pc] += Ccol[ii];
-        __threadfence_block();
-      }
-    }
-  }
+  assemble_column<true, true>(P, s, pc, f, k, col0, buf);
   for (int i = lane; i < nrow; i += 64) col[i] = buf[i];
 }
-// ------------------------------------------------------------------------------------------ (end of the copy)
 
 // ------------------------------------------------------------------------------------------
 // the sums over the items.  Stage one: thread t of group g adds entry t of the group's items, in item order, from 0.0; neighbouring
@@ -158,7 +95,9 @@ __global__ __launch_bounds__(256) void k_batch_schur_vsum(const double* __restri
 
 // ------------------------------------------------------------------------------------------
 // k_batch_schur_gather: the item coordinate on k_schur_gather (solve.hip).  The body from "w[q] =" to the end of the loop over the records
-// is a COPY of fwd_gather<R> (solve.hip): a change to either must be made to both (tests/test_gpu_schur_batch.py compares r2 bit for bit)
+// is a COPY of fwd_gather<R> (solve.hip): a change to either must be made to both (tests/test_gpu_schur_batch.py compares r2 bit for bit).
+// The one copy left in the batch kernels: a call of fwd_gather, which the compiler optimises on its own with w behind a pointer before it
+// inlines it, costs the R = 4 form 110 registers against 88 and one wave of occupancy
 // ------------------------------------------------------------------------------------------
 template <int R>
 __global__ __launch_bounds__(256) void k_batch_schur_gather(DevPlan P, BatchSlots S, int64_t gcb, int col0, int ns, int nr, double* __restrict__ r2i, double* __restrict__ items,

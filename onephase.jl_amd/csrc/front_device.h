@@ -1,6 +1,7 @@
 // Device code shared by the per-step kernels of numeric.hip and the dataflow kernel of dataflow.hip: pivot classification and
-// counting, the stop flag of the delta loop, the diagonal-block factorisation (diag2_body), the row-parallel triangular
-// solve below it (trsm_body) and the constants of the trailing update.
+// counting, the stop flag of the delta loop, the LDS factorisation of a small front (ldl_partial_lds), the diagonal-block
+// factorisation (diag2_body), the row-parallel triangular solve below it (trsm_body) and the constants of the trailing update.
+// The whole per-front bodies that the batch kernels share with the single-system ones are built on these in front_bodies.h.
 #pragma once
 #include "numeric.h"
 
@@ -496,7 +497,7 @@ __device__ __forceinline__ void trsm_body(const DevPlan& P, int s, int step, int
   if (AG) {
     if (tid == 0) {
       // bounded like every in-launch wait; a wait that runs into its bound is counted as a non-finite pivot and raises the time-out
-      // word (flow_wait does the same): the factorisation fails on its pivot counts instead of solving with a block that never came
+      // word (flow_wait_task of front_bodies.h does the same): the factorisation fails on its pivot counts instead of solving with a block that never came
       int spins = 0;
       while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < epoch && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(2);
       if (spins >= (1 << 22)) { atomicAdd(&P.counters[3], 1ull); atomicExch(&P.counters[5], 1ull); }

@@ -14,7 +14,7 @@
 // Extend-add is deterministic: every destination entry is owned by exactly one workgroup that
 // adds the children's contribution blocks in a fixed order -- no floating-point atomics.
 #include "numeric.h"
-#include "front_device.h"
+#include "front_bodies.h"
 #include "solve_sparse.h"
 #include <map>
 
@@ -51,108 +51,18 @@ __global__ void k_fold_counts(DevPlan P) {
 // ------------------------------------------------------------------------------------------
 // small fronts: one workgroup, front resident in LDS
 // ------------------------------------------------------------------------------------------
-// FLOW (round 3): the tasks of SEVERAL levels in one launch.  `list` holds them level by level, so a task's children tasks have
-// lower block indices (dispatch order = dependency order: a waiting workgroup never keeps its producers from being scheduled).
-// A task raises flags[root] = epoch once its last front is in HBM; a parent waits on the flag of every child that lies outside
-// its own index range.  The contribution blocks travel with agent-scope (sc1) accesses, which the memory side serves: no
-// release / acquire fences.  A banded KKT system (BASELINE config 2) is factored by one launch instead of one per level.
-__device__ __forceinline__ void flow_st(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double flow_ld(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// bounded: a hand-off that never comes ends the wait instead of hanging the GPU -- and is counted as a non-finite pivot (`bad`,
-// slot 0 word 3) and in the time-out word (slot 0 word 5): the factorisation reports a wrong inertia, solves return NaN
-__device__ __forceinline__ void flow_wait(const int* flag, int value, unsigned long long* counters) {
-  if (threadIdx.x == 0) {
-    int spins = 0;
-    while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < value && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(1);
-    if (spins >= (1 << 22)) { atomicAdd(&counters[3], 1ull); atomicExch(&counters[5], 1ull); }
-  }
-  __syncthreads();
-}
-__device__ __forceinline__ void flow_signal(int* flag, int value) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // every storing wave: its stores have been acknowledged
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// (batch.hip, front_task: a copy of this kernel's loop body with FLOW = false, for the uniform batches -- a change here must be made there
-// too: tests/test_gpu_batch.py compares the two bit for bit)
+// the tasks of `list`, one workgroup each (front_small_body, front_bodies.h).  FLOW: the tasks of several levels in one launch; a task
+// raises flags[root] = epoch once its last front is in HBM
 template <int TPB, bool FLOW = false>
 __global__ __launch_bounds__(TPB) void k_front_small(DevPlan P, const int* __restrict__ list, double tol, int* __restrict__ flags = nullptr, int epoch = 0, int wait_epoch = 0) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  constexpr int G = TPB / 32;
-  const int tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
   const int s_root = list[blockIdx.x];
   unsigned pos = 0, neg = 0, zer = 0, bad = 0;
   if (stop_requested_wg(P)) {
     if (FLOW) flow_signal(flags + s_root, epoch);    // the consumers must not wait for a task that will never run
     return;
   }
-  const int t_lo = P.task_lo[s_root];
-  // the task: the fronts task_lo[root] .. root in postorder, children's contribution blocks pass through HBM (the
-  // barrier at the end of an iteration makes the workgroup's stores visible to its own later loads)
-  for (int s = t_lo; s <= s_root; ++s) {
-  const int col0 = P.sn_col0[s];
-  const int k = P.sn_col0[s + 1] - col0;
-  const int f = (int)(P.row_ptr[s + 1] - P.row_ptr[s]);
-  const int ldf = f | 1;
-  double* F = sm;
-  double* wcol = sm + (size_t)ldf * f;
-  double* front = P.arena + P.front_pos[s];
-
-  for (int i = tid; i < ldf * f; i += TPB) F[i] = 0.0;
-  __syncthreads();
-  // original matrix entries of this supernode's columns
-  {
-    const int64_t e0 = P.aent_ptr[s], e1 = P.aent_ptr[s + 1];
-    if (!P.has_dup) {
-      for (int64_t e = e0 + tid; e < e1; e += TPB) {
-        const int dst = (int)P.aent_dst[e];      // f <= 136 here: the offset fits in 32 bits
-        const int lc = dst / f, lr = dst - lc * f;
-        F[lr + lc * ldf] = P.vals[P.aent_src[e]];
-      }
-    } else if (tid == 0) {
-      for (int64_t e = e0; e < e1; ++e) {
-        const int dst = (int)P.aent_dst[e];
-        const int lc = dst / f, lr = dst - lc * f;
-        F[lr + lc * ldf] += P.vals[P.aent_src[e]];
-      }
-    }
-  }
-  __syncthreads();
-  for (int j = tid; j < k; j += TPB) F[j + j * ldf] += P.diagadd[col0 + j];
-  __syncthreads();
-  // extend-add of the children's contribution blocks, one child at a time (fixed order)
-  for (int64_t q = P.child_ptr[s]; q < P.child_ptr[s + 1]; ++q) {
-    const int c = P.children[q];
-    const int kc = P.sn_col0[c + 1] - P.sn_col0[c];
-    const int fc = (int)(P.row_ptr[c + 1] - P.row_ptr[c]);
-    const int rc = fc - kc;
-    const double* C = P.arena + P.front_pos[c] + P.cb_shift[c];      // only the child's contribution block (columns >= kc) is read
-    const int* rl = P.rel + P.rel_ptr[c];
-    if (FLOW && c < t_lo) flow_wait(flags + c, wait_epoch, P.counters);      // a child task of this launch (workgroup-uniform)
-    for (int jj = grp; jj < rc; jj += G) {
-      const int pj = rl[jj];
-      const double* Ccol = C + (size_t)(kc + jj) * fc + kc;
-      for (int ii = jj + lane; ii < rc; ii += 32) F[rl[ii] + pj * ldf] += FLOW ? flow_ld(Ccol + ii) : Ccol[ii];
-    }
-    __syncthreads();
-  }
-  ldl_partial_lds<TPB>(F, wcol, ldf, f, k);
-  // write back: L panel (rows >= col), contribution block (lower), D, inertia counts
-  for (int c = grp; c < f; c += G) {
-    double* dst = front + (size_t)c * f + cb_off(P, s, c, k);
-    if (FLOW && c >= k) { for (int i = c + lane; i < f; i += 32) flow_st(dst + i, F[i + c * ldf]); }
-    else for (int i = c + lane; i < f; i += 32) dst[i] = F[i + c * ldf];
-  }
-  for (int j = tid; j < k; j += TPB) {
-    const double d = F[j + j * ldf];
-    P.dvals[col0 + j] = d;
-    classify_pivot(d, tol, pos, neg, zer, bad);
-  }
-  if (FLOW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next front of the task reads this contribution block back
-  __threadfence_block();
-  __syncthreads();
-  }
+  front_small_body<TPB, FLOW>(P, s_root, tol, sm, flags, wait_epoch, pos, neg, zer, bad);
   flush_counts(P, 1 + (int)(blockIdx.x % (kCountSlots - 1)), pos, neg, zer, bad);
   if (FLOW) flow_signal(flags + s_root, epoch);
 }
@@ -170,124 +80,7 @@ __device__ __forceinline__ int lower_bound_dev(const int* a, int n, int key) {
   return lo;
 }
 
-// Each front column is owned by exactly one wave, which applies the contributions in list order:
-// deterministic, no atomics, no workgroup barriers.
-// column pc of front s accumulated in `buf` (buf[0] = row pc): zero, A entries, delta, children's contributions in
-// their fixed order.  LDS = true: buf is the wave's LDS column; false: the HBM column itself.
-// extend-add items whose records and first rows are in flight together (round 5: packed 32-byte records, 4 / 8 / 16 items measured: 2047 / 2058 /
-// 2485 us of assembly per S-metric factorisation -- the kernels are not bound by the record fetches)
-#ifndef OKKT_ASM_BATCH
-#define OKKT_ASM_BATCH 4
-#endif
-#ifndef OKKT_ASM_BATCH_CHUNKED
-#define OKKT_ASM_BATCH_CHUNKED 4
-#endif
-#ifndef OKKT_ASM_UNROLL
-#define OKKT_ASM_UNROLL 4
-#endif
-constexpr int kAsmBatch = OKKT_ASM_BATCH, kAsmBatchChunked = OKKT_ASM_BATCH_CHUNKED;
-constexpr int kAsmUnroll = OKKT_ASM_UNROLL;      // 64-row groups of an item whose index and value loads are in flight together (round 6: 8 instead of 4 is SLOWER -- S-metric 17.3 against 17.1 ms, S-C5 3.95 / 3.87: the registers cost waves, and waves are what hides the latency here)
-// (k_batch_schur_assemble of batch_schur.hip holds a COPY of the <true, true> form and of the LDS branch of k_big_assemble<true> below, with
-// the values, the shift and the arena of a batch item: a change to either must be made to both -- tests/test_gpu_schur_batch.py compares S bit for bit)
-template <bool LDS, bool BATCH>
-__device__ __forceinline__ void assemble_column(const DevPlan& P, int s, int pc, int f, int k, int col0, double* __restrict__ buf) {
-  const int lane = threadIdx.x & 63;
-  const int nrow = f - pc;
-  for (int i = lane; i < nrow; i += 64) buf[i] = 0.0;
-  __threadfence_block();
-  if (pc < k) {
-    const int64_t e0 = P.aent_ptr[s];
-    const int ne = (int)(P.aent_ptr[s + 1] - e0);
-    const int64_t* dstv = P.aent_dst + e0;
-    // range of this column's entries: precomputed on the host (two binary searches = ~25 dependent loads otherwise)
-    const int64_t gcol = P.bigcol_base[s] + pc;
-    const int lo = (int)(P.acol_lo[gcol] - e0);
-    const int hi = pc + 1 < f ? (int)(P.acol_lo[gcol + 1] - e0) : ne;
-    const int64_t base = (int64_t)pc * f + pc;     // dstv holds offsets in the front; entry (row, pc) sits at pc * f + row (past 2^31 above 46 340 rows)
-    if (!P.has_dup) {
-      for (int e = lo + lane; e < hi; e += 64) buf[(int)(dstv[e] - base)] = P.vals[P.aent_src[e0 + e]];
-    } else if (lane == 0) {
-      for (int e = lo; e < hi; ++e) buf[(int)(dstv[e] - base)] += P.vals[P.aent_src[e0 + e]];
-    }
-    __threadfence_block();
-    if (lane == 0) buf[0] += P.diagadd[col0 + pc];
-    __threadfence_block();
-  }
-  const int64_t gc = P.bigcol_base[s] + pc;
-  // one precomputed record per item (source column in the arena, rel list, lengths): the per-child metadata
-  // would cost two more dependent memory round trips per item; the next record is fetched while the current
-  // item is applied
-  const int64_t q0 = P.ea_ptr[gc], q1 = P.ea_ptr[gc + 1];
-  // Items are applied strictly in order (same destination column), but their loads need not wait for each other:
-  // four items at a time have their records, and then the first 64 rows of their index and source columns, in
-  // flight together (clamped addresses, no branches); most items of the lower levels are no longer than that.
-  constexpr int NB4 = kAsmBatch;
-  if constexpr (!BATCH) {
-    // long columns (upper levels, bandwidth-bound): one item after the other, the next record fetched meanwhile
-    int64_t src_n = 0, rel_n = 0;
-    int rc_n = 0, jj_n = 0;
-    if (q0 < q1) { const EaRec r = P.ea_rec[q0]; src_n = r.src; rel_n = r.rel; rc_n = r.rc; jj_n = r.jj; }
-    for (int64_t q = q0; q < q1; ++q) {
-      const int rc = rc_n, jj = jj_n;
-      const int* rl = P.rel + rel_n;
-      const double* Ccol = P.arena + src_n;
-      if (q + 1 < q1) { const EaRec r = P.ea_rec[q + 1]; src_n = r.src; rel_n = r.rel; rc_n = r.rc; jj_n = r.jj; }
-      int ii = jj + lane;
-      for (; ii + 64 * (kAsmUnroll - 1) < rc; ii += 64 * kAsmUnroll) {
-        int d[kAsmUnroll];
-        double v[kAsmUnroll], o[kAsmUnroll];
-#pragma unroll
-        for (int u = 0; u < kAsmUnroll; ++u) d[u] = rl[ii + 64 * u] - pc;
-#pragma unroll
-        for (int u = 0; u < kAsmUnroll; ++u) { v[u] = Ccol[ii + 64 * u]; o[u] = buf[d[u]]; }
-#pragma unroll
-        for (int u = 0; u < kAsmUnroll; ++u) buf[d[u]] = o[u] + v[u];
-      }
-      for (; ii < rc; ii += 64) buf[rl[ii] - pc] += Ccol[ii];
-      __threadfence_block();
-    }
-    return;
-  }
-  for (int64_t q = q0; q < q1; q += NB4) {
-    int64_t src[NB4], rel[NB4];
-    int rc[NB4], jj[NB4];
-#pragma unroll
-    for (int u = 0; u < NB4; ++u) {
-      const EaRec r = P.ea_rec[min(q + u, q1 - 1)];
-      src[u] = r.src; rel[u] = r.rel; rc[u] = r.rc; jj[u] = r.jj;
-    }
-    int d[NB4];
-    double v[NB4];
-#pragma unroll
-    for (int u = 0; u < NB4; ++u) {
-      const int ii = min(jj[u] + lane, rc[u] - 1);
-      d[u] = P.rel[rel[u] + ii] - pc;
-      v[u] = P.arena[src[u] + ii];
-    }
-#pragma unroll
-    for (int u = 0; u < NB4; ++u) {
-      if (q + u < q1) {       // wave-uniform
-        if (jj[u] + lane < rc[u]) buf[d[u]] += v[u];
-        const int* rl = P.rel + rel[u];
-        const double* Ccol = P.arena + src[u];
-        int ii = jj[u] + 64 + lane;
-        for (; ii + 64 * (kAsmUnroll - 1) < rc[u]; ii += 64 * kAsmUnroll) {
-          int dd[kAsmUnroll];
-          double vv[kAsmUnroll], oo[kAsmUnroll];
-#pragma unroll
-          for (int w = 0; w < kAsmUnroll; ++w) dd[w] = rl[ii + 64 * w] - pc;
-#pragma unroll
-          for (int w = 0; w < kAsmUnroll; ++w) { vv[w] = Ccol[ii + 64 * w]; oo[w] = buf[dd[w]]; }
-#pragma unroll
-          for (int w = 0; w < kAsmUnroll; ++w) buf[dd[w]] = oo[w] + vv[w];
-        }
-        for (; ii < rc[u]; ii += 64) buf[rl[ii] - pc] += Ccol[ii];
-        __threadfence_block();
-      }
-    }
-  }
-}
-
+// (a column is accumulated by assemble_column<LDS, BATCH> of front_bodies.h, where its tuning constants kAsmBatch and kAsmUnroll are)
 template <bool BATCH>
 __global__ __launch_bounds__(256) void k_big_assemble(DevPlan P, const int* __restrict__ list, int lcol) {
   // One wave per front column.  Columns of at most `lcol` rows are accumulated in LDS and written to HBM once:

@@ -15,6 +15,7 @@
 //   * panel reads are 16 bytes per lane (two rows), 8 - 16 loads in flight per lane.
 // Results are deterministic: every output entry is owned by one workgroup that sums in a fixed order.
 #include "numeric.h"
+#include "front_bodies.h"
 #include "solve_sparse.h"
 
 #include <algorithm>
@@ -74,7 +75,7 @@ __device__ __forceinline__ void xblock(int k, int b, int& c0, int& kb, int& ld, 
 // forward right-hand-side entry of front row r (before any block of this front has been applied): the permuted rhs on the
 // pivot rows plus the children's contribution vectors through the inverted extend-add lists (fixed order)
 // (k_batch_schur_gather of batch_schur.hip holds a COPY of this body with the sweep vectors of a batch item: a change to either must be made
-// to both -- tests/test_gpu_schur_batch.py compares r2 bit for bit)
+// to both -- tests/test_gpu_schur_batch.py compares r2 bit for bit.  Why it is not a call of this function is written there)
 template <int R>
 __device__ __forceinline__ void fwd_gather(const DevPlan& P, int64_t gcb, int col0, int k, int r, double (&w)[R]) {
 #pragma unroll
@@ -222,22 +223,8 @@ __global__ __launch_bounds__(256) void k_xinv_gemm(DevPlan P, const int* __restr
       }
 }
 
-// ---- in-launch hand-offs between the workgroups of one front (round 3): a level's two dependent launches become one.
-// Producer workgroups have LOWER block indices than their consumers (dispatch order = dependency order, so a waiting
-// consumer never keeps its producer from being scheduled); the protocol is the MI355X guide's: every storing wave drains its
-// stores, the workgroup meets at a barrier, one lane releases at agent scope and then raises the flag / counter; the consumer
-// polls with relaxed agent-scope loads (bounded: a hand-off that never arrives ends the wait instead of hanging the GPU and
-// raises the plan's time-out word, which turns the solution into NaN in k_permute_out_r), acquires once, and only then reads the data.
-// The handed-off bytes are a few hundred doubles per front: they are written and read with agent-scope (sc1) accesses, which
-// bypass the CU's L1 and are served by the memory side -- no release / acquire fences (an agent release writes back the whole L2,
-// an acquire invalidates the whole L1: 2 - 7 us each, per workgroup, measured as a net loss on the fused sweeps).
-__device__ __forceinline__ void st_agent(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double ld_agent(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void front_signal_store(int* flag, int value) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // every storing wave: its sc1 stores have been acknowledged
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// ---- in-launch hand-offs between the workgroups of one front (round 3): the protocol, and st_agent, ld_agent, front_signal_store and
+// front_wait, which the small-front sweeps use too, are in front_bodies.h; here the forms that only the big fronts need
 __device__ __forceinline__ void front_signal_add(int* counter) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -265,20 +252,11 @@ __device__ __forceinline__ void front_wait64(const unsigned long long* counter, 
   }
   __syncthreads();
 }
-// waits until *flag >= value (monotonic flags); the payload is then read with ld_agent only
-__device__ __forceinline__ void front_wait(const int* flag, int value, unsigned long long* tmo = nullptr) {
-  if (threadIdx.x == 0) {
-    int spins = 0;
-    while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < value && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(2);
-    if (spins >= (1 << 22) && tmo) atomicExch(tmo, 1ull);
-  }
-  __syncthreads();
-}
 
 // Flow sweeps of the wide fronts (k_fwd_wide_flow / k_bwd_wide_flow): wave 0 waits until the tile words ver[t0 .. t0 + nt) have
 // reached `want` (nt <= 62) and, with a counter, until the arrival counter has reached `cwant` -- one condition per lane, one
-// ballot per poll; bounded like the other waits.  The payload travels with agent-scope accesses only (no fences, see above).
-__device__ __forceinline__ void flow_wait(const unsigned long long* ver, int t0, int nt, unsigned long long want, const unsigned long long* counter, unsigned long long cwant,
+// ballot per poll; bounded like the other waits.  The payload travels with agent-scope accesses only (no fences, see front_bodies.h).
+__device__ __forceinline__ void flow_wait_tiles(const unsigned long long* ver, int t0, int nt, unsigned long long want, const unsigned long long* counter, unsigned long long cwant,
                                           unsigned long long* tmo) {
   if (threadIdx.x < 64) {
     const int ln = threadIdx.x;
@@ -307,72 +285,13 @@ __device__ __forceinline__ void flow_publish(unsigned long long* ver, int t0, in
 // ------------------------------------------------------------------------------------------------------------------
 // small fronts (one workgroup per task of fronts, the front's vector in LDS), R right-hand sides
 // ------------------------------------------------------------------------------------------------------------------
-// FLOW: the tasks of several levels in one launch (see k_front_small<.., FLOW> in numeric.hip): a task waits for the flags of its
-// children tasks, contribution vectors travel with agent-scope accesses, flags[root] = epoch when the task is done.
-// (batch.hip, fs_task / bs_task: copies of the loop bodies of k_fs_small and k_bs_small with FLOW = false, for the uniform batches -- a change
-// here must be made there too: tests/test_gpu_batch.py compares the solutions bit for bit)
+// one workgroup per task of `list`: fs_small_body / bs_small_body of front_bodies.h.  FLOW: the tasks of several levels in one launch (see
+// k_front_small<.., FLOW> in numeric.hip): flags[root] = epoch when the task is done.
 template <int TPB, int R, bool FLOW = false>
 __global__ __launch_bounds__(TPB) void k_fs_small(DevPlan P, const int* __restrict__ list, int ldw, int* __restrict__ flags = nullptr, int epoch = 0, int wait_epoch = 0) {
   extern __shared__ __attribute__((aligned(16))) double sm[];      // [R][ldw]
-  const int tid = threadIdx.x;
   const int s_root = list[blockIdx.x];
-  const int t_lo = P.task_lo[s_root];
-  for (int s = t_lo; s <= s_root; ++s) {      // the task's fronts, children first
-    const int col0 = P.sn_col0[s];
-    const int k = P.sn_col0[s + 1] - col0;
-    const int f = (int)(P.row_ptr[s + 1] - P.row_ptr[s]);
-    const double* L = P.arena + P.front_pos[s];
-    for (int i = tid; i < f; i += TPB)
-#pragma unroll
-      for (int q = 0; q < R; ++q) sm[q * ldw + i] = i < k ? P.xwork[(size_t)q * P.xw_stride + col0 + i] : 0.0;
-    __syncthreads();
-    for (int64_t c = P.child_ptr[s]; c < P.child_ptr[s + 1]; ++c) {
-      const int ch = P.children[c];
-      const int rc = (int)(P.rel_ptr[ch + 1] - P.rel_ptr[ch]);
-      const int* rl = P.rel + P.rel_ptr[ch];
-      const double* cvc = P.cv + P.cv_pos[ch];
-      if (FLOW && ch < t_lo) front_wait(flags + ch, wait_epoch, P.counters + 5);
-      for (int ii = tid; ii < rc; ii += TPB) {
-        const int d = rl[ii];
-#pragma unroll
-        for (int q = 0; q < R; ++q) sm[q * ldw + d] += FLOW ? ld_agent(cvc + (size_t)q * P.cv_stride + ii) : cvc[(size_t)q * P.cv_stride + ii];
-      }
-      __syncthreads();
-    }
-    // unit lower triangular k x k
-    for (int j = 0; j < k; ++j) {
-      const double* col = L + (size_t)j * f;
-      for (int i = j + 1 + tid; i < k; i += TPB) {
-        const double l = col[i];
-#pragma unroll
-        for (int q = 0; q < R; ++q) sm[q * ldw + i] -= l * sm[q * ldw + j];
-      }
-      __syncthreads();
-    }
-    // rows below the pivot block: contribution vector for the parent
-    double* cvs = P.cv + P.cv_pos[s];
-    for (int i = k + tid; i < f; i += TPB) {
-      double acc[R];
-#pragma unroll
-      for (int q = 0; q < R; ++q) acc[q] = sm[q * ldw + i];
-      for (int j = 0; j < k; ++j) {
-        const double l = L[(size_t)j * f + i];
-#pragma unroll
-        for (int q = 0; q < R; ++q) acc[q] -= l * sm[q * ldw + j];
-      }
-#pragma unroll
-      for (int q = 0; q < R; ++q) { if (FLOW) st_agent(cvs + (size_t)q * P.cv_stride + i - k, acc[q]); else cvs[(size_t)q * P.cv_stride + i - k] = acc[q]; }
-    }
-    // z = D^-1 y
-    for (int j = tid; j < k; j += TPB) {
-      const double d = P.dvals[col0 + j];
-#pragma unroll
-      for (int q = 0; q < R; ++q) P.zwork[(size_t)q * P.xw_stride + col0 + j] = sm[q * ldw + j] / d;
-    }
-    if (FLOW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __threadfence_block();
-    __syncthreads();
-  }
+  fs_small_body<TPB, R, FLOW>(P, s_root, ldw, sm, flags, wait_epoch);
   if (FLOW) front_signal_store(flags + s_root, epoch);
 }
 
@@ -381,61 +300,12 @@ __global__ __launch_bounds__(TPB) void k_fs_small(DevPlan P, const int* __restri
 template <int TPB, int R, bool FLOW = false>
 __global__ __launch_bounds__(TPB) void k_bs_small(DevPlan P, const int* __restrict__ list, int ldw, int* __restrict__ flags = nullptr, int epoch = 0) {
   extern __shared__ __attribute__((aligned(16))) double sm[];      // [R][ldw]
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  constexpr int NW = TPB / 64;
   const int s_root = list[FLOW ? gridDim.x - 1 - blockIdx.x : blockIdx.x];
   if (FLOW) {
     const int up = P.unit_parent[s_root];
     if (up >= 0) front_wait(flags + up, epoch, P.counters + 5);
   }
-  for (int s = s_root; s >= P.task_lo[s_root]; --s) {      // the task's fronts, parents first
-    const int col0 = P.sn_col0[s];
-    const int k = P.sn_col0[s + 1] - col0;
-    const int f = (int)(P.row_ptr[s + 1] - P.row_ptr[s]);
-    const double* L = P.arena + P.front_pos[s];
-    const int* rows = P.rows + P.row_ptr[s];
-    for (int i = tid; i < f; i += TPB) {
-      const int g = rows[i];     // rows[i] = col0 + i for i < k: this front's z; beyond: the ancestors' solution
-      const double* src = i < k ? P.zwork : P.xwork;
-#pragma unroll
-      for (int q = 0; q < R; ++q) sm[q * ldw + i] = (FLOW && i >= k) ? ld_agent(src + (size_t)q * P.xw_stride + g) : src[(size_t)q * P.xw_stride + g];
-    }
-    __syncthreads();
-    // rhs_j = z_j - sum_{i >= k} L[i, j] * x_i
-    for (int j = wv; j < k; j += NW) {
-      const double* col = L + (size_t)j * f;
-      double acc[R];
-#pragma unroll
-      for (int q = 0; q < R; ++q) acc[q] = 0.0;
-      for (int i = k + lane; i < f; i += 64) {
-        const double l = col[i];
-#pragma unroll
-        for (int q = 0; q < R; ++q) acc[q] += l * sm[q * ldw + i];
-      }
-#pragma unroll
-      for (int q = 0; q < R; ++q) {
-        double a = acc[q];
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
-        if (lane == 0) sm[q * ldw + j] -= a;
-      }
-    }
-    __syncthreads();
-    // unit upper triangular (L11^T) k x k, column oriented
-    for (int j = k - 1; j >= 0; --j) {
-      for (int i = tid; i < j; i += TPB) {
-        const double l = L[(size_t)i * f + j];
-#pragma unroll
-        for (int q = 0; q < R; ++q) sm[q * ldw + i] -= l * sm[q * ldw + j];
-      }
-      __syncthreads();
-    }
-    for (int j = tid; j < k; j += TPB)
-#pragma unroll
-      for (int q = 0; q < R; ++q) { if (FLOW) st_agent(P.xwork + (size_t)q * P.xw_stride + col0 + j, sm[q * ldw + j]); else P.xwork[(size_t)q * P.xw_stride + col0 + j] = sm[q * ldw + j]; }
-    if (FLOW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __threadfence_block();
-    __syncthreads();
-  }
+  bs_small_body<TPB, R, FLOW>(P, s_root, ldw, sm);
   if (FLOW) front_signal_store(flags + s_root, epoch);
 }
 
@@ -601,7 +471,7 @@ __device__ __forceinline__ bool fwd_y_body(const DevPlan& P, int s, int b, int b
   const double* X = P.xinv + P.xinv_pos[s] + off + (size_t)q0 * ld;
   const int ic = min(i, kb - 1);
   const int64_t gcb = P.bigcol_base[s];
-  if (ver && b > 0) flow_wait(ver, (c0 + q0) >> 5, ((c0 + q0 + kq - 1) >> 5) - ((c0 + q0) >> 5) + 1, vwant, nullptr, 0ull, P.counters + 5);
+  if (ver && b > 0) flow_wait_tiles(ver, (c0 + q0) >> 5, ((c0 + q0 + kq - 1) >> 5) - ((c0 + q0) >> 5) + 1, vwant, nullptr, 0ull, P.counters + 5);
   for (int c = tid; c < CW; c += 256) {
     double w[R];
 #pragma unroll
@@ -678,7 +548,7 @@ __device__ __forceinline__ void fwd_upd_body(const DevPlan& P, int s, int b, int
   const bool is_first = first >= 0 ? first != 0 : bx == 0;
   if (!is_first && rb >= f) return;
   const int vt0 = rb >> 5, vnt = rb < f ? min(ROWS / 32, (f - rb + 31) >> 5) : 0;
-  if (ver) flow_wait(ver, vt0, b > 0 ? vnt : 0, vbase + (unsigned long long)b, counter, (epoch << 20) + (unsigned long long)yexp, P.counters + 5);
+  if (ver) flow_wait_tiles(ver, vt0, b > 0 ? vnt : 0, vbase + (unsigned long long)b, counter, (epoch << 20) + (unsigned long long)yexp, P.counters + 5);
   else if (counter) front_wait64(counter, epoch, ((kb + 63) / 64) * kCS, P.counters + 5);
   const double* yp = P.ypart + P.ypart_pos[s] + (ver ? (size_t)b * kMaxRhs * kCS * kSB : 0);
   for (int p = tid; p < kSB; p += 256) {
