@@ -32,7 +32,7 @@ def lb_s_predict(it, dir, frac_bd_predict, ex):  # frac_boundary.jl:12-15
 
 
 def lb_y(it, dir, frac_bd):  # frac_boundary.jl:17-20
-    return frac_bd * it.y * min(1.0, _norm_inf(dir.x))
+    return frac_bd * it.y * _jmin(1.0, _norm_inf(dir.x))      # Julia's min: a NaN norm gives NaN (Python's min would drop it)
 
 
 def lb_s(it, dir, frac_bd, ex):  # frac_boundary.jl:22-28
@@ -42,12 +42,8 @@ def lb_s(it, dir, frac_bd, ex):  # frac_boundary.jl:22-28
 def simple_max_step(val, dir, lb):  # frac_boundary.jl:31-35
     with np.errstate(divide="ignore", invalid="ignore"):
         r = -dir / (val - lb)
-    ratio = 1.0
-    for v in r:              # Julia's maximum propagates NaN
-        if v != v:
-            ratio = math.nan
-            break
-        ratio = max(ratio, float(v))
+    # maximum([1.0; r]): Julia's maximum propagates NaN, and a maximum does not depend on the order
+    ratio = math.nan if np.isnan(r).any() else max(1.0, float(np.max(r))) if len(r) else 1.0
     return 1.0 / ratio
 
 
@@ -66,20 +62,24 @@ def _jmin(a, b):
 def dual_bounds(s, mu, y, dy, comp_feas):  # move.jl:28-80 (s, mu of the candidate)
     lb, ub = 0.0, 1.0
     safety_factor, safety_add = 1.001, 0.0
+    s, y, dy = (np.asarray(v, dtype=np.float64) for v in (s, y, dy))
+    assert np.all(s > 0.0)
+    # the two quotients of a row do not depend on the rows before it: evaluated for all rows at once (the same IEEE operations in the
+    # same order), so that the loop below, which is what depends on the order, stays fast at several 100 000 rows
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        for i in range(len(y)):
-            si, dyi, yi = np.float64(s[i]), np.float64(dy[i]), np.float64(y[i])
-            assert si > 0.0
-            ub_dyi = float(np.float64(mu) / (np.float64(comp_feas) * si * dyi) - yi / dyi)
-            lb_dyi = float(np.float64(mu) * np.float64(comp_feas) / (si * dyi) - yi / dyi)
-            if dyi > 0.0:
-                lb = _jmax(lb_dyi * safety_factor + safety_add, lb)
-                ub = _jmin(ub_dyi / safety_factor - safety_add, ub)
-            elif dyi < 0.0:
-                lb = _jmax(ub_dyi * safety_factor + safety_add, lb)
-                ub = _jmin(lb_dyi / safety_factor - safety_add, ub)
-            elif lb_dyi >= 0.0 or ub_dyi <= 0.0:
-                lb, ub = 0.0, -1.0
+        ub_dy = np.float64(mu) / (np.float64(comp_feas) * s * dy) - y / dy
+        lb_dy = np.float64(mu) * np.float64(comp_feas) / (s * dy) - y / dy
+        pos, neg = dy > 0.0, dy < 0.0
+        a = np.where(pos, lb_dy * safety_factor + safety_add, ub_dy * safety_factor + safety_add)
+        b = np.where(pos, ub_dy / safety_factor - safety_add, lb_dy / safety_factor - safety_add)
+        reset = ~pos & ~neg & ((lb_dy >= 0.0) | (ub_dy <= 0.0))
+    # the fold is what depends on the order: it stays the reference's loop, row by row (max / min as Julia's: NaN propagates)
+    for counts, resets, ai, bi in zip((pos | neg).tolist(), reset.tolist(), a.tolist(), b.tolist()):
+        if counts:
+            lb = math.nan if (ai != ai or lb != lb) else (ai if ai > lb else lb)
+            ub = math.nan if (bi != bi or ub != ub) else (bi if bi < ub else ub)
+        elif resets:
+            lb, ub = 0.0, -1.0
     if not (math.isfinite(lb) and math.isfinite(ub)):
         return 0.0, -1.0
     return lb, ub
