@@ -174,6 +174,11 @@ int okkt_residual(okkt_handle h, const double* nzval, const double* rhs, const d
 /* the same with device pointers for nzval, rhs, x and r; omega_out is host memory */
 int okkt_residual_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, const double* d_x, double* d_r, int64_t nrhs,
                       double* omega_out);
+/* read-only, for tests: the partition of the row map that the residual, scaling and ||F||_1 passes share (csrc/refine.hip):
+ * out = { lanes per short row, long_min (rows with more entries take a workgroup each), workgroups of the short rows, long rows,
+ * entries that sum duplicates, entries of the full symmetric pattern }.  Builds the map when no call has built it yet, as
+ * okkt_residual does, and carries okkt_residual's refusals; OKKT_ERR_INVALID for a NULL out. */
+int okkt_debug_row_map(okkt_handle h, int64_t out[6]);
 int okkt_solve_refine(okkt_handle h, const double* nzval, const double* rhs, double* sol, int64_t nrhs, int32_t max_steps,
                       double tol, okkt_refine_info* info /* or NULL */, double* omega_out /* [nrhs] or NULL */);
 int okkt_solve_refine_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,

@@ -442,6 +442,7 @@ SIGNATURES = {
     "okkt_solve_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64]),
     "okkt_residual": (C.c_int, [_vp, _f64p, _f64p, _f64p, _f64p, C.c_int64, _f64p]),
     "okkt_residual_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _f64p]),
+    "okkt_debug_row_map": (C.c_int, [_vp, _i64p]),
     "okkt_solve_refine": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
     "okkt_solve_refine_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_double, C.POINTER(OkktRefineInfo), _f64p]),
     "okkt_solve_gmres": (C.c_int, [_vp, _f64p, _f64p, _f64p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(OkktGmresInfo),

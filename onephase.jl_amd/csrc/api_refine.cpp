@@ -523,6 +523,18 @@ int okkt_residual(okkt_handle h, const double* nzval, const double* rhs, const d
   });
 }
 
+int okkt_debug_row_map(okkt_handle h, int64_t out[6]) {
+  if (!h) return OKKT_ERR_INVALID;
+  return fence(h, "okkt_debug_row_map", [&]() -> int {
+    int rc = refine_ready(h, false);
+    if (rc != OKKT_OK) return rc;
+    if (!out) return solver_set_error(h, OKKT_ERR_INVALID, "null pointer");
+    const RefineMap& M = h->rf;
+    out[0] = M.lpr; out[1] = M.long_min; out[2] = M.nb_short; out[3] = M.nlong; out[4] = M.ndup; out[5] = M.nnz;
+    return OKKT_OK;
+  });
+}
+
 int okkt_solve_refine_dev(okkt_handle h, const double* d_nzval, const double* d_rhs, double* d_sol, int64_t nrhs, int32_t max_steps,
                           double tol, okkt_refine_info* info, double* omega_out) {
   return refine_dev_entry(h, false, d_nzval, d_rhs, d_sol, nrhs, max_steps, tol, info, omega_out);
