@@ -87,9 +87,8 @@ static int check_tridiag() {
 // of rounds is the largest count, and that an item leaves the active list exactly once.
 static int check_items_loop() {
   int bad = 0;
-  okkt_kkt_pars P;
-  P.delta_start = 1e-6; P.delta_min = 1e-12; P.delta_max = 1e3; P.delta_inc = 8.0; P.delta_dec = 1.0 / 3.0; P.delta_zero = 0.0;
-  P.ItRefine_Num = 3; P.max_it = 500;
+  okkt_kkt_pars P = default_kkt_pars();
+  P.delta_max = 1e3; P.delta_dec = 1.0 / 3.0;
   // item 6 starts from a large previous delta: it passes delta_max at its third attempt and leaves with status 0 while items 1 and 4
   // are still making attempts (item 1 succeeds at its fourth)
   const double dmin[] = {0.5, 0.5, -2.0, -2.0, 0.5, 0.25, 0.5};
@@ -147,6 +146,39 @@ static int check_items_loop() {
   }
   if (status[6] != 0 || nfac[6] != 3 || status[1] != 1 || nfac[1] != 4 || rounds <= nfac[6]) { fprintf(stderr, "items loop: the early failure: status %d after %d attempts\n", status[6], nfac[6]); ++bad; }
   if (rounds != max_fac || status[4] != 0 || status[0] != 1 || nfac[0] != 1) { fprintf(stderr, "items loop: %d rounds, largest count %d\n", rounds, max_fac); ++bad; }
+  return bad;
+}
+
+// The sequence all three delta loops step (DeltaSeq), against delta_strategy.jl:37-114 evaluated by hand with the default parameters
+// (start 1e-6, min 1e-12, max 1e50, inc 8, dec 1/pi, zero 0): the attempt at delta_zero outside the loop (tau = 1.5 diag_min > 0), an
+// attempt that a caller skips (it is consumed: the next one is delta * inc all the same), the first attempt of the loop above
+// delta_max (1e-6 * 8^63 = 1e-6 * 2^189 = 7.8e50; 8^62 gives 9.8e49), and the first attempts with tau < 0
+static int check_delta_seq() {
+  int bad = 0;
+  const okkt_kkt_pars P = default_kkt_pars();
+  double d = -1.0;
+  bool lp = true;
+  auto expect = [&](DeltaSeq& s, double want, bool want_loop, const char* what) {
+    if (!s.next(P, &d, &lp) || d != want || lp != want_loop) { fprintf(stderr, "delta seq: %s: (%.17g, %d), expected (%.17g, %d)\n", what, d, (int)lp, want, (int)want_loop); ++bad; }
+  };
+  DeltaSeq s;
+  s.start(0.5, 0.0, P);
+  expect(s, 0.0, false, "the attempt at delta_zero");
+  expect(s, 1e-6, true, "i = 1: delta_start - tau with tau = 0 (this one is skipped, not factored)");
+  expect(s, 8e-6, true, "i = 2 after the skipped attempt");
+  for (int i = 3; i <= 63; ++i) {
+    if (!s.next(P, &d, &lp) || !lp || d > P.delta_max) { fprintf(stderr, "delta seq: i = %d: %.17g is above delta_max or outside the loop\n", i, d); ++bad; break; }
+  }
+  expect(s, std::ldexp(1e-6, 189), true, "i = 64: the first attempt above delta_max");
+  if (!(d > P.delta_max)) { fprintf(stderr, "delta seq: i = 64 is not above delta_max\n"); ++bad; }
+  s.start(-2.0, 0.0, P);
+  expect(s, 3.000001, true, "tau = -3, no previous delta: delta_start - tau");
+  expect(s, 24.000008, true, "then delta * inc");
+  s.start(-2.0, 0.3, P);
+  expect(s, 3.000000000001, true, "tau = -3, previous delta 0.3: max(delta_min - tau, 0.3 / pi)");
+  s.start(-2.0, 30.0, P);
+  expect(s, 30.0 * (1.0 / M_PI), true, "tau = -3, previous delta 30: 30 * dec");
+  if (!bad) printf("delta seq    zero-first, skipped, above delta_max and tau < 0 attempts as delta_strategy.jl gives them\n");
   return bad;
 }
 
@@ -562,6 +594,7 @@ int main() {
   bad += check_tridiag();
   bad += check_sym_eig();
   bad += check_items_loop();
+  bad += check_delta_seq();
   bad += check_ls_finish();
   if (bad) { fprintf(stderr, "%d case(s) failed\n", bad); return 1; }
   printf("asan driver: all cases clean\n");

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "kkt_device.h"
+#include "kkt_items_seq.h"
 #include "kkt_state.h"
 #include "lanczos.h"
 
@@ -405,8 +406,6 @@ inline int pick_lpr(int64_t nnz, int64_t rows) {
       }                                                                                                              \
   } while (0)
 
-int kk_fail(okkt_kkt_s* k, int code, const std::string& msg) { k->err = msg; return code; }
-
 // OKKT_SCHUR_GROUPS in the environment: the largest column-group count of k_assemble_schur_lds that okkt_kkt_set_structure may pick
 // (16, 8, 4; 0 = always the contribution-list kernel k_assemble_schur).  Unset or any other value: 16, i.e. no cap
 int schur_groups_cap() {
@@ -419,12 +418,6 @@ int schur_groups_cap() {
   }();
   return cap;
 }
-
-int kk_check_ls(okkt_kkt_s* k, int rc, const char* what) {
-  if (rc < 0) { k->err = std::string(what) + ": " + okkt_last_error(k->ls); }
-  return rc;
-}
-
 
 int kk_reduce(okkt_kkt_s* k, int64_t n, const double* v, int mode, double* host_out) {
   hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, kk_stream(k), n, v, mode, k->red);
@@ -468,14 +461,7 @@ extern "C" {
 
 int okkt_kkt_default_pars(okkt_kkt_pars* p) {
   if (!p) return OKKT_ERR_INVALID;
-  p->delta_start = 1e-6;                 // parameters.jl:147-158
-  p->delta_min = 1e-12;
-  p->delta_max = 1e50;
-  p->delta_inc = 8.0;
-  p->delta_dec = 1.0 / M_PI;
-  p->delta_zero = 0.0;
-  p->ItRefine_Num = 3;                   // parameters.jl:20
-  p->max_it = 500;                       // delta_strategy.jl:40
+  *p = default_kkt_pars();
   return OKKT_OK;
 }
 
@@ -981,8 +967,7 @@ static int ipopt_strategy_impl(okkt_kkt_s* k, double delta_prev, const okkt_kkt_
   // after a failed attempt the reference scans the x-block for diagonal dominance and prints a warning
   // (delta_strategy.jl:94-98); here a device scan, counted for the glue to print (okkt_kkt_diag_dom_warnings)
   auto scan_after_failure = [&]() -> int {
-    static const bool on = !(getenv("OKKT_DIAG_DOM_SCAN") && atoi(getenv("OKKT_DIAG_DOM_SCAN")) == 0);
-    if (!on) return OKKT_OK;
+    if (!kk_diag_dom_scan_on()) return OKKT_OK;
     int32_t dom = -1;
     const int rc3 = okkt_kkt_is_diag_dom(k, &dom);
     if (rc3 == OKKT_OK && dom == 1) ++k->diag_dom_warnings;
@@ -1006,26 +991,13 @@ static int ipopt_strategy_impl(okkt_kkt_s* k, double delta_prev, const okkt_kkt_
   };
   int rc = okkt_kkt_diag_min(k, &dmin);
   if (rc != OKKT_OK) return rc;
-  double tau = 1.5 * dmin;
-  double delta = P.delta_zero;
+  DeltaSeq seq;
+  seq.start(dmin, delta_prev, P);
   *num_fac_out = 0;
-  *delta_out = delta;
-  if (tau > 0.0) {
-    tau = 0.0;
-    rc = okkt_kkt_factor_trial(k, delta, nullptr);   // a failed attempt is discarded: it may stop early
-    if (rc < 0) return rc;
-    ++num_fac;
-    if (rc == 1) { *num_fac_out = num_fac; *delta_out = delta; return 1; }
-    if ((rc = scan_after_failure()) < 0) return rc;
-    if ((rc = estimate_after_failure()) < 0) return rc;
-  }
-  for (int i = 1; i <= P.max_it; ++i) {
-    if (i == 1) {
-      if (delta_prev != 0.0) delta = std::max(P.delta_min - tau, delta_prev * P.delta_dec);
-      else delta = P.delta_start - tau;
-    } else {
-      delta = delta * P.delta_inc;
-    }
+  *delta_out = P.delta_zero;
+  double delta = 0.0;
+  bool in_loop = false;
+  while (seq.next(P, &delta, &in_loop)) {
     if (can_skip && delta <= skip_below && delta <= P.delta_max) { ++*skipped_out; continue; }   // certified to fail: not factored
     rc = okkt_kkt_factor_trial(k, delta, nullptr);   // a failed attempt is discarded: it may stop early
     if (rc < 0) return rc;
@@ -1033,9 +1005,9 @@ static int ipopt_strategy_impl(okkt_kkt_s* k, double delta_prev, const okkt_kkt_
     *num_fac_out = num_fac;
     *delta_out = delta;
     if (rc == 1) return 1;
-    { const int rc3 = scan_after_failure(); if (rc3 < 0) return rc3; }
-    { const int rc4 = estimate_after_failure(); if (rc4 < 0) return rc4; }
-    if (delta > P.delta_max) {   // :failure
+    if ((rc = scan_after_failure()) < 0) return rc;
+    if ((rc = estimate_after_failure()) < 0) return rc;
+    if (in_loop && delta > P.delta_max) {   // :failure
       // The reference's default initialiser does not look at the status: gertz_init.jl:25-27 runs ipopt_strategy!,
       // kkt_associate_rhs! and compute_direction! whatever came back, i.e. it solves with the failed factor of the last
       // delta.  A trial that stopped early has no factor to solve with: complete it (not counted as an attempt).
@@ -1070,9 +1042,9 @@ int okkt_kkt_ipopt_strategy_eig(okkt_kkt_handle k, double delta_prev, const okkt
   return ipopt_strategy_impl(k, delta_prev, pars, true, max_steps, scaled, num_fac_out, delta_out, skipped_out, info);
 }
 
-// ipopt_strategy! with its attempts taken `width` at a time: the sequence of ipopt_strategy_impl -- the tau rule,
-// the first attempt at delta_zero, delta_inc, the delta_max exit -- is known before any attempt is factored, so a group of attempts is
-// ONE okkt_factor_batch_dev on the formed values (val_stride = 0) with the candidates as shifts.  The first attempt in sequence order
+// ipopt_strategy! with its attempts taken `width` at a time: the DeltaSeq that ipopt_strategy_impl steps is
+// known before any attempt is factored, so a group of attempts is ONE okkt_factor_batch_dev on the formed values (val_stride = 0)
+// with the candidates as shifts.  The first attempt in sequence order
 // that succeeds, or exceeds delta_max, ends the loop; its slot becomes the handle's factor.  Status, delta, the factor left behind and
 // the diagonal-dominance warnings are those of the serial loop; num_fac_out is the serial count (index of the chosen attempt + 1),
 // launches_out the batched factorisations.
@@ -1102,23 +1074,9 @@ int okkt_kkt_ipopt_strategy_batch(okkt_kkt_handle k, double delta_prev, const ok
   k->diag_dom_warnings = 0;
   double dmin = 0.0;
   if ((rc = okkt_kkt_diag_min(k, &dmin)) != OKKT_OK) return rc;
-  double tau = 1.5 * dmin;
-  double delta = P.delta_zero;
-  *delta_out = delta;
-  // the attempts in the order of ipopt_strategy_impl: (delta, inside the loop: the delta_max exit applies)
-  bool zero_first = tau > 0.0;
-  if (zero_first) tau = 0.0;
-  int it = 0;
-  auto next_attempt = [&](double* d, bool* in_loop) -> bool {
-    if (zero_first) { zero_first = false; *d = P.delta_zero; *in_loop = false; return true; }
-    if (it >= P.max_it) return false;
-    ++it;
-    if (it == 1) delta = delta_prev != 0.0 ? std::max(P.delta_min - tau, delta_prev * P.delta_dec) : P.delta_start - tau;
-    else delta = delta * P.delta_inc;
-    *d = delta;
-    *in_loop = true;
-    return true;
-  };
+  *delta_out = P.delta_zero;
+  DeltaSeq seq;
+  seq.start(dmin, delta_prev, P);
   const int64_t mm = k->kind == OKKT_KKT_SYMMETRIC ? k->m : k->kd;
   const int sym = (k->kind == OKKT_KKT_SYMMETRIC || k->kd) ? OKKT_SYM_SYMMETRIC : OKKT_SYM_DEFINITE;
   const bool zero_tol = k->kind != OKKT_KKT_SYMMETRIC && k->kd;      // the bordered Schur system counts as the Cholesky rule does (kkt_factor_impl)
@@ -1132,7 +1090,7 @@ int okkt_kkt_ipopt_strategy_batch(okkt_kkt_handle k, double delta_prev, const ok
     bool loop[64];
     int32_t flags[64];
     int g = 0;
-    while (g < width && next_attempt(&cand[g], &loop[g])) {
+    while (g < width && seq.next(P, &cand[g], &loop[g])) {
       ++g;
       if (loop[g - 1] && cand[g - 1] > P.delta_max) break;      // this attempt ends the loop whatever its inertia
     }
@@ -1150,8 +1108,7 @@ int okkt_kkt_ipopt_strategy_batch(okkt_kkt_handle k, double delta_prev, const ok
       bool chosen = flags[j] == 1;
       int status = 1;
       if (!chosen) {
-        static const bool scan = !(getenv("OKKT_DIAG_DOM_SCAN") && atoi(getenv("OKKT_DIAG_DOM_SCAN")) == 0);
-        if (scan) {
+        if (kk_diag_dom_scan_on()) {
           int32_t dom = -1;
           const int rc3 = okkt_kkt_is_diag_dom(k, &dom);
           if (rc3 < 0) return rc3;
@@ -1165,6 +1122,16 @@ int okkt_kkt_ipopt_strategy_batch(okkt_kkt_handle k, double delta_prev, const ok
       return status;
     }
   }
+}
+
+// System_rhs (system_rhs.jl:57-73) at the resident iterate (cur_Jx, cur_s, cur_y, cur_mu, cur_pen) for one triple of reduction
+// factors: grad and cons are device copies of its gradient and constraint values
+static void kk_system_rhs_launch(okkt_kkt_s* k, const double* grad, const double* cons, double eta_P, double eta_D, double eta_mu, double* rD,
+                                 double* rP, double* rC) {
+  hipStream_t st = kk_stream(k);
+  const int64_t n = k->n, m = k->m;
+  SEG_LAUNCH(k_rhs_dual_seg, k->lprJc, n, st, n, k->Jp, k->Ji, k->cur_Jx, k->cur_y, grad, (k->cur_mu * eta_mu) * k->cur_pen, 1.0 - eta_D, rD);
+  if (m) hipLaunchKernelGGL(k_rhs_pc, grid1(m), dim3(256), 0, st, m, cons, k->cur_s, k->cur_y, 1.0 - eta_P, k->cur_mu * eta_mu, rP, rC);
 }
 
 int okkt_kkt_system_rhs(okkt_kkt_handle k, const double* J_nzval_cur, const double* grad, const double* cons,
@@ -1204,11 +1171,8 @@ int okkt_kkt_system_rhs(okkt_kkt_handle k, const double* J_nzval_cur, const doub
   }
   k->tm_rhs.reset();
   const size_t e0 = k->tm_rhs.mark(st);
-  SEG_LAUNCH(k_rhs_dual_seg, k->lprJc, n, st, n, k->Jp, k->Ji, Jx, k->cur_y, k->vn1, (mu * eta_mu) * a_norm_penalty, 1.0 - eta_D, k->rD);
-  if (m) {
-    hipLaunchKernelGGL(k_rhs_pc, grid1(m), dim3(256), 0, st, m, k->vm1, k->cur_s, k->cur_y, 1.0 - eta_P, mu * eta_mu, k->rP, k->rC);
-    hipLaunchKernelGGL(k_div, grid1(m), dim3(256), 0, st, m, k->cur_y, k->cur_s, k->cur_sig);   // Sigma of the current iterate (schur_direct.jl:47)
-  }
+  kk_system_rhs_launch(k, k->vn1, k->vm1, eta_P, eta_D, eta_mu, k->rD, k->rP, k->rC);
+  if (m) hipLaunchKernelGGL(k_div, grid1(m), dim3(256), 0, st, m, k->cur_y, k->cur_s, k->cur_sig);   // Sigma of the current iterate (schur_direct.jl:47)
   const size_t e1 = k->tm_rhs.mark(st);
   k->tm_rhs.seg(0, e0, e1);
   if (n && dual_r) KK_TRY(k, hipMemcpyAsync(dual_r, k->rD, (size_t)n * 8, hipMemcpyDeviceToHost, st));
@@ -1259,6 +1223,176 @@ int okkt_kkt_set_ls_scaling(okkt_kkt_handle k, int mode, int32_t sweeps) {
   return rc < 0 ? kk_check_ls(k, rc, "okkt_kkt_set_ls_scaling") : rc;
 }
 
+// The timer laps of a direction call (tm_dir): tags 0 solve, 1 vector work, 2 N err, 3 the whole call.  Every lap is an event on the stream.
+struct DirLaps {
+  okkt_kkt_s::Timer& T;
+  hipStream_t st;
+  size_t t_begin, t_last;
+  explicit DirLaps(okkt_kkt_s* k) : T(k->tm_dir), st(kk_stream(k)) {
+    T.reset();
+    k->n_solves = 0;
+    t_begin = t_last = T.mark(st);
+  }
+  void lap(int tag) { const size_t t = T.mark(st); T.seg(tag, t_last, t); t_last = t; }
+  static void lap_of(void* self, int tag) { ((DirLaps*)self)->lap(tag); }
+  void close() { T.seg(3, t_begin, t_last); }
+};
+
+// Where a direction pass reads and writes: nrhs right-hand sides, number q of every family at its pointer + q * its stride (one
+// right-hand side: the strides stay 0)
+struct DirVecs {
+  int nrhs = 1;
+  const double *rD = nullptr, *rP = nullptr, *rC = nullptr;   // the rhs triples: strides sx, sm, sm
+  double *rhs = nullptr, *sol = nullptr, *res = nullptr;      // the linear system: rhs, the solves' target, the refinement's residual; stride sl
+  // the directions, strides sx, sm, sm.  Schur kinds: dx is sol itself (the solves accumulate into dir_x) or, with dense rows and
+  // several right-hand sides, a view of stride n that the first n entries of every solution of n + kd are compacted into
+  double *dx = nullptr, *dy = nullptr, *ds = nullptr;
+  double* red = nullptr;                                      // the maxima of the N err, stride 8
+  int64_t sx = 0, sm = 0, sl = 0;
+  // okkt_kkt_compute_directions closes the vector-work lap once more than okkt_kkt_compute_direction does (after the rounds of the
+  // Schur kinds, before the refined solve of the symmetric kind): an event each entry point has always recorded, kept
+  bool batch_laps = false;
+};
+
+// the dots that dense_dots left for right-hand side q of nrhs: pair q for the rows dy / ds take (those of factor_it, or of current_it
+// for schur_direct), pair nrhs + q for Jcsr when the two differ
+static const double* ddot_pair(const okkt_kkt_s* k, int nrhs, int q, bool of_Jcsr) {
+  const bool two = k->kind == OKKT_KKT_SCHUR_DIRECT && k->cur_Jcsr != k->Jcsr;
+  return k->ddot + (of_Jcsr && two ? nrhs + q : q) * k->kd;
+}
+
+// update_kkt_error! (p = Inf), kkt_system_solver.jl:67-96, of every direction in D: always with the matrices of factor_it
+static void kk_nerr_pass(okkt_kkt_s* k, const DirVecs& D, DirLaps& L) {
+  hipStream_t st = L.st;
+  const int64_t n = k->n, m = k->m;
+  const int64_t nbD = n ? (int64_t)seg_grid(n, k->lprJc).x : 0, nbM = m ? (int64_t)seg_grid(m, k->lprJr).x : 0;
+  for (int q = 0; q < D.nrhs; ++q) {
+    const double *dxq = D.dx + q * D.sx, *dyq = D.dy + q * D.sm, *dsq = D.ds + q * D.sm;
+    SEG_LAUNCH(k_err_dual, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, dyq, k->Hrp, k->Hrj, k->Hcsr, k->Hp, k->Hi, k->Hx, k->Hdiag, dxq, D.rD + q * D.sx, k->delta, k->part);
+    if (dense_dot_on(k))
+      SEG_LAUNCH_DR(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, dsq, dyq, k->s, k->y, D.rP + q * D.sm, D.rC + q * D.sm, k->part + nbD * 8, k->dflag,
+                    ddot_pair(k, D.nrhs, q, true));
+    else
+      SEG_LAUNCH(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, dsq, dyq, k->s, k->y, D.rP + q * D.sm, D.rC + q * D.sm, k->part + nbD * 8, NO_DR);
+    hipLaunchKernelGGL(k_err_final, dim3(1), dim3(256), 0, st, nbD, nbM, k->part, D.red + q * 8);
+  }
+  L.lap(2);
+  L.close();
+}
+
+// compute_direction! of the Schur, Schur-direct and symmetric kinds for the rhs triples of D, behind okkt_kkt_compute_direction (the
+// resident vectors) and okkt_kkt_compute_directions (the b_* buffers): the rhs of the linear system, the solves (every right-hand
+// side per sweep), dy and ds, the N err
+static int kk_direction_pass(okkt_kkt_s* k, const DirVecs& D, int32_t ItRefine_Num, DirLaps& L) {
+  hipStream_t st = L.st;
+  const int64_t n = k->n, m = k->m;
+  const int nrhs = D.nrhs;
+  int rc;
+  if (k->kind != OKKT_KKT_SYMMETRIC) {
+    // schur.jl:89-128 / schur_direct.jl:32-66 + solver_schur_rhs schur.jl:131-182.  The rhs terms, dy and ds take y, s, J of
+    // factor_it (schur) or of current_it (direct); the refinement always works on the factorised system.
+    const bool direct = k->kind == OKKT_KKT_SCHUR_DIRECT;
+    const double* ys = direct ? k->cur_y : k->y;
+    const double* ss = direct ? k->cur_s : k->s;
+    const double* sg = direct ? k->cur_sig : k->sig;
+    const double* Jc = direct ? k->cur_Jx : k->Jx;
+    const double* Jr = direct ? k->cur_Jcsr : k->Jcsr;
+    for (int q = 0; q < nrhs; ++q) {   // schur_rhs = dual_r + J' y_
+      if (m) hipLaunchKernelGGL(k_schur_t1, grid1(m), dim3(256), 0, st, m, D.rP + q * D.sm, D.rC + q * D.sm, sg, ss, k->vm1);
+      SEG_LAUNCH(k_seg_spmv, k->lprJc, n, st, n, k->Jp, k->Ji, Jc, k->vm1, (const double*)nullptr, D.rD + q * D.sx, 1.0, D.rhs + q * D.sl, NO_DR);
+    }
+    // with dense rows the system is bordered: rhs [r; 0] (rhs and res have a zero tail of kd), the solves accumulate into solutions of
+    // n + kd entries, of which the first n are dir_x
+    const int64_t kd = k->kd;
+    const bool dr = dense_dot_on(k);
+    if (n) KK_TRY(k, hipMemsetAsync(D.sol, 0, (size_t)nrhs * (n + kd) * 8, st));
+    for (int it = 0; it < ItRefine_Num; ++it) {
+      L.lap(1);
+      rc = solver_solve_enqueue(k->ls, it == 0 ? D.rhs : D.res, D.sol, nrhs, true);     // dir_x .+= ls_solve(res_old)
+      if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
+      k->n_solves += nrhs;
+      L.lap(0);
+      // the residual behind the last solve is only printed by the reference (output_level >= 4): not evaluated
+      if (it + 1 < ItRefine_Num && n) {
+        if (dr) dense_dots(k, st, k->Jcsr, nullptr, D.sol, D.sl, nrhs);
+        for (int q = 0; q < nrhs; ++q) {
+          double* xq = D.sol + q * D.sl;
+          if (dr)
+            SEG_LAUNCH_DR(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, xq, k->sig, (const double*)nullptr, 0.0, k->vm2, k->dflag, ddot_pair(k, nrhs, q, false));
+          else
+            SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, xq, k->sig, (const double*)nullptr, 0.0, k->vm2, NO_DR);   // Sigma .* (J dx)
+          SEG_LAUNCH(k_schur_resid, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, k->vm2, k->Hrp, k->Hrj, k->Hcsr, k->Hp, k->Hi, k->Hx, k->Hdiag, xq, D.rhs + q * D.sl,
+                     k->delta, D.res + q * D.sl);
+        }
+      }
+    }
+    if (D.batch_laps) L.lap(1);
+    if (D.dx != D.sol)
+      KK_TRY(k, hipMemcpy2DAsync(D.dx, (size_t)D.sx * 8, D.sol, (size_t)D.sl * 8, (size_t)n * 8, (size_t)nrhs, hipMemcpyDeviceToDevice, st));
+    // J dx with the rows dy / ds take (Jr) and with those of the N err (Jcsr): see ddot_pair
+    if (dr) dense_dots(k, st, Jr, Jr == k->Jcsr ? nullptr : k->Jcsr, D.dx, D.sx, nrhs);
+    for (int q = 0; q < nrhs; ++q) {
+      if (dr)
+        SEG_LAUNCH_DR(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, D.dx + q * D.sx, D.rP + q * D.sm, D.rC + q * D.sm, ys, ss, sg, direct ? 1 : 0,
+                      D.dy + q * D.sm, D.ds + q * D.sm, k->dflag, ddot_pair(k, nrhs, q, false));
+      else
+        SEG_LAUNCH(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, D.dx + q * D.sx, D.rP + q * D.sm, D.rC + q * D.sm, ys, ss, sg, direct ? 1 : 0,
+                   D.dy + q * D.sm, D.ds + q * D.sm, NO_DR);
+    }
+  } else {
+    // symmetric.jl:59-83
+    for (int q = 0; q < nrhs && n + m; ++q)
+      hipLaunchKernelGGL(k_sym_rhs, grid1(n + m), dim3(256), 0, st, n, m, D.rD + q * D.sx, D.rP + q * D.sm, D.rC + q * D.sm, k->y, D.rhs + q * D.sl);
+    if (k->ls_refine_steps > 0) {   // okkt_kkt_set_ls_refine
+      if (D.batch_laps) L.lap(1);
+      rc = kk_refined_solve(k, D.rhs, D.sol, nrhs, DirLaps::lap_of, &L);
+    } else {
+      L.lap(1);
+      rc = solver_solve_enqueue(k->ls, D.rhs, D.sol, nrhs, false);
+      L.lap(0);
+      k->n_solves += nrhs;
+    }
+    if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
+    for (int q = 0; q < nrhs; ++q) {
+      if (n + m) hipLaunchKernelGGL(k_sym_split, grid1(n + m), dim3(256), 0, st, n, m, D.sol + q * D.sl, D.dx + q * D.sx, D.dy + q * D.sm);
+      SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, D.dx + q * D.sx, (const double*)nullptr, D.rP + q * D.sm, -1.0, D.ds + q * D.sm, NO_DR);   // J dx - primal_r
+    }
+  }
+  L.lap(1);
+  kk_nerr_pass(k, D, L);
+  return OKKT_OK;
+}
+
+// compute_direction_implementation!(::Clever_Symmetric_KKT_solver), clever_symmetric.jl:417-492: one right-hand side, on the resident
+// vectors and the vectors of the reduced system
+static int kk_clever_direction(okkt_kkt_s* k, int32_t ItRefine_Num, DirLaps& L) {
+  hipStream_t st = L.st;
+  const int64_t n = k->n, m = k->m, mn = k->m_new, dim = n + mn;
+  if (m) hipLaunchKernelGGL(k_clever_symrhs, grid1(m), dim3(256), 0, st, m, k->rP, k->rC, k->y, k->vm1);
+  if (mn) hipLaunchKernelGGL(k_clever_crhs, grid1(mn), dim3(256), 0, st, mn, k->gptr, k->mind, k->rowg, k->vm1, k->crhs);
+  if (dim) {
+    hipLaunchKernelGGL(k_clever_rhs, grid1(dim), dim3(256), 0, st, n, mn, k->rD, k->crhs, k->Dres, k->big1);   // rescaled rhs
+    KK_TRY(k, hipMemsetAsync(k->big2, 0, (size_t)dim * 8, st));                                                  // sol
+  }
+  for (int it = 0; it < ItRefine_Num; ++it) {       // ls_solve with refinement, clever_symmetric.jl:402-415
+    if (it > 0 && dim) {
+      hipLaunchKernelGGL(k_spmv_symlower, grid1(dim), dim3(256), 0, st, dim, k->dAp, k->dAi, k->Avals, k->Arp, k->Arj, k->Armap, k->big2, k->big4);
+      hipLaunchKernelGGL(k_clever_res, grid1(dim), dim3(256), 0, st, dim, n, k->delta, k->big1, k->big4, k->big2, k->big3);
+    }
+    L.lap(1);
+    const int rc = solver_solve_enqueue(k->ls, it == 0 ? k->big1 : k->big3, k->big2, 1, true);       // sol += ls_solve(err)
+    L.lap(0);
+    ++k->n_solves;
+    if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
+  }
+  if (dim) hipLaunchKernelGGL(k_clever_unscale, grid1(dim), dim3(256), 0, st, n, mn, k->big2, k->Dres, k->dx, k->big4);   // big4 = v
+  if (m) {
+    hipLaunchKernelGGL(k_clever_y, grid1(m), dim3(256), 0, st, m, k->row_grp, k->row_ratio, k->s, k->y, k->vm1, k->crhs, k->gU, k->big4, k->dy);
+    SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, (const double*)nullptr, k->rP, -1.0, k->ds, NO_DR);   // J dx - primal_r
+  }
+  return OKKT_OK;
+}
+
 int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const double* primal_r, const double* comp_r,
                                int32_t ItRefine_Num, double* dx, double* dy, double* ds, okkt_kkt_error* err_out) {
   if (!k) return OKKT_ERR_INVALID;
@@ -1272,11 +1406,10 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
   if (!host_rhs && !k->have_rhs) return kk_fail(k, OKKT_ERR_INVALID, "no resident rhs: okkt_kkt_system_rhs has not been called");
   k->sym_dir_ok = false;
   k->clever_vecs_ok = false;
-  const bool direct = k->kind == OKKT_KKT_SCHUR_DIRECT;
-  if (direct && !k->have_cur) return kk_fail(k, OKKT_ERR_INVALID, "Schur_KKT_solver_direct reads current_it: kkt_associate_rhs! (okkt_kkt_system_rhs) has not been called");
+  if (k->kind == OKKT_KKT_SCHUR_DIRECT && !k->have_cur)
+    return kk_fail(k, OKKT_ERR_INVALID, "Schur_KKT_solver_direct reads current_it: kkt_associate_rhs! (okkt_kkt_system_rhs) has not been called");
   hipStream_t st = kk_stream(k);
   const int64_t n = k->n, m = k->m;
-  std::string e;
   if (host_rhs) {
     if (n) KK_TRY(k, hipMemcpyAsync(k->rD, dual_r, (size_t)n * 8, hipMemcpyHostToDevice, st));
     if (m) {
@@ -1285,105 +1418,24 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
     }
     k->have_rhs = true;
   }
-  okkt_kkt_s::Timer& T = k->tm_dir;
-  T.reset();
-  k->n_solves = 0;
-  const size_t t_begin = T.mark(st);
-  size_t t_last = t_begin;
-  auto lap = [&](int tag) { const size_t t = T.mark(st); T.seg(tag, t_last, t); t_last = t; };   // tags: 0 solve, 1 vector work, 2 N err
-  auto solve = [&](const double* rhs, double* sol, bool accumulate) -> int {
-    lap(1);
-    const int rc2 = solver_solve_enqueue(k->ls, rhs, sol, 1, accumulate);
-    lap(0);
-    ++k->n_solves;
-    return rc2;
-  };
+  // the resident vectors.  Schur kinds: the solves accumulate straight into dx (n + kd entries with dense rows) from vn2; symmetric: big1 -> big2
+  const bool sym = k->kind == OKKT_KKT_SYMMETRIC;
+  DirVecs D;
+  D.rD = k->rD; D.rP = k->rP; D.rC = k->rC;
+  D.rhs = sym ? k->big1 : k->vn2;
+  D.sol = sym ? k->big2 : k->dx;
+  D.res = k->kd ? k->pad_res : k->big1;
+  D.dx = k->dx; D.dy = k->dy; D.ds = k->ds;
+  D.red = k->red;
+  DirLaps L(k);
   int rc;
-  if (k->kind == OKKT_KKT_SCHUR || direct) {
-    // schur.jl:89-128 / schur_direct.jl:32-66 + solver_schur_rhs schur.jl:131-182.  The rhs terms, dy and ds take y, s, J of
-    // factor_it (schur) or of current_it (direct); the refinement always works on the factorised system.
-    const double* ys = direct ? k->cur_y : k->y;
-    const double* ss = direct ? k->cur_s : k->s;
-    const double* sg = direct ? k->cur_sig : k->sig;
-    const double* Jc = direct ? k->cur_Jx : k->Jx;
-    const double* Jr = direct ? k->cur_Jcsr : k->Jcsr;
-    if (m) hipLaunchKernelGGL(k_schur_t1, grid1(m), dim3(256), 0, st, m, k->rP, k->rC, sg, ss, k->vm1);
-    // vn2 = schur_rhs = dual_r + J' y_
-    SEG_LAUNCH(k_seg_spmv, k->lprJc, n, st, n, k->Jp, k->Ji, Jc, k->vm1, (const double*)nullptr, k->rD, 1.0, k->vn2, NO_DR);
-    // with dense rows the system is bordered: rhs [r; 0] (vn2 and pad_res have a zero tail of kd), the solves accumulate into dx of
-    // n + kd entries, of which the first n are dir_x
-    const int64_t kd = k->kd;
-    const bool dr = dense_dot_on(k);
-    double* res = kd ? k->pad_res : k->big1;
-    if (n) KK_TRY(k, hipMemsetAsync(k->dx, 0, (size_t)(n + kd) * 8, st));
-    for (int it = 0; it < ItRefine_Num; ++it) {
-      rc = solve(it == 0 ? k->vn2 : res, k->dx, true);          // dir_x .+= ls_solve(res_old)
-      if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
-      // the residual behind the last solve is only printed by the reference (output_level >= 4): not evaluated
-      if (it + 1 < ItRefine_Num && n) {
-        if (dr) {
-          dense_dots(k, st, k->Jcsr, nullptr, k->dx, 0, 1);
-          SEG_LAUNCH_DR(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, k->sig, (const double*)nullptr, 0.0, k->vm2, k->dflag, k->ddot);
-        } else {
-          SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, k->sig, (const double*)nullptr, 0.0, k->vm2, NO_DR);   // Sigma .* (J dx)
-        }
-        SEG_LAUNCH(k_schur_resid, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, k->vm2, k->Hrp, k->Hrj, k->Hcsr, k->Hp, k->Hi, k->Hx, k->Hdiag, k->dx, k->vn2,
-                   k->delta, res);
-      }
-    }
-    if (dr) {
-      // J dx with the rows dy / ds take (Jr) and with those of the N err (Jcsr): pairs 0 and, when they differ, 1
-      dense_dots(k, st, Jr, Jr == k->Jcsr ? nullptr : k->Jcsr, k->dx, 0, 1);
-      SEG_LAUNCH_DR(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, k->dx, k->rP, k->rC, ys, ss, sg, direct ? 1 : 0, k->dy, k->ds, k->dflag, k->ddot);
-    } else {
-      SEG_LAUNCH(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, k->dx, k->rP, k->rC, ys, ss, sg, direct ? 1 : 0, k->dy, k->ds, NO_DR);
-    }
-  } else if (k->kind == OKKT_KKT_CLEVER_SYMMETRIC) {
-    // compute_direction_implementation!(::Clever_Symmetric_KKT_solver), clever_symmetric.jl:417-492
-    const int64_t mn = k->m_new, dim = n + mn;
-    if (m) hipLaunchKernelGGL(k_clever_symrhs, grid1(m), dim3(256), 0, st, m, k->rP, k->rC, k->y, k->vm1);
-    if (mn) hipLaunchKernelGGL(k_clever_crhs, grid1(mn), dim3(256), 0, st, mn, k->gptr, k->mind, k->rowg, k->vm1, k->crhs);
-    if (dim) {
-      hipLaunchKernelGGL(k_clever_rhs, grid1(dim), dim3(256), 0, st, n, mn, k->rD, k->crhs, k->Dres, k->big1);   // rescaled rhs
-      KK_TRY(k, hipMemsetAsync(k->big2, 0, (size_t)dim * 8, st));                                                  // sol
-    }
-    for (int it = 0; it < ItRefine_Num; ++it) {       // ls_solve with refinement, clever_symmetric.jl:402-415
-      if (it > 0 && dim) {
-        hipLaunchKernelGGL(k_spmv_symlower, grid1(dim), dim3(256), 0, st, dim, k->dAp, k->dAi, k->Avals, k->Arp, k->Arj, k->Armap, k->big2, k->big4);
-        hipLaunchKernelGGL(k_clever_res, grid1(dim), dim3(256), 0, st, dim, n, k->delta, k->big1, k->big4, k->big2, k->big3);
-      }
-      rc = solve(it == 0 ? k->big1 : k->big3, k->big2, true);       // sol += ls_solve(err)
-      if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
-    }
-    if (dim) hipLaunchKernelGGL(k_clever_unscale, grid1(dim), dim3(256), 0, st, n, mn, k->big2, k->Dres, k->dx, k->big4);   // big4 = v
-    if (m) {
-      hipLaunchKernelGGL(k_clever_y, grid1(m), dim3(256), 0, st, m, k->row_grp, k->row_ratio, k->s, k->y, k->vm1, k->crhs, k->gU, k->big4, k->dy);
-      SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, (const double*)nullptr, k->rP, -1.0, k->ds, NO_DR);   // J dx - primal_r
-    }
-  } else {
-    // symmetric.jl:59-83
-    if (n + m) hipLaunchKernelGGL(k_sym_rhs, grid1(n + m), dim3(256), 0, st, n, m, k->rD, k->rP, k->rC, k->y, k->big1);
-    if (k->ls_refine_steps > 0) rc = kk_refined_solve(k, k->big1, k->big2, 1, [](void* c, int tag) { (*(decltype(lap)*)c)(tag); }, &lap);   // okkt_kkt_set_ls_refine
-    else rc = solve(k->big1, k->big2, false);
-    if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
-    if (n + m) hipLaunchKernelGGL(k_sym_split, grid1(n + m), dim3(256), 0, st, n, m, k->big2, k->dx, k->dy);
-    SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, (const double*)nullptr, k->rP, -1.0, k->ds, NO_DR);       // J dx - primal_r
+  if (k->kind == OKKT_KKT_CLEVER_SYMMETRIC) {
+    if ((rc = kk_clever_direction(k, ItRefine_Num, L)) != OKKT_OK) return rc;
+    L.lap(1);
+    kk_nerr_pass(k, D, L);
+  } else if ((rc = kk_direction_pass(k, D, ItRefine_Num, L)) != OKKT_OK) {
+    return rc;
   }
-  lap(1);
-  // update_kkt_error! (p = Inf), kkt_system_solver.jl:67-96: always with the matrices of factor_it
-  okkt_kkt_error E;
-  std::memset(&E, 0, sizeof(E));
-  const int64_t nbD = n ? (int64_t)seg_grid(n, k->lprJc).x : 0, nbM = m ? (int64_t)seg_grid(m, k->lprJr).x : 0;
-  SEG_LAUNCH(k_err_dual, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, k->dy, k->Hrp, k->Hrj, k->Hcsr, k->Hp, k->Hi, k->Hx, k->Hdiag, k->dx, k->rD, k->delta, k->part);
-  if (dense_dot_on(k)) {
-    const double* dd = k->ddot + (direct && k->cur_Jcsr != k->Jcsr ? k->kd : 0);   // the Jcsr pair of the dense_dots above
-    SEG_LAUNCH_DR(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, k->ds, k->dy, k->s, k->y, k->rP, k->rC, k->part + nbD * 8, k->dflag, dd);
-  } else {
-    SEG_LAUNCH(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->dx, k->ds, k->dy, k->s, k->y, k->rP, k->rC, k->part + nbD * 8, NO_DR);
-  }
-  hipLaunchKernelGGL(k_err_final, dim3(1), dim3(256), 0, st, nbD, nbM, k->part, k->red);
-  lap(2);
-  T.seg(3, t_begin, t_last);
   double red[6] = {0, 0, 0, 0, 0, 0};
   KK_TRY(k, hipMemcpyAsync(red, k->red, sizeof(red), hipMemcpyDeviceToHost, st));
   if (host_dir) {
@@ -1395,12 +1447,7 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
   }
   KK_TRY(k, hipStreamSynchronize(st));       // the only synchronisation of the call
   KK_TRY(k, hipGetLastError());
-  auto mx = [](double a, double b) { return (a != a || b != b) ? NAN : std::max(a, b); };
-  E.error_D = red[0]; E.error_P = red[2]; E.error_mu = red[3];
-  E.overall = mx(mx(red[0], red[2]), red[3]);
-  E.rhs_norm = mx(mx(red[1], red[4]), red[5]);
-  E.ratio = E.overall / E.rhs_norm;
-  if (err_out) *err_out = E;
+  if (err_out) *err_out = kkt_error_from(red);
   k->have_dir = true;
   k->have_dxnorm = false;
   k->sym_dir_ok = k->kind == OKKT_KKT_SYMMETRIC;
@@ -1408,13 +1455,12 @@ int okkt_kkt_compute_direction(okkt_kkt_handle k, const double* dual_r, const do
   return OKKT_OK;
 }
 
-
 // compute_direction! for several reduction-factor triples in ONE pass over the factor: the probe of the aggressive step
 // (Reduct_affine, take_step.jl:2-3) and the candidates of take_step2! (take_step.jl:34-66) are right-hand sides of the same
 // factorised system -- System_rhs (system_rhs.jl:57-73) is evaluated on the device for every triple from the gradient, constraint
-// values, s and y that the last okkt_kkt_system_rhs left in HBM, the triangular solves carry up to four right-hand sides per
-// sweep (okkt_solve(nrhs)), the Schur refinement rounds are batched the same way.  etas: nrhs x (eta_P, eta_D, eta_mu);
-// dx: nrhs x n, dy / ds: nrhs x m (any of the three NULL: not downloaded); err: nrhs records or NULL.
+// values, s and y that the last okkt_kkt_system_rhs left in HBM, then kk_direction_pass runs on the b_* buffers: the triangular solves
+// carry up to four right-hand sides per sweep (okkt_solve(nrhs)), the Schur refinement rounds are batched the same way.
+// etas: nrhs x (eta_P, eta_D, eta_mu); dx: nrhs x n, dy / ds: nrhs x m (any of the three NULL: not downloaded); err: nrhs records or NULL.
 int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* etas, int32_t ItRefine_Num,
                                 double* dx, double* dy, double* ds, okkt_kkt_error* err_out) {
   if (!k || !etas || nrhs < 1 || nrhs > 16) return OKKT_ERR_INVALID;
@@ -1422,13 +1468,12 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
   if (!k->factored) return kk_fail(k, OKKT_ERR_INVALID, "kkt solver not ready to compute direction!");
   if (!k->ls->factored) return kk_fail(k, OKKT_ERR_INVALID, "the last factorisation was a discarded trial of the delta loop: factor! again before a direction");
   if (!k->have_cur || !k->cur_grad) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_system_rhs (kkt_associate_rhs!) has not been called: no resident iterate");
-  const bool schur = k->kind != OKKT_KKT_SYMMETRIC, direct = k->kind == OKKT_KKT_SCHUR_DIRECT;
+  const bool schur = k->kind != OKKT_KKT_SYMMETRIC;
   hipStream_t st = kk_stream(k);
-  const int64_t n = k->n, m = k->m, dim = schur ? n : n + m;
+  const int64_t n = k->n, m = k->m;
   // the bordered Schur system (dense rows): the linear system has order n + kd; per rhs its rhs [r; 0], solution and residual have
   // that stride (b_rhs, b_sol, b_res), dir_x is compacted to stride n (b_dx) after the refinement
   const int64_t kd = k->kd, dS = n + kd;
-  const bool dr = dense_dot_on(k);
   if (k->batch_cap < nrhs) {
     const size_t c = (size_t)nrhs;
     int rc2;
@@ -1440,104 +1485,25 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
       return rc2;
     k->batch_cap = nrhs;     // the smaller buffers of an earlier call stay on the handle's allocation list until it is destroyed
   }
-  okkt_kkt_s::Timer& T = k->tm_dir;
-  T.reset();
-  k->n_solves = 0;
-  const size_t t_begin = T.mark(st);
-  size_t t_last = t_begin;
-  auto lap = [&](int tag) { const size_t t = T.mark(st); T.seg(tag, t_last, t); t_last = t; };
-  const double* Jcur = k->cur_Jx;
-  const double* ys = direct ? k->cur_y : k->y;
-  const double* ss = direct ? k->cur_s : k->s;
-  const double* sg = direct ? k->cur_sig : k->sig;
-  const double* Jc = direct ? k->cur_Jx : k->Jx;
-  const double* Jr = direct ? k->cur_Jcsr : k->Jcsr;
-  // System_rhs for every triple, then the rhs of the linear system
+  DirVecs D;
+  D.nrhs = nrhs;
+  D.rD = k->b_rD; D.rP = k->b_rP; D.rC = k->b_rC;
+  D.rhs = k->b_rhs; D.res = k->b_res;
+  D.sol = schur && !kd ? k->b_dx : k->b_sol;
+  D.dx = k->b_dx; D.dy = k->b_dy; D.ds = k->b_ds;
+  D.red = k->b_red;
+  D.sx = n; D.sm = m; D.sl = schur ? dS : n + m;
+  D.batch_laps = true;
+  DirLaps L(k);
   if (kd) {
     KK_TRY(k, hipMemsetAsync(k->b_rhs, 0, (size_t)nrhs * dS * 8, st));
     KK_TRY(k, hipMemsetAsync(k->b_res, 0, (size_t)nrhs * dS * 8, st));
   }
-  for (int q = 0; q < nrhs; ++q) {
-    const double eP = etas[3 * q], eD = etas[3 * q + 1], eM = etas[3 * q + 2];
-    double* rD = k->b_rD + (size_t)q * n; double* rP = k->b_rP + (size_t)q * m; double* rC = k->b_rC + (size_t)q * m;
-    SEG_LAUNCH(k_rhs_dual_seg, k->lprJc, n, st, n, k->Jp, k->Ji, Jcur, k->cur_y, k->cur_grad, (k->cur_mu * eM) * k->cur_pen, 1.0 - eD, rD);
-    if (m) hipLaunchKernelGGL(k_rhs_pc, grid1(m), dim3(256), 0, st, m, k->cur_cons, k->cur_s, k->cur_y, 1.0 - eP, k->cur_mu * eM, rP, rC);
-    if (schur) {
-      if (m) hipLaunchKernelGGL(k_schur_t1, grid1(m), dim3(256), 0, st, m, rP, rC, sg, ss, k->vm1);
-      SEG_LAUNCH(k_seg_spmv, k->lprJc, n, st, n, k->Jp, k->Ji, Jc, k->vm1, (const double*)nullptr, rD, 1.0, k->b_rhs + (size_t)q * dS, NO_DR);
-    } else if (dim) {
-      hipLaunchKernelGGL(k_sym_rhs, grid1(dim), dim3(256), 0, st, n, m, rD, rP, rC, k->y, k->b_rhs + (size_t)q * dim);
-    }
-  }
-  lap(1);
-  int rc;
-  if (schur) {
-    double* xs = kd ? k->b_sol : k->b_dx;       // the solves' target, stride dS
-    if (n) KK_TRY(k, hipMemsetAsync(xs, 0, (size_t)nrhs * dS * 8, st));
-    for (int it = 0; it < ItRefine_Num; ++it) {
-      rc = solver_solve_enqueue(k->ls, it == 0 ? k->b_rhs : k->b_res, xs, nrhs, true);     // dir_x .+= ls_solve(res_old), all right-hand sides per sweep
-      if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
-      k->n_solves += nrhs;
-      lap(0);
-      if (it + 1 < ItRefine_Num && n) {
-        if (dr) dense_dots(k, st, k->Jcsr, nullptr, xs, dS, nrhs);
-        for (int q = 0; q < nrhs; ++q) {
-          double* dxq = xs + (size_t)q * dS;
-          if (dr)
-            SEG_LAUNCH_DR(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, k->sig, (const double*)nullptr, 0.0, k->vm2, k->dflag, k->ddot + q * kd);
-          else
-            SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, k->sig, (const double*)nullptr, 0.0, k->vm2, NO_DR);
-          SEG_LAUNCH(k_schur_resid, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, k->vm2, k->Hrp, k->Hrj, k->Hcsr, k->Hp, k->Hi, k->Hx, k->Hdiag, dxq,
-                     k->b_rhs + (size_t)q * dS, k->delta, k->b_res + (size_t)q * dS);
-        }
-      }
-      lap(1);
-    }
-    if (kd) {
-      KK_TRY(k, hipMemcpy2DAsync(k->b_dx, (size_t)n * 8, xs, (size_t)dS * 8, (size_t)n * 8, (size_t)nrhs, hipMemcpyDeviceToDevice, st));
-      if (dr) dense_dots(k, st, Jr, Jr == k->Jcsr ? nullptr : k->Jcsr, k->b_dx, n, nrhs);   // pairs q (Jr) and nrhs + q (Jcsr, when it differs)
-    }
-    for (int q = 0; q < nrhs; ++q) {
-      if (dr)
-        SEG_LAUNCH_DR(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, k->b_dx + (size_t)q * n, k->b_rP + (size_t)q * m, k->b_rC + (size_t)q * m, ys, ss, sg,
-                      direct ? 1 : 0, k->b_dy + (size_t)q * m, k->b_ds + (size_t)q * m, k->dflag, k->ddot + q * kd);
-      else
-        SEG_LAUNCH(k_schur_dyds, k->lprJr, m, st, m, k->Jrp, k->Jrj, Jr, k->b_dx + (size_t)q * n, k->b_rP + (size_t)q * m, k->b_rC + (size_t)q * m, ys, ss, sg,
-                   direct ? 1 : 0, k->b_dy + (size_t)q * m, k->b_ds + (size_t)q * m, NO_DR);
-    }
-  } else if (k->ls_refine_steps > 0) {
-    rc = kk_refined_solve(k, k->b_rhs, k->b_sol, nrhs, [](void* c, int tag) { (*(decltype(lap)*)c)(tag); }, &lap);   // okkt_kkt_set_ls_refine
-    if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
-    for (int q = 0; q < nrhs; ++q) {
-      if (dim) hipLaunchKernelGGL(k_sym_split, grid1(dim), dim3(256), 0, st, n, m, k->b_sol + (size_t)q * dim, k->b_dx + (size_t)q * n, k->b_dy + (size_t)q * m);
-      SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->b_dx + (size_t)q * n, (const double*)nullptr, k->b_rP + (size_t)q * m, -1.0,
-                 k->b_ds + (size_t)q * m, NO_DR);
-    }
-  } else {
-    rc = solver_solve_enqueue(k->ls, k->b_rhs, k->b_sol, nrhs, false);
-    if (rc != OKKT_OK) return kk_check_ls(k, rc, "ls_solve");
-    k->n_solves += nrhs;
-    lap(0);
-    for (int q = 0; q < nrhs; ++q) {
-      if (dim) hipLaunchKernelGGL(k_sym_split, grid1(dim), dim3(256), 0, st, n, m, k->b_sol + (size_t)q * dim, k->b_dx + (size_t)q * n, k->b_dy + (size_t)q * m);
-      SEG_LAUNCH(k_seg_spmv, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, k->b_dx + (size_t)q * n, (const double*)nullptr, k->b_rP + (size_t)q * m, -1.0,
-                 k->b_ds + (size_t)q * m, NO_DR);
-    }
-  }
-  lap(1);
-  const int64_t nbD = n ? (int64_t)seg_grid(n, k->lprJc).x : 0, nbM = m ? (int64_t)seg_grid(m, k->lprJr).x : 0;
-  for (int q = 0; q < nrhs; ++q) {
-    const double* dxq = k->b_dx + (size_t)q * n; const double* dyq = k->b_dy + (size_t)q * m; const double* dsq = k->b_ds + (size_t)q * m;
-    SEG_LAUNCH(k_err_dual, k->lprJc, n, st, n, k->Jp, k->Ji, k->Jx, dyq, k->Hrp, k->Hrj, k->Hcsr, k->Hp, k->Hi, k->Hx, k->Hdiag, dxq, k->b_rD + (size_t)q * n, k->delta, k->part);
-    if (dr)
-      SEG_LAUNCH_DR(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, dsq, dyq, k->s, k->y, k->b_rP + (size_t)q * m, k->b_rC + (size_t)q * m,
-                    k->part + nbD * 8, k->dflag, k->ddot + (Jr == k->Jcsr ? q : nrhs + q) * kd);
-    else
-      SEG_LAUNCH(k_err_pc, k->lprJr, m, st, m, k->Jrp, k->Jrj, k->Jcsr, dxq, dsq, dyq, k->s, k->y, k->b_rP + (size_t)q * m, k->b_rC + (size_t)q * m, k->part + nbD * 8, NO_DR);
-    hipLaunchKernelGGL(k_err_final, dim3(1), dim3(256), 0, st, nbD, nbM, k->part, k->b_red + (size_t)q * 8);
-  }
-  lap(2);
-  T.seg(3, t_begin, t_last);
+  for (int q = 0; q < nrhs; ++q)   // System_rhs for every triple
+    kk_system_rhs_launch(k, k->cur_grad, k->cur_cons, etas[3 * q], etas[3 * q + 1], etas[3 * q + 2], k->b_rD + (size_t)q * n, k->b_rP + (size_t)q * m,
+                         k->b_rC + (size_t)q * m);
+  const int rc = kk_direction_pass(k, D, ItRefine_Num, L);
+  if (rc != OKKT_OK) return rc;
   std::vector<double> red((size_t)nrhs * 8, 0.0);
   KK_TRY(k, hipMemcpyAsync(red.data(), k->b_red, red.size() * 8, hipMemcpyDeviceToHost, st));
   if (dx && n) KK_TRY(k, hipMemcpyAsync(dx, k->b_dx, (size_t)nrhs * n * 8, hipMemcpyDeviceToHost, st));
@@ -1545,16 +1511,7 @@ int okkt_kkt_compute_directions(okkt_kkt_handle k, int32_t nrhs, const double* e
   if (ds && m) KK_TRY(k, hipMemcpyAsync(ds, k->b_ds, (size_t)nrhs * m * 8, hipMemcpyDeviceToHost, st));
   KK_TRY(k, hipStreamSynchronize(st));
   KK_TRY(k, hipGetLastError());
-  auto mx = [](double a, double b) { return (a != a || b != b) ? NAN : std::max(a, b); };
-  for (int q = 0; q < nrhs && err_out; ++q) {
-    const double* r = red.data() + (size_t)q * 8;
-    okkt_kkt_error E;
-    E.error_D = r[0]; E.error_P = r[2]; E.error_mu = r[3];
-    E.overall = mx(mx(r[0], r[2]), r[3]);
-    E.rhs_norm = mx(mx(r[1], r[4]), r[5]);
-    E.ratio = E.overall / E.rhs_norm;
-    err_out[q] = E;
-  }
+  for (int q = 0; q < nrhs && err_out; ++q) err_out[q] = kkt_error_from(red.data() + (size_t)q * 8);
   k->have_dir = false;
   k->clever_vecs_ok = false;
   k->sym_dir_ok = false;     // the resident single direction of okkt_kkt_compute_direction is not touched; the step-side kernels keep refusing until it is set

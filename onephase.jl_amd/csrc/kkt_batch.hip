@@ -177,11 +177,6 @@ inline dim3 seg_grid_b(int64_t rows, int lpr, int64_t B) { return dim3(seg_grid(
       }                                                                                                              \
   } while (0)
 
-int ki_fail(okkt_kkt_s* k, int code, const std::string& msg) { k->err = msg; return code; }
-int ki_check_ls(okkt_kkt_s* k, int rc, const char* what) {
-  if (rc < 0) k->err = std::string(what) + ": " + okkt_last_error(k->ls);
-  return rc;
-}
 const double* const kNoVec = nullptr;
 
 // why the family does not apply to the handle: the first reason in the order of the codes (okkt.h), 0 when it does
@@ -215,17 +210,17 @@ int64_t slot_doubles(const okkt_kkt_s* k) {
 
 // no device -> NO_DEVICE; not eligible -> INVALID with the reason; with need_B: a reservation of at least B
 int items_gate(okkt_kkt_s* k, const char* what, int64_t B, bool need_slots) {
-  if (!k->ls || k->ls->opts.host_symbolic_only || !k->ls->device_ready) return ki_fail(k, OKKT_ERR_NO_DEVICE, "no HIP device (host_symbolic_only handle)");
+  if (!k->ls || k->ls->opts.host_symbolic_only || !k->ls->device_ready) return kk_fail(k, OKKT_ERR_NO_DEVICE, "no HIP device (host_symbolic_only handle)");
   std::string why;
   KktItems* I = k->items;
   const bool plan_known = need_slots && I && I->B && k->ls->bt.s.arena && k->ls->bt.generation == I->ls_generation;
-  if (items_reason(k, &why, nullptr, plan_known) != OKKT_KKT_ITEMS_OK) return ki_fail(k, OKKT_ERR_INVALID, std::string(what) + ": " + why);
+  if (items_reason(k, &why, nullptr, plan_known) != OKKT_KKT_ITEMS_OK) return kk_fail(k, OKKT_ERR_INVALID, std::string(what) + ": " + why);
   if (!need_slots) return OKKT_OK;
-  if (!I || !I->B) return ki_fail(k, OKKT_ERR_INVALID, std::string(what) + ": no slots are reserved (okkt_kkt_items_reserve)");
+  if (!I || !I->B) return kk_fail(k, OKKT_ERR_INVALID, std::string(what) + ": no slots are reserved (okkt_kkt_items_reserve)");
   if (!k->ls->bt.s.arena || k->ls->bt.generation != I->ls_generation || k->ls->bt.B < I->B)
-    return ki_fail(k, OKKT_ERR_INVALID, std::string(what) + ": the linear solver's slots have been replaced since okkt_kkt_items_reserve (okkt_batch_reserve, "
+    return kk_fail(k, OKKT_ERR_INVALID, std::string(what) + ": the linear solver's slots have been replaced since okkt_kkt_items_reserve (okkt_batch_reserve, "
                                             "okkt_kkt_ipopt_strategy_batch): reserve again");
-  if (B < 1 || B > I->B) return ki_fail(k, OKKT_ERR_INVALID, std::string(what) + ": B must be in 1 .. the reserved " + std::to_string(I->B));
+  if (B < 1 || B > I->B) return kk_fail(k, OKKT_ERR_INVALID, std::string(what) + ": B must be in 1 .. the reserved " + std::to_string(I->B));
   KK_TRY(k, hipSetDevice(k->ls->device));
   return OKKT_OK;
 }
@@ -253,7 +248,7 @@ int ensure_vals(okkt_kkt_s* k, double** p, int64_t* cap, int64_t count, int64_t 
     *cap = 0;
   }
   if (!slot_alloc(I, p, (size_t)count * (size_t)nnz))
-    return ki_fail(k, OKKT_ERR_ALLOC, "okkt_kkt_items_form_system: " + std::to_string(count) + " value arrays of " + std::to_string(nnz * 8) + " bytes do not fit the device memory");
+    return kk_fail(k, OKKT_ERR_ALLOC, "okkt_kkt_items_form_system: " + std::to_string(count) + " value arrays of " + std::to_string(nnz * 8) + " bytes do not fit the device memory");
   KK_TRY(k, hipDeviceSynchronize());      // the fill ran on the null stream
   *cap = count;
   return OKKT_OK;
@@ -294,7 +289,7 @@ int factor_round(okkt_kkt_s* k, int64_t B, const std::vector<int32_t>& list, con
   const int64_t mm = k->kind == OKKT_KKT_SYMMETRIC ? k->m : 0;
   const int sym = k->kind == OKKT_KKT_SYMMETRIC ? OKKT_SYM_SYMMETRIC : OKKT_SYM_DEFINITE;
   const int rc = solver_factor_batch_device(k->ls, (int64_t)list.size(), I->S.Avals, k->nnzA, delta, k->n, k->n, mm, sym, inertia, flags, false, list.data(), B);
-  if (rc < 0) return ki_check_ls(k, rc, "batched factor");
+  if (rc < 0) return kk_check_ls(k, rc, "batched factor");
   k->t_factor_ms += k->ls->last_factor_ms;
   return OKKT_OK;
 }
@@ -347,7 +342,7 @@ int okkt_kkt_items_query(okkt_kkt_handle k, okkt_kkt_items_info* out) {
     }
     return OKKT_OK;
   } catch (...) {
-    return ki_fail(k, OKKT_ERR_INTERNAL, "unexpected exception in okkt_kkt_items_query");
+    return kk_fail(k, OKKT_ERR_INTERNAL, "unexpected exception in okkt_kkt_items_query");
   }
 }
 
@@ -358,7 +353,7 @@ int okkt_kkt_items_release(okkt_kkt_handle k) {
   kkt_items_free(k);
   if (ls_slots) {
     const int rc = okkt_batch_release(k->ls);
-    if (rc != OKKT_OK) return ki_check_ls(k, rc, "okkt_kkt_items_release");
+    if (rc != OKKT_OK) return kk_check_ls(k, rc, "okkt_kkt_items_release");
   }
   return OKKT_OK;
 }
@@ -367,12 +362,12 @@ int okkt_kkt_items_reserve(okkt_kkt_handle k, int64_t B) {
   if (!k) return OKKT_ERR_INVALID;
   int rc = items_gate(k, "okkt_kkt_items_reserve", B, false);
   if (rc != OKKT_OK) return rc;
-  if (B < 1 || B > 65535) return ki_fail(k, OKKT_ERR_INVALID, "okkt_kkt_items_reserve: B outside 1 .. 65535");
+  if (B < 1 || B > 65535) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_items_reserve: B outside 1 .. 65535");
   try {
     kkt_items_free(k);
     KK_TRY(k, hipSetDevice(k->ls->device));
     rc = okkt_batch_reserve(k->ls, B, 1);
-    if (rc != OKKT_OK) return ki_check_ls(k, rc, "okkt_kkt_items_reserve");
+    if (rc != OKKT_OK) return kk_check_ls(k, rc, "okkt_kkt_items_reserve");
     KktItems* I = new KktItems();
     k->items = I;
     KktItemSlots& S = I->S;
@@ -394,7 +389,7 @@ int okkt_kkt_items_reserve(okkt_kkt_handle k, int64_t B) {
       const int64_t bytes = slot_doubles(k) * 8;
       kkt_items_free(k);
       (void)okkt_batch_release(k->ls);
-      return ki_fail(k, OKKT_ERR_ALLOC, "okkt_kkt_items_reserve: " + std::to_string(B) + " slots of " + std::to_string(bytes) + " bytes do not fit the device memory");
+      return kk_fail(k, OKKT_ERR_ALLOC, "okkt_kkt_items_reserve: " + std::to_string(B) + " slots of " + std::to_string(bytes) + " bytes do not fit the device memory");
     }
     KK_TRY(k, hipDeviceSynchronize());      // the fills ran on the null stream
     // the LDS-staged Schur assembly asks for more dynamic LDS than the default limit allows only beyond 64 KiB: G * maxcol * 8 <= 64 KiB by construction
@@ -406,9 +401,9 @@ int okkt_kkt_items_reserve(okkt_kkt_handle k, int64_t B) {
     if ((rc = ensure_ones(k)) != OKKT_OK) return rc;
     return OKKT_OK;
   } catch (const std::bad_alloc&) {
-    return ki_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_kkt_items_reserve");
+    return kk_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_kkt_items_reserve");
   } catch (...) {
-    return ki_fail(k, OKKT_ERR_INTERNAL, "unexpected exception in okkt_kkt_items_reserve");
+    return kk_fail(k, OKKT_ERR_INTERNAL, "unexpected exception in okkt_kkt_items_reserve");
   }
 }
 
@@ -419,7 +414,7 @@ int okkt_kkt_items_form_system(okkt_kkt_handle k, int64_t B, const double* H_nzv
   if (rc != OKKT_OK) return rc;
   if ((k->nnzH > 0 && !H_nzval) || (k->nnzJ > 0 && !J_nzval)) return OKKT_ERR_INVALID;
   if ((H_stride != 0 && H_stride < k->nnzH) || (J_stride != 0 && J_stride < k->nnzJ))
-    return ki_fail(k, OKKT_ERR_INVALID, "okkt_kkt_items_form_system: a stride must be 0 (one array for every item) or at least the number of entries");
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_items_form_system: a stride must be 0 (one array for every item) or at least the number of entries");
   KktItems* I = k->items;
   KktItemSlots& S = I->S;
   items_state_reset(I);
@@ -477,7 +472,7 @@ int okkt_kkt_items_diag_min(okkt_kkt_handle k, int64_t B, double* out) {
   int rc = items_gate(k, "okkt_kkt_items_diag_min", B, true);
   if (rc != OKKT_OK) return rc;
   KktItems* I = k->items;
-  if (I->formed_B < B) return ki_fail(k, OKKT_ERR_INVALID, "form_system has not been called");
+  if (I->formed_B < B) return kk_fail(k, OKKT_ERR_INVALID, "form_system has not been called");
   hipStream_t st = kk_stream(k);
   hipLaunchKernelGGL(kb_reduce, dim3(1, (unsigned)B), dim3(1024), 0, st, k->n, I->S.schur_diag, k->n, 0, I->S.rmin, (const int*)nullptr);
   KK_TRY(k, hipMemcpyAsync(out, I->S.rmin, (size_t)B * 8, hipMemcpyDeviceToHost, st));
@@ -491,7 +486,7 @@ int okkt_kkt_items_factor(okkt_kkt_handle k, int64_t B, const double* delta, okk
   int rc = items_gate(k, "okkt_kkt_items_factor", B, true);
   if (rc != OKKT_OK) return rc;
   KktItems* I = k->items;
-  if (I->formed_B < B) return ki_fail(k, OKKT_ERR_INVALID, "kkt solver not ready to factor: form_system has not been called");
+  if (I->formed_B < B) return kk_fail(k, OKKT_ERR_INVALID, "kkt solver not ready to factor: form_system has not been called");
   try {
     I->factored_B = I->dir_B = I->solved_B = 0;
     k->t_factor_ms = 0.0;
@@ -505,7 +500,7 @@ int okkt_kkt_items_factor(okkt_kkt_handle k, int64_t B, const double* delta, okk
     I->factored_B = B;
     return OKKT_OK;
   } catch (const std::bad_alloc&) {
-    return ki_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_kkt_items_factor");
+    return kk_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_kkt_items_factor");
   }
 }
 
@@ -516,12 +511,12 @@ int okkt_kkt_items_ipopt_strategy(okkt_kkt_handle k, int64_t B, const double* de
   int rc = items_gate(k, "okkt_kkt_items_ipopt_strategy", B, true);
   if (rc != OKKT_OK) return rc;
   KktItems* I = k->items;
-  if (I->formed_B < B) return ki_fail(k, OKKT_ERR_INVALID, "kkt solver not ready to factor: form_system has not been called");
+  if (I->formed_B < B) return kk_fail(k, OKKT_ERR_INVALID, "kkt solver not ready to factor: form_system has not been called");
   try {
     okkt_kkt_pars P;
     okkt_kkt_default_pars(&P);
     if (pars) P = *pars;
-    static const bool scan = !(getenv("OKKT_DIAG_DOM_SCAN") && atoi(getenv("OKKT_DIAG_DOM_SCAN")) == 0);
+    const bool scan = kk_diag_dom_scan_on();
     hipStream_t st = kk_stream(k);
     I->factored_B = I->dir_B = I->solved_B = 0;
     k->t_factor_ms = 0.0;
@@ -543,7 +538,7 @@ int okkt_kkt_items_ipopt_strategy(okkt_kkt_handle k, int64_t B, const double* de
       // every active item's next attempt, then ONE batched factorisation over the active items
       for (const int32_t b : L.active) {
         bool lp = false;
-        if (!seq[(size_t)b].next(P, &cand[(size_t)b], &lp)) return ki_fail(k, OKKT_ERR_INTERNAL, "max it");      // error("max it"), delta_strategy.jl:113
+        if (!seq[(size_t)b].next(P, &cand[(size_t)b], &lp)) return kk_fail(k, OKKT_ERR_INTERNAL, "max it");      // error("max it"), delta_strategy.jl:113
         in_loop[(size_t)b] = lp ? 1 : 0;
       }
       if ((rc = factor_round(k, B, L.active, cand.data(), nullptr, flags.data())) != OKKT_OK) return rc;
@@ -573,7 +568,7 @@ int okkt_kkt_items_ipopt_strategy(okkt_kkt_handle k, int64_t B, const double* de
     I->factored_B = B;
     return OKKT_OK;
   } catch (const std::bad_alloc&) {
-    return ki_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_kkt_items_ipopt_strategy");
+    return kk_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_kkt_items_ipopt_strategy");
   }
 }
 
@@ -581,12 +576,12 @@ int okkt_debug_kkt_items_factor_list(okkt_kkt_handle k, int64_t B, const int32_t
   if (!k || !items || !delta || !flag_out || nitems < 1) return OKKT_ERR_INVALID;
   int rc = items_gate(k, "okkt_debug_kkt_items_factor_list", B, true);
   if (rc != OKKT_OK) return rc;
-  if (k->items->formed_B < B) return ki_fail(k, OKKT_ERR_INVALID, "kkt solver not ready to factor: form_system has not been called");
+  if (k->items->formed_B < B) return kk_fail(k, OKKT_ERR_INVALID, "kkt solver not ready to factor: form_system has not been called");
   try {
     const std::vector<int32_t> list(items, items + nitems);
     return factor_round(k, B, list, delta, nullptr, flag_out);
   } catch (const std::bad_alloc&) {
-    return ki_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_debug_kkt_items_factor_list");
+    return kk_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_debug_kkt_items_factor_list");
   }
 }
 
@@ -628,7 +623,7 @@ int okkt_kkt_items_system_rhs(okkt_kkt_handle k, int64_t B, const double* grad, 
   int rc = items_gate(k, "okkt_kkt_items_system_rhs", B, true);
   if (rc != OKKT_OK) return rc;
   KktItems* I = k->items;
-  if (I->formed_B < B) return ki_fail(k, OKKT_ERR_INVALID, "form_system has not been called");
+  if (I->formed_B < B) return kk_fail(k, OKKT_ERR_INVALID, "form_system has not been called");
   KktItemSlots& S = I->S;
   hipStream_t st = kk_stream(k);
   const int64_t n = k->n, m = k->m;
@@ -670,11 +665,11 @@ int okkt_kkt_items_compute_direction(okkt_kkt_handle k, int64_t B, int32_t ItRef
   int rc = items_gate(k, "okkt_kkt_items_compute_direction", B, true);
   if (rc != OKKT_OK) return rc;
   const bool host_dir = dx || dy || ds;
-  if (host_dir && (!dx || !dy || !ds)) return ki_fail(k, OKKT_ERR_INVALID, "dx, dy, ds: three host vectors or three NULLs");
+  if (host_dir && (!dx || !dy || !ds)) return kk_fail(k, OKKT_ERR_INVALID, "dx, dy, ds: three host vectors or three NULLs");
   KktItems* I = k->items;
-  if (I->factored_B < B) return ki_fail(k, OKKT_ERR_INVALID, "kkt solver not ready to compute direction!");  // kkt_system_solver.jl:181-183
-  if (I->rhs_B < B) return ki_fail(k, OKKT_ERR_INVALID, "no resident rhs: okkt_kkt_system_rhs has not been called");
-  if (k->ls->bt.factored_B < B) return ki_fail(k, OKKT_ERR_INVALID, "okkt_kkt_items_compute_direction: the linear solver holds no factored batch of B items");
+  if (I->factored_B < B) return kk_fail(k, OKKT_ERR_INVALID, "kkt solver not ready to compute direction!");  // kkt_system_solver.jl:181-183
+  if (I->rhs_B < B) return kk_fail(k, OKKT_ERR_INVALID, "no resident rhs: okkt_kkt_system_rhs has not been called");
+  if (k->ls->bt.factored_B < B) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_items_compute_direction: the linear solver holds no factored batch of B items");
   try {
     KktItemSlots& S = I->S;
     okkt_solver_s* ls = k->ls;
@@ -689,7 +684,7 @@ int okkt_kkt_items_compute_direction(okkt_kkt_handle k, int64_t B, int32_t ItRef
     // one solve of every item, one right-hand side each: the level-mode sweeps of the uniform batch (rhs, sol: [B][dim])
     auto solve = [&](const double* rhs, double* sol) -> int {
       const std::string e = batch_solve_enqueue(ls->N, ls->bt, OKKT_BATCH_LEVEL, B, rhs, sol, 1, 0, 1, 1);
-      if (!e.empty()) return ki_fail(k, OKKT_ERR_HIP, "ls_solve: " + e);
+      if (!e.empty()) return kk_fail(k, OKKT_ERR_HIP, "ls_solve: " + e);
       k->n_solves += (int)B;
       return OKKT_OK;
     };
@@ -735,20 +730,11 @@ int okkt_kkt_items_compute_direction(okkt_kkt_handle k, int64_t B, int32_t ItRef
     }
     KK_TRY(k, hipStreamSynchronize(st));       // the only synchronisation of the call
     KK_TRY(k, hipGetLastError());
-    auto mx = [](double a, double b) { return (a != a || b != b) ? NAN : std::max(a, b); };
-    for (int64_t b = 0; b < B && err_out; ++b) {
-      const double* r = red.data() + (size_t)b * 8;
-      okkt_kkt_error E;
-      E.error_D = r[0]; E.error_P = r[2]; E.error_mu = r[3];
-      E.overall = mx(mx(r[0], r[2]), r[3]);
-      E.rhs_norm = mx(mx(r[1], r[4]), r[5]);
-      E.ratio = E.overall / E.rhs_norm;
-      err_out[b] = E;
-    }
+    for (int64_t b = 0; b < B && err_out; ++b) err_out[b] = kkt_error_from(red.data() + (size_t)b * 8);
     I->dir_B = I->solved_B = B;
     return OKKT_OK;
   } catch (const std::bad_alloc&) {
-    return ki_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_kkt_items_compute_direction");
+    return kk_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_kkt_items_compute_direction");
   }
 }
 
@@ -757,7 +743,7 @@ int okkt_kkt_items_select(okkt_kkt_handle k, int64_t b) {
   int rc = items_gate(k, "okkt_kkt_items_select", 1, true);
   if (rc != OKKT_OK) return rc;
   KktItems* I = k->items;
-  if (b < 0 || b >= I->formed_B) return ki_fail(k, OKKT_ERR_INVALID, "okkt_kkt_items_select: b outside the items of the last okkt_kkt_items_form_system");
+  if (b < 0 || b >= I->formed_B) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_items_select: b outside the items of the last okkt_kkt_items_form_system");
   const KktItemSlots& S = I->S;
   hipStream_t st = kk_stream(k);
   const int64_t n = k->n, m = k->m;
@@ -798,7 +784,7 @@ int okkt_kkt_items_select(okkt_kkt_handle k, int64_t b) {
   if (has_fac) {
     k->delta = I->delta[(size_t)b];
     k->diag_dom_warnings = I->warnings[(size_t)b];
-    if ((rc = okkt_batch_select(k->ls, b)) != OKKT_OK) return ki_check_ls(k, rc, "okkt_kkt_items_select");
+    if ((rc = okkt_batch_select(k->ls, b)) != OKKT_OK) return kk_check_ls(k, rc, "okkt_kkt_items_select");
     k->factored = true;
   }
   return OKKT_OK;

@@ -1,15 +1,30 @@
-// The attempts of ipopt_strategy! (delta_strategy.jl:37-114) as a sequence known before any of them is factored: what the delta loop
-// over the items of a KKT batch (kkt_batch.hip) steps every item through.  Host code only, no device and no
-// handle (the sanitizer driver runs it); the expressions and their order are those of ipopt_strategy_impl (kkt.hip), so that the doubles
-// are the same.
+// The attempts of ipopt_strategy! (delta_strategy.jl:37-114) as a sequence known before any of them is factored.  All three delta loops
+// step it: the serial one and the one that factors `width` attempts at a time (kkt.hip), and the one over the
+// items of a KKT batch (kkt_batch.hip, section 8.17) -- so their doubles are the same because the code is.  Host code only, no device
+// and no handle: the sanitizer driver runs it.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
 #include "../../include/okkt.h"
 
 namespace okkt {
+
+// the reference's defaults: what okkt_kkt_default_pars hands out
+inline okkt_kkt_pars default_kkt_pars() {
+  okkt_kkt_pars P;
+  P.delta_start = 1e-6;                 // parameters.jl:147-158
+  P.delta_min = 1e-12;
+  P.delta_max = 1e50;
+  P.delta_inc = 8.0;
+  P.delta_dec = 1.0 / M_PI;
+  P.delta_zero = 0.0;
+  P.ItRefine_Num = 3;                   // parameters.jl:20
+  P.max_it = 500;                       // delta_strategy.jl:40
+  return P;
+}
 
 struct DeltaSeq {
   double tau = 0.0, delta = 0.0, delta_prev = 0.0;

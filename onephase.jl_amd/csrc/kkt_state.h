@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -140,7 +142,31 @@ struct okkt_kkt_s {
     if (e__ != hipSuccess) { (k)->err = std::string(#expr) + ": " + hipGetErrorString(e__); return OKKT_ERR_HIP; } \
   } while (0)
 
+// a refusal: the message the caller reads through okkt_kkt_last_error, and the code to return
+inline int kk_fail(okkt_kkt_s* k, int code, const std::string& msg) { k->err = msg; return code; }
+// a return code of the level-1 handle passed on: a negative one takes that handle's message along
+inline int kk_check_ls(okkt_kkt_s* k, int rc, const char* what) {
+  if (rc < 0) { k->err = std::string(what) + ": " + okkt_last_error(k->ls); }
+  return rc;
+}
+// update_kkt_error! (kkt_system_solver.jl:67-96) from the six maxima the N-err kernels reduce: (error_D, |dual_r|, error_P, error_mu,
+// |primal_r|, |comp_r|); max as Julia's, a NaN wins
+inline okkt_kkt_error kkt_error_from(const double* red) {
+  auto mx = [](double a, double b) { return (a != a || b != b) ? NAN : std::max(a, b); };
+  okkt_kkt_error E;
+  E.error_D = red[0]; E.error_P = red[2]; E.error_mu = red[3];
+  E.overall = mx(mx(red[0], red[2]), red[3]);
+  E.rhs_norm = mx(mx(red[1], red[4]), red[5]);
+  E.ratio = E.overall / E.rhs_norm;
+  return E;
+}
+
 namespace okkt {
+// OKKT_DIAG_DOM_SCAN=0 in the environment: the delta loops skip the diagonal-dominance scan after a failed attempt (read once)
+inline bool kk_diag_dom_scan_on() {
+  static const bool on = !(getenv("OKKT_DIAG_DOM_SCAN") && atoi(getenv("OKKT_DIAG_DOM_SCAN")) == 0);
+  return on;
+}
 // y = J x (m), y = J' v with the Jacobian values Jx (n), y = H x with the lower-stored H (n): on the handle's stream
 void kk_spmv_J(okkt_kkt_s* k, const double* x, double* y);
 void kk_spmv_JT(okkt_kkt_s* k, const double* Jx, const double* v, double* y);

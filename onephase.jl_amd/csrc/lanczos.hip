@@ -193,14 +193,13 @@ int64_t apply_op(okkt_kkt_s* k, LanczosWork& W, const double* x, double* y) {
   return nblk;
 }
 
-int lz_fail(okkt_kkt_s* k, int code, const std::string& msg) { k->err = msg; return code; }
 
 int lz_ensure(okkt_kkt_s* k, int steps) {
   LanczosWork* W = k->lz;
   if (W && W->base && W->n == k->n && W->m == k->m && W->steps >= steps) return OKKT_OK;
   if (!W) {
     W = new (std::nothrow) LanczosWork();
-    if (!W) return lz_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_kkt_min_eig");
+    if (!W) return kk_fail(k, OKKT_ERR_ALLOC, "out of host memory in okkt_kkt_min_eig");
     k->lz = W;
   }
   if (W->base) { (void)hipFree(W->base); W->base = nullptr; }
@@ -246,15 +245,15 @@ void lanczos_release(okkt_kkt_s* k) {
 int kk_min_eig(okkt_kkt_s* k, int32_t max_steps, double tol, int32_t scaled, okkt_kkt_eig_info* info, double* v_out) {
   if (!info) return OKKT_ERR_INVALID;
   std::memset(info, 0, sizeof(*info));
-  if (!k->ls || k->ls->opts.host_symbolic_only || !k->ls->device_ready) return lz_fail(k, OKKT_ERR_NO_DEVICE, "no HIP device (host_symbolic_only handle)");
+  if (!k->ls || k->ls->opts.host_symbolic_only || !k->ls->device_ready) return kk_fail(k, OKKT_ERR_NO_DEVICE, "no HIP device (host_symbolic_only handle)");
   if (k->kind == OKKT_KKT_CLEVER_SYMMETRIC)
-    return lz_fail(k, OKKT_ERR_INVALID, "okkt_kkt_min_eig: not for the clever-symmetric kind (its factored matrix is the merged and rescaled M, not K(delta))");
-  if (!k->formed) return lz_fail(k, OKKT_ERR_INVALID, "okkt_kkt_min_eig: okkt_kkt_form_system has not been called");
-  if (max_steps > kTriMax) return lz_fail(k, OKKT_ERR_INVALID, "okkt_kkt_min_eig: max_steps > 64");
-  if (scaled != 0 && scaled != 1) return lz_fail(k, OKKT_ERR_INVALID, "okkt_kkt_min_eig: scaled must be 0 or 1");
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_min_eig: not for the clever-symmetric kind (its factored matrix is the merged and rescaled M, not K(delta))");
+  if (!k->formed) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_min_eig: okkt_kkt_form_system has not been called");
+  if (max_steps > kTriMax) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_min_eig: max_steps > 64");
+  if (scaled != 0 && scaled != 1) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_min_eig: scaled must be 0 or 1");
   const int64_t lim = (int64_t)1 << 24;
   if (k->n >= lim || k->eig_maxlen >= lim)
-    return lz_fail(k, OKKT_ERR_INVALID, "okkt_kkt_min_eig: n, the longest row or column of J or the longest row of H reaches 2^24: rho_margin = 2^-26 rho_abs would not cover the rounding of rho");
+    return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_min_eig: n, the longest row or column of J or the longest row of H reaches 2^24: rho_margin = 2^-26 rho_abs would not cover the rounding of rho");
   const int steps_req = max_steps <= 0 ? 32 : (int)max_steps;
   const double tolv = tol > 0.0 ? tol : 0.0625;
   const int64_t n = k->n;

@@ -44,12 +44,11 @@ __global__ void k_axpb(int64_t n, double a, const double* __restrict__ x, double
   ld_axpb(n, a, x, b, o, recip);
 }
 
-int ls_fail(okkt_kkt_s* k, int code, const char* msg) { k->err = msg; return code; }
 
 int ls_ready(okkt_kkt_s* k, bool need_dir) {
   if (!k) return OKKT_ERR_INVALID;
-  if (!k->formed) return ls_fail(k, OKKT_ERR_INVALID, "okkt_kkt_form_system has not been called");
-  if (need_dir && !k->have_dir) return ls_fail(k, OKKT_ERR_INVALID, "no direction: call okkt_kkt_compute_direction for this system first");
+  if (!k->formed) return kk_fail(k, OKKT_ERR_INVALID, "okkt_kkt_form_system has not been called");
+  if (need_dir && !k->have_dir) return kk_fail(k, OKKT_ERR_INVALID, "no direction: call okkt_kkt_compute_direction for this system first");
   KK_TRY(k, hipSetDevice(k->ls->device));
   if (!k->ls_part) {
     auto grab = [&](size_t count, double** out) -> int {

@@ -85,7 +85,6 @@ __global__ void kb_ls_axpb(int64_t len, KktLsSlots L, int64_t B, const double* _
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-int lb_fail(okkt_kkt_s* k, int code, const std::string& msg) { k->err = msg; return code; }
 inline int ls_blocks(int64_t len) { return (int)std::min<int64_t>(kLsMaxBlocks, (len + 1023) / 1024); }
 inline dim3 grid1b(int64_t n, int64_t nl) { return dim3((unsigned)std::max<int64_t>(1, (n + 255) / 256), (unsigned)nl); }
 
@@ -121,7 +120,7 @@ int ensure_ls_slots(okkt_kkt_s* k, const char* what) {
                   ls_alloc(I, &L.sn[0], b * n) && ls_alloc(I, &L.sn[1], b * n) && ls_alloc(I, &L.part, b * kLsMaxBlocks * 8) && ls_alloc(I, &L.out, b * 8) &&
                   ls_alloc(I, &L.scal, b * kLsScalars) && ls_alloc(I, &L.list, b);
   if (!ok)      // what was allocated stays in the reservation's list and goes with it
-    return lb_fail(k, OKKT_ERR_ALLOC, std::string(what) + ": the line-search slots of " + std::to_string(I->B) + " items (" + std::to_string(ls_slot_doubles(k) * 8) +
+    return kk_fail(k, OKKT_ERR_ALLOC, std::string(what) + ": the line-search slots of " + std::to_string(I->B) + " items (" + std::to_string(ls_slot_doubles(k) * 8) +
                                           " bytes each) do not fit the device memory");
   L.ready = true;
   return OKKT_OK;
@@ -134,19 +133,19 @@ int ls_begin(okkt_kkt_s* k, const char* what, int64_t B, const int32_t* items, i
   if (rc != OKKT_OK) return rc;
   KktItems* I = k->items;
   const std::string w(what);
-  if (I->formed_B < 1) return lb_fail(k, OKKT_ERR_INVALID, w + ": okkt_kkt_items_form_system has not been called");
-  if (B > I->formed_B) return lb_fail(k, OKKT_ERR_INVALID, w + ": B above the " + std::to_string(I->formed_B) + " items of the last okkt_kkt_items_form_system");
+  if (I->formed_B < 1) return kk_fail(k, OKKT_ERR_INVALID, w + ": okkt_kkt_items_form_system has not been called");
+  if (B > I->formed_B) return kk_fail(k, OKKT_ERR_INVALID, w + ": B above the " + std::to_string(I->formed_B) + " items of the last okkt_kkt_items_form_system");
   if (B > I->dir_B)
-    return lb_fail(k, OKKT_ERR_INVALID, "no direction: call okkt_kkt_items_compute_direction or okkt_kkt_items_set_direction for " + std::to_string(B) + " items first (" +
+    return kk_fail(k, OKKT_ERR_INVALID, "no direction: call okkt_kkt_items_compute_direction or okkt_kkt_items_set_direction for " + std::to_string(B) + " items first (" +
                                             std::to_string(I->dir_B) + " hold one)");
   c->k = k; c->I = I; c->what = what; c->B = B;
   if (items) {
-    if (nitems < 0 || nitems > B) return lb_fail(k, OKKT_ERR_INVALID, w + ": nitems outside 0 .. B");
+    if (nitems < 0 || nitems > B) return kk_fail(k, OKKT_ERR_INVALID, w + ": nitems outside 0 .. B");
     std::vector<char> seen((size_t)B, 0);
     for (int64_t q = 0; q < nitems; ++q) {
       const int32_t b = items[q];
-      if (b < 0 || b >= B) return lb_fail(k, OKKT_ERR_INVALID, w + ": item " + std::to_string(b) + " outside 0 .. B-1");
-      if (seen[(size_t)b]) return lb_fail(k, OKKT_ERR_INVALID, w + ": item " + std::to_string(b) + " is listed twice");
+      if (b < 0 || b >= B) return kk_fail(k, OKKT_ERR_INVALID, w + ": item " + std::to_string(b) + " outside 0 .. B-1");
+      if (seen[(size_t)b]) return kk_fail(k, OKKT_ERR_INVALID, w + ": item " + std::to_string(b) + " is listed twice");
       seen[(size_t)b] = 1;
     }
     c->slots.assign(items, items + nitems);
@@ -213,8 +212,8 @@ int ensure_dx_norms(LsCall& c) {
   return OKKT_OK;
 }
 
-int bad_stride(okkt_kkt_s* k, const char* what) { return lb_fail(k, OKKT_ERR_INVALID, std::string(what) + ": frac_stride must be 0 (one vector for every item) or m"); }
-int null_array(okkt_kkt_s* k, const char* what) { return lb_fail(k, OKKT_ERR_INVALID, std::string(what) + ": a required array is NULL"); }
+int bad_stride(okkt_kkt_s* k, const char* what) { return kk_fail(k, OKKT_ERR_INVALID, std::string(what) + ": frac_stride must be 0 (one vector for every item) or m"); }
+int null_array(okkt_kkt_s* k, const char* what) { return kk_fail(k, OKKT_ERR_INVALID, std::string(what) + ": a required array is NULL"); }
 
 }  // namespace
 
@@ -246,8 +245,8 @@ int okkt_kkt_items_set_direction(okkt_kkt_handle k, int64_t B, const double* dx,
   int rc = kkt_items_gate(k, what, B);
   if (rc != OKKT_OK) return rc;
   KktItems* I = k->items;
-  if (I->formed_B < 1) return lb_fail(k, OKKT_ERR_INVALID, std::string(what) + ": okkt_kkt_items_form_system has not been called");
-  if (B > I->formed_B) return lb_fail(k, OKKT_ERR_INVALID, std::string(what) + ": B above the " + std::to_string(I->formed_B) + " items of the last okkt_kkt_items_form_system");
+  if (I->formed_B < 1) return kk_fail(k, OKKT_ERR_INVALID, std::string(what) + ": okkt_kkt_items_form_system has not been called");
+  if (B > I->formed_B) return kk_fail(k, OKKT_ERR_INVALID, std::string(what) + ": B above the " + std::to_string(I->formed_B) + " items of the last okkt_kkt_items_form_system");
   const int64_t n = k->n, m = k->m;
   if ((n > 0 && !dx) || (m > 0 && (!dy || !ds))) return null_array(k, what);
   hipStream_t st = kk_stream(k);
@@ -294,7 +293,7 @@ int okkt_kkt_items_max_step_primal(okkt_kkt_handle k, int64_t B, const int32_t* 
     }
     return OKKT_OK;
   } catch (const std::bad_alloc&) {
-    return lb_fail(k, OKKT_ERR_ALLOC, std::string("out of host memory in ") + what);
+    return kk_fail(k, OKKT_ERR_ALLOC, std::string("out of host memory in ") + what);
   }
 }
 
@@ -327,7 +326,7 @@ int okkt_kkt_items_s_bound_ok(okkt_kkt_handle k, int64_t B, const int32_t* items
     for (const int32_t b : c.slots) ok[b] = out[(size_t)b * 8] == 1.0 ? 1 : 0;
     return OKKT_OK;
   } catch (const std::bad_alloc&) {
-    return lb_fail(k, OKKT_ERR_ALLOC, std::string("out of host memory in ") + what);
+    return kk_fail(k, OKKT_ERR_ALLOC, std::string("out of host memory in ") + what);
   }
 }
 
@@ -397,7 +396,7 @@ int okkt_kkt_items_dual_step_range(okkt_kkt_handle k, int64_t B, const int32_t* 
     for (const int32_t b : c.slots) dual_range_finish(out.data() + (size_t)b * 8, lb_out + b, ub_out + b);
     return OKKT_OK;
   } catch (const std::bad_alloc&) {
-    return lb_fail(k, OKKT_ERR_ALLOC, std::string("out of host memory in ") + what);
+    return kk_fail(k, OKKT_ERR_ALLOC, std::string("out of host memory in ") + what);
   }
 }
 
@@ -455,7 +454,7 @@ int okkt_kkt_items_predicted_reduction(okkt_kkt_handle k, int64_t B, const int32
     }
     return OKKT_OK;
   } catch (const std::bad_alloc&) {
-    return lb_fail(k, OKKT_ERR_ALLOC, std::string("out of host memory in ") + what);
+    return kk_fail(k, OKKT_ERR_ALLOC, std::string("out of host memory in ") + what);
   }
 }
 
@@ -477,7 +476,7 @@ int okkt_kkt_items_dual_step(okkt_kkt_handle k, int64_t B, const int32_t* items,
       return null_array(k, what);
     const bool own_J = J_nzval_cand && k->nnzJ;
     if (own_J && J_stride != 0 && J_stride < k->nnzJ)
-      return lb_fail(k, OKKT_ERR_INVALID, std::string(what) + ": J_stride must be 0 (one array for every item) or at least the number of entries");
+      return kk_fail(k, OKKT_ERR_INVALID, std::string(what) + ": J_stride must be 0 (one array for every item) or at least the number of entries");
     if (c.nl == 0) return OKKT_OK;
     KktItems* I = c.I;
     KktItemSlots& S = I->S;
@@ -490,7 +489,7 @@ int okkt_kkt_items_dual_step(okkt_kkt_handle k, int64_t B, const int32_t* items,
       if (L.Jcand_cap < need) {
         L.Jcand_cap = 0;
         if (!ls_alloc(I, &L.Jcand, (size_t)need * (size_t)k->nnzJ))
-          return lb_fail(k, OKKT_ERR_ALLOC, std::string(what) + ": " + std::to_string(need) + " arrays of " + std::to_string(k->nnzJ * 8) + " bytes do not fit the device memory");
+          return kk_fail(k, OKKT_ERR_ALLOC, std::string(what) + ": " + std::to_string(need) + " arrays of " + std::to_string(k->nnzJ * 8) + " bytes do not fit the device memory");
         L.Jcand_cap = need;
       }
       const size_t row = (size_t)k->nnzJ * 8;
@@ -545,7 +544,7 @@ int okkt_kkt_items_dual_step(okkt_kkt_handle k, int64_t B, const int32_t* items,
     }
     return OKKT_OK;
   } catch (const std::bad_alloc&) {
-    return lb_fail(k, OKKT_ERR_ALLOC, std::string("out of host memory in ") + what);
+    return kk_fail(k, OKKT_ERR_ALLOC, std::string("out of host memory in ") + what);
   }
 }
 
